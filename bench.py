@@ -1,9 +1,24 @@
 #!/usr/bin/env python3
 """AC/TC scoring throughput on MI355X -- BASELINE.json's metric on its configs[1] workload.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run (the default `score` workload without --full) does only what the headline figure needs: setup, W warm-up
+steps, K timed steps, the --dump-outputs files, and one JSON line with `metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step` (wall milliseconds per timed step) and the workload's description.  Everything else described
+below -- the CPU baseline, the oracle comparison (`precision`), the f16 `throughput_mode` run, the per-stage timings
+and rooflines (extra untimed steps and standalone launches), the bit-equality check of the last step against the
+first, and the nested config-3 `e2e` record -- is measured only with --full, which prints the same line with those
+records added.  The other workloads (--workload e2e / tag / cfg5) are not part of the plain run and measure what they
+always did, with or without --full.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step computed: `ac.npy` (per-video AC, float32)
+and `tc.npy` (per-video TC, float64) from the pinned host buffers the step fills, and `seq_embed.npy` / `tc_windows.npy`
+(float32), the per-window sequence embeddings and TC terms the encoder wrote for them.  An array over its share of the
+64 MB limit is stored as a fixed, seeded sample of its rows.  The inputs (vge.synth clips, weights, real set) are
+generated from fixed seeds, so two runs with the same arguments score identical inputs.
 
 Workload (config 2 of BASELINE.json, "1 MI355X bf16"): 256 synthetic 32-frame clips per GPU with
 pre-extracted per-frame features (SMPL rotations, betas, 1024-d token, 120-d keypoints) resident in
@@ -35,7 +50,7 @@ eval.py in the reference's structure (DataLoader workers=4, bs 32, torch-fp32 on
 this host on a bounded sample before the GPU is touched.  `--workload cfg5` runs config 5 (10k 64-frame
 clips, strong scaling); `tag` config 4's flow; `e2e` config 3.
 
-At N = 1 the default line also carries `e2e`: BASELINE config 3 (1k clips x 32 frames at 256x256: the Faster R-CNN
+With --full at N = 1 the line also carries `e2e`: BASELINE config 3 (1k clips x 32 frames at 256x256: the Faster R-CNN
 gate + TokenHMR and YOLOX + DWPose extractors -> featurise -> encoder -> AC/TC; bench_e2e.py) as one timed step after
 one warm-up, run in a child process after the config-2 measurements, with its own stage_ms, the ViT-H GEMM and gate
 detector rooflines, PMC traffic and CPU baseline (`--no-e2e` skips it).
@@ -310,6 +325,34 @@ def launch_command(args, env, argv, port=None):
             str(Path(__file__).resolve()), *argv]
 
 
+def plain_run(args) -> bool:
+    """The default `score` workload without --full: setup, warm-up, the timed steps, --dump-outputs, the line."""
+    return args.workload == "score" and not args.full
+
+
+def dump_outputs(out_dir, arrays: dict, rank: int = 0, world: int = 1, limit_bytes: int = 64_000_000) -> dict:
+    """--dump-outputs: `arrays` ({name: float32 / float64 ndarray}) as out_dir/<name>.npy (ranks other than 0 of a
+    multi-rank run: <name>.rank<r>.npy), at most `limit_bytes` in all: an array over its equal share of the limit is
+    stored as a sample of its rows drawn by a generator with a fixed seed (the same rows in every run).  -> {name:
+    {"shape", "dtype", "sampled_rows"}} for the result line."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    share = limit_bytes // max(1, len(arrays))
+    info = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        rows = None
+        if a.nbytes > share:
+            keep = max(1, share // max(1, a.nbytes // a.shape[0]))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+            a = a[rows]
+        np.save(out_dir / (f"{name}.npy" if world == 1 or rank == 0 else f"{name}.rank{rank}.npy"), a)
+        info[name] = {"shape": list(a.shape), "dtype": str(a.dtype),
+                      "sampled_rows": None if rows is None else int(rows.size)}
+    return info
+
+
 def launch_ranks(args, cmd) -> int:
     """Parent of a self-launched N-rank run: the CPU baseline first (this process never touches the GPU: it
     is measured on the host before any rank starts, and handed to rank 0 in the environment), then torchrun as a
@@ -317,7 +360,7 @@ def launch_ranks(args, cmd) -> int:
     rank 0's JSON line goes straight to this process's stdout.  Returns the children's exit status."""
     import subprocess
     env = dict(os.environ)
-    if args.workload in ("score", "tag", "cfg5") and not args.no_cpu_baseline:
+    if args.workload in ("score", "tag", "cfg5") and not args.no_cpu_baseline and not plain_run(args):
         if args.workload == "score":
             cpu = cpu_baseline(args.cpu_seconds)
         elif args.workload == "cfg5":
@@ -331,17 +374,24 @@ def launch_ranks(args, cmd) -> int:
     return subprocess.run(cmd, env=env).returncode
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
                     help="GPUs (ranks) of this node.  Without torchrun's WORLD_SIZE and N > 1, bench.py launches N ranks "
                          "itself (torch.distributed.run as a child process, before any GPU call); under torchrun it "
                          "must equal WORLD_SIZE")
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (ms_per_step = their wall time / this)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--clips", type=int, default=256, help="32-frame clips per GPU per step (config 2: 256)")
+    ap.add_argument("--full", action="store_true",
+                    help="score: beside the headline figure, measure everything else the line can carry -- the CPU "
+                         "baseline, the oracle comparison, the f16 throughput mode, per-stage timings and rooflines, "
+                         "and at N = 1 the nested config-3 record (minutes; a plain run skips all of it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="score/cfg5: after the timed steps, write the last timed step's outputs to DIR/<name>.npy "
+                         "(ac, tc, seq_embed, tc_windows; at most 64 MB, larger arrays as a seeded row sample)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full and the other workloads: skip it")
     ap.add_argument("--compute", default=None, choices=["f32x3", "f32", "f16"],
                     help="f32x3: 3xfp16 split-precision MFMA (f32-class, default of score/tag/e2e); f32: exact f32 "
                          "MFMA; f16: single-fp16 MFMA throughput mode (default of cfg5)")
@@ -391,10 +441,11 @@ def main():
                          "scores (bench_e2e.py; --clips defaults to 8 there); tag: config 4 on pre-extracted "
                          "features, the full sharded eval flow over 300 videos (bench_tag.py); cfg5: config 5, --clips "
                          "(default 10000) 64-frame clips sharded over the ranks, f16 MFMA path by default")
-    args = ap.parse_args()
-    cmd = launch_command(args, os.environ, sys.argv[1:])
-    if cmd is not None:
-        sys.exit(launch_ranks(args, cmd))
+    return ap.parse_args(argv)
+
+
+def apply_defaults(args):
+    """The workload-dependent defaults of a rank's arguments (compute mode, config 5's clip count, pipeline)."""
     if args.compute is None:
         args.compute = "f16" if args.workload == "cfg5" else "f32x3"
     if args.workload == "cfg5" and args.compute == "f16":
@@ -405,10 +456,19 @@ def main():
         args.clips = 10_000
     if args.pipeline is None:
         args.pipeline = "serial"
+    return args
+
+
+def main():
+    args = parse_args()
+    cmd = launch_command(args, os.environ, sys.argv[1:])
+    if cmd is not None:
+        sys.exit(launch_ranks(args, cmd))
+    apply_defaults(args)
 
     cpu = json.loads(os.environ["VGE_BENCH_CPU_BASELINE"]) if os.environ.get("VGE_BENCH_CPU_BASELINE") else None
     if cpu is None and args.workload in ("score", "cfg5") and int(os.environ.get("WORLD_SIZE", "1")) == 1 and \
-            not args.no_cpu_baseline:
+            not args.no_cpu_baseline and not plain_run(args):
         # before the GPU is initialised: its DataLoader workers are forked
         cpu = cpu_baseline(args.cpu_seconds, T=64 if args.workload == "cfg5" else CLIP_LEN)
     if cpu is None and args.workload == "tag" and int(os.environ.get("WORLD_SIZE", "1")) == 1 and \
@@ -437,18 +497,19 @@ def main():
             dist.destroy_process_group()
         return
     out = run_score(args, world, rank, dev)
-    if args.workload == "score" and args.compute == "f32x3" and not args.no_throughput_mode:
+    if args.full and args.workload == "score" and args.compute == "f32x3" and not args.no_throughput_mode:
         # the fp16-operand throughput mode on the same workload, reported nested beside the f32-class headline
         import copy
         pa = copy.copy(args)
-        pa.compute, pa.steps, pa.warmup = "f16", max(5, args.steps // 2), 2
+        pa.compute, pa.steps, pa.warmup, pa.dump_outputs = "f16", max(5, args.steps // 2), 2, None
         thr = run_score(pa, world, rank, dev)
         if rank == 0:
             out["throughput_mode"] = {k: thr[k] for k in ("dtype", "value", "ms_per_step", "steps", "precision",
                                                           "roofline", "stage_ms")}
     if rank == 0:
-        out["cpu_baseline"] = cpu
-        if args.workload == "score" and world == 1 and not args.no_e2e:
+        if not plain_run(args):
+            out["cpu_baseline"] = cpu
+        if args.full and args.workload == "score" and world == 1 and not args.no_e2e:
             out["e2e"] = run_e2e_child(args)
         print(json.dumps(out))
     if world > 1:
@@ -598,6 +659,7 @@ def run_score(args, world, rank, dev):
     from vge.data import ACTION_CLASSES, pack_frame_store
     from vge.dist import shard, shard_bounds
     cfg5 = args.workload == "cfg5"
+    lean = plain_run(args)  # only what the headline figure needs: no oracle pass, no untimed profiling steps
     T = 64 if cfg5 else CLIP_LEN
     starts = list(range(0, T - CLIP_LEN + 1, 8))
     if cfg5:
@@ -765,12 +827,15 @@ def run_score(args, world, rank, dev):
         return ac, tc
 
     # precision evidence for the timed mode: the untimed first step's scores vs the oracle on a sample of clips
-    ac_a, tc_a = step(flush=True)
-    torch.cuda.synchronize()  # the scores may come from the tail stream
-    ac_a, tc_a = ac_a.clone(), tc_a.clone()  # (--host-scores direct: the pinned buffers every step rewrites)
-    precision = oracle_precision(gen_clips, stats.mean, stats.std, centroids, vcls, seq, ac_a, tc_a, starts,
-                                 n=16 if cfg5 else V) if rank == 0 else None
-    torch.cuda.synchronize()
+    precision = None
+    if not lean:
+        ac_a, tc_a = step(flush=True)
+        torch.cuda.synchronize()  # the scores may come from the tail stream
+        ac_a, tc_a = ac_a.clone(), tc_a.clone()  # (--host-scores direct: the pinned buffers every step rewrites)
+        if rank == 0:
+            precision = oracle_precision(gen_clips, stats.mean, stats.std, centroids, vcls, seq, ac_a, tc_a, starts,
+                                         n=16 if cfg5 else V)
+        torch.cuda.synchronize()
     setup_s = time.perf_counter() - t_setup
 
     for k in range(args.warmup):
@@ -779,7 +844,7 @@ def run_score(args, world, rank, dev):
     # inside the timed steps only the conv stage's two events are recorded (each event is a queue marker: all six
     # stage markers measured -1.3 % videos/s); the other stages are timed on untimed steps afterwards
     enc.profile_mask(0x3)
-    enc.profile_begin(args.steps * n_chunks)
+    enc.profile_begin(-(-args.steps // args.event_every) * n_chunks)  # (the steps that record events)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -798,6 +863,48 @@ def run_score(args, world, rank, dev):
     # every rank's (wall time, videos): the line's time is the max over ranks, `value` all ranks' videos / that time
     per_rank = gather_rank_times(dt, V, world, dev)
     dt = max(t for t, _ in per_rank)
+    assert np.isfinite(host_ac.numpy()).all() and np.isfinite(host_tc.numpy()).all()
+    sq_last, tw_last = (seq_b[(n_step[0] - 1) % 2], tcw_b[(n_step[0] - 1) % 2]) if mode in ("side2", "side3") else (seq, tcw)
+    dumped = None
+    if args.dump_outputs and args.steps > 0:
+        # what the last timed step handed to its caller: the per-video scores in the pinned host buffers, and the
+        # per-window embeddings / TC terms the encoder wrote for them
+        dumped = dump_outputs(args.dump_outputs, {"ac": host_ac.numpy(), "tc": host_tc.numpy(),
+                                                  "seq_embed": sq_last.cpu().numpy(),
+                                                  "tc_windows": tw_last.cpu().numpy()}, rank, world)
+    total_videos = sum(v for _, v in per_rank) * args.steps
+    if cfg5:
+        workload = (f"BASELINE config 5: {args.clips} synthetic 64-frame clips (5 windows each) sharded over "
+                    f"{world} GPU(s), fusion-encoder fwd + AC/TC, pre-extracted features resident in HBM, "
+                    f"{args.compute} MFMA path")
+    else:
+        workload = ("BASELINE config 2: fusion-encoder fwd + AC/TC metrics, 256 clips x 32 frames per GPU, "
+                    "pre-extracted features resident in HBM (featurise included in the step)")
+    line = {
+        "metric": METRIC,
+        "value": total_videos / dt,
+        "unit": "videos/s",
+        "n_gpus": world,
+        "ranks_seen": len(per_rank),
+        "per_rank_videos_per_s": [v * args.steps / t for t, v in per_rank],
+        "backend": dist.get_backend() if dist.is_initialized() else None,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong" if cfg5 else "weak",
+        "vs_baseline": None,
+        "dtype": args.compute,
+        "data": "synthetic (deterministic generator vge.synth: quaternion-walk SMPL rotations, N(0,1) betas/tokens, "
+                "U[0,1] keypoints with 5% invisible; random-init weights of the reference architecture)",
+        "config": {"workload": workload, "clips_per_gpu": V, "frames_per_clip": T, "windows_per_step_per_gpu": NW,
+                   "windows_per_encode": CH, "parallelism": f"video-sharded x{world}"},
+        "setup_s": setup_s,
+    }
+    if dumped is not None:
+        line["dumped_outputs"] = dumped
+    if lean:
+        return line if rank == 0 else None
     stage_ms, ncalls = enc.profile_read()
     n_extra = 5
     enc.profile_mask(0x3F)
@@ -845,38 +952,12 @@ def run_score(args, world, rank, dev):
         kname = F16_X3S_KNAME
     pk = device_peaks()
     peak = {"f16": pk["f16"], "f32x3": pk["f16"] / 3, "f32": pk["f32"]}[args.compute]
-    total_videos = sum(v for _, v in per_rank) * args.steps
-    if cfg5:
-        workload = (f"BASELINE config 5: {args.clips} synthetic 64-frame clips (5 windows each) sharded over "
-                    f"{world} GPU(s), fusion-encoder fwd + AC/TC, pre-extracted features resident in HBM, "
-                    f"{args.compute} MFMA path")
-    else:
-        workload = ("BASELINE config 2: fusion-encoder fwd + AC/TC metrics, 256 clips x 32 frames per GPU, "
-                    "pre-extracted features resident in HBM (featurise included in the step)")
-    return {
-        "metric": METRIC,
-        "value": total_videos / dt,
-        "unit": "videos/s",
-        "n_gpus": world,
-        "ranks_seen": len(per_rank),
-        "per_rank_videos_per_s": [v * args.steps / t for t, v in per_rank],
-        "backend": dist.get_backend() if dist.is_initialized() else None,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "strong" if cfg5 else "weak",
-        "vs_baseline": None,
-        "dtype": args.compute,
+    line.update({
         "precision": {"arith": ARITH[args.compute] if not (args.compute == "f16" and
                                                              os.environ.get("VGE_F16_MIX", "2") == "0") else
                       ARITH["f16"].replace("transformer: 3xfp16 split (VGE_F16 default)",
                                            "transformer: fp16 too (VGE_F16_MIX=0)"), **precision,
                       "last_step_equals_first": last_equals_first},
-        "data": "synthetic (deterministic generator vge.synth: quaternion-walk SMPL rotations, N(0,1) betas/tokens, "
-                "U[0,1] keypoints with 5% invisible; random-init weights of the reference architecture)",
-        "config": {"workload": workload, "clips_per_gpu": V, "frames_per_clip": T, "windows_per_step_per_gpu": NW,
-                   "windows_per_encode": CH, "parallelism": f"video-sharded x{world}"},
         "roofline": {"bound": "mfma", "kernel": kname,
                      "achieved": achieved, "peak": peak, "peak_source": pk["source"], "unit": "TFLOP/s",
                      "frac": achieved / peak, "traffic": pmc_traffic(args.compute, CH),
@@ -892,8 +973,8 @@ def run_score(args, world, rank, dev):
                                      "achieved_GBs": FEAT_BYTES_PER_WINDOW * b1 / (feat_alone_ms * 1e-3) / 1e9,
                                      "source": "10 launches on the current stream after the timed steps, hipEvents"}},
         "encoder_tflops_2.0203GF_per_window": ENCODER_FLOP_PER_WINDOW * NW * args.steps / dt / 1e12,
-        "setup_s": setup_s,
-    }
+    })
+    return line
 
 if __name__ == "__main__":
     main()

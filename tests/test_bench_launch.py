@@ -19,7 +19,7 @@ def _bench():
 
 
 def _args(**kw):
-    a = dict(gpus=None, workload="score", no_cpu_baseline=True, cpu_seconds=1.0)
+    a = dict(gpus=None, workload="score", no_cpu_baseline=True, cpu_seconds=1.0, full=False)
     a.update(kw)
     return SimpleNamespace(**a)
 
@@ -51,15 +51,63 @@ def test_under_torchrun_world_size_must_match():
 
 
 def test_parent_measures_cpu_baseline_and_hands_it_to_the_ranks(monkeypatch):
-    """The parent runs the CPU baseline (no GPU in this process) and passes it to the children in the environment;
-    its exit status is the children's."""
+    """With --full the parent runs the CPU baseline (no GPU in this process) and passes it to the children in the
+    environment; its exit status is the children's."""
     b = _bench()
     monkeypatch.setattr(b, "cpu_baseline", lambda s: {"value": 1.5, "unit": "videos/s", "cores": 3})
     probe = [sys.executable, "-c", "import json, os, sys; d = json.loads(os.environ['VGE_BENCH_CPU_BASELINE']); "
                                    "sys.exit(0 if d['cores'] == 3 else 5)"]
-    assert b.launch_ranks(_args(gpus=2, no_cpu_baseline=False), probe) == 0
-    assert b.launch_ranks(_args(gpus=2, no_cpu_baseline=False),
+    assert b.launch_ranks(_args(gpus=2, no_cpu_baseline=False, full=True), probe) == 0
+    assert b.launch_ranks(_args(gpus=2, no_cpu_baseline=False, full=True),
                           [sys.executable, "-c", "import sys; sys.exit(7)"]) == 7
+
+
+def test_plain_run_measures_no_cpu_baseline(monkeypatch):
+    """Without --full the parent of a multi-rank `score` run starts its ranks at once: no CPU baseline is measured or
+    handed on; the other workloads keep theirs."""
+    b = _bench()
+
+    def never(*a, **k):
+        raise AssertionError("a plain run measured the CPU baseline")
+    monkeypatch.setattr(b, "cpu_baseline", never)
+    monkeypatch.delenv("VGE_BENCH_CPU_BASELINE", raising=False)
+    probe = [sys.executable, "-c", "import os, sys; sys.exit(5 if 'VGE_BENCH_CPU_BASELINE' in os.environ else 0)"]
+    assert b.launch_ranks(_args(gpus=2, no_cpu_baseline=False), probe) == 0
+    assert b.plain_run(_args()) and not b.plain_run(_args(full=True)) and not b.plain_run(_args(workload="cfg5"))
+    with pytest.raises(AssertionError, match="plain run"):
+        b.launch_ranks(_args(gpus=2, no_cpu_baseline=False, workload="cfg5"), probe)
+
+
+def test_full_and_dump_outputs_are_options_off_by_default():
+    b = _bench()
+    a = b.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = b.parse_args(["--full", "--dump-outputs", "somewhere"])
+    assert a.full and a.dump_outputs == "somewhere"
+
+
+def test_dump_outputs_keeps_small_arrays_whole_and_samples_large_ones_by_a_fixed_seed(tmp_path):
+    """--dump-outputs: float32 / float64 arrays as <name>.npy, at most the limit in all; an array over its share is a
+    row sample that is the same in every run (rows in ascending order), so two builds can be compared row for row."""
+    import numpy as np
+    b = _bench()
+    rng = np.random.default_rng(5)
+    arrays = {"ac": rng.normal(size=37).astype(np.float32), "tc": rng.normal(size=37),
+              "seq_embed": rng.normal(size=(1000, 64)).astype(np.float32)}
+    info = b.dump_outputs(tmp_path / "a", arrays, limit_bytes=3 * 64 * 4 * 100)   # 100 rows of seq_embed per share
+    b.dump_outputs(tmp_path / "b", arrays, limit_bytes=3 * 64 * 4 * 100)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in arrays}
+    assert np.array_equal(got["ac"], arrays["ac"]) and got["ac"].dtype == np.float32
+    assert np.array_equal(got["tc"], arrays["tc"]) and got["tc"].dtype == np.float64
+    assert got["seq_embed"].shape == (100, 64) and info["seq_embed"]["sampled_rows"] == 100
+    assert info["ac"]["sampled_rows"] is None
+    assert sum(g.nbytes for g in got.values()) <= 3 * 64 * 4 * 100
+    assert np.array_equal(got["seq_embed"], np.load(tmp_path / "b" / "seq_embed.npy"))
+    rows = [int(np.flatnonzero((arrays["seq_embed"] == r).all(axis=1))[0]) for r in got["seq_embed"]]
+    assert rows == sorted(set(rows))
+    # a second rank of a multi-rank run writes beside rank 0's files, not over them
+    b.dump_outputs(tmp_path / "a", {"ac": arrays["ac"]}, rank=1, world=2)
+    assert (tmp_path / "a" / "ac.rank1.npy").exists()
 
 
 def test_gather_rank_times_two_gloo_ranks(tmp_path):
@@ -84,12 +132,12 @@ def test_gather_rank_times_two_gloo_ranks(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_gpus_2_launches_two_ranks():
-    """`python bench.py --gpus 2` (no torchrun) on the one-GPU box: two ranks (gloo, both on cuda:0) each score their
+    """`python bench.py --gpus 2 --full` (no torchrun) on the one-GPU box: two ranks (gloo, both on cuda:0) each score their
     256 clips; the line reports the process group's world size, both ranks, and value = all videos / the slowest rank."""
     env = dict(os.environ, VGE_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-throughput-mode"], env=env, capture_output=True, text=True,
+                        "--full", "--no-cpu-baseline", "--no-throughput-mode"], env=env, capture_output=True, text=True,
                        timeout=600, cwd=str(REPO))
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -135,7 +183,7 @@ def test_pmc_traffic_refuses_a_pass_of_the_other_f16_kernel(monkeypatch):
 
 
 def test_nested_e2e_record_failure_is_recorded_not_raised():
-    """The config-3 record of the default line runs as a child process (bench.py --workload e2e, 1 step after 1
+    """The config-3 record of the --full line runs as a child process (bench.py --workload e2e, 1 step after 1
     warm-up); when it cannot run (here: no GPU) the record says why and the config-2 line still prints."""
     if __import__("torch").cuda.is_available():
         pytest.skip("CPU-only check of the failure path")
@@ -144,3 +192,40 @@ def test_nested_e2e_record_failure_is_recorded_not_raised():
     assert "error" in rec and rec["error"].startswith("exit status"), rec
     assert "--workload e2e --clips 2 --steps 1 --warmup 1" in rec["cmd"]
     json.dumps(rec)
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain `score` run in this process: --steps sets the timed steps, the line carries the headline keys and none
+    of the --full records, and --dump-outputs holds what the last timed step computed: AC / TC per video and the
+    window embeddings they were scored from (AC of a one-window video = || normalize(seq_embed) - centroid || <= 2).
+    A second run with the same arguments scores identical inputs: identical files."""
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    b = _bench()
+    dev = torch.device("cuda", 0)
+    outs = []
+    for d in ("a", "b"):
+        args = b.apply_defaults(b.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1",
+                                              "--dump-outputs", str(tmp_path / d)]))
+        line = b.run_score(args, 1, 0, dev)
+        outs.append({n: np.load(tmp_path / d / f"{n}.npy") for n in ("ac", "tc", "seq_embed", "tc_windows")})
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["dtype"] == "f32x3" and line["unit"] == "videos/s"
+    assert line["higher_is_better"] is True and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(256 * 1e3 / line["ms_per_step"], rel=1e-9)
+    for k in ("precision", "cpu_baseline", "throughput_mode", "e2e", "roofline", "stage_ms", "stage_roofline"):
+        assert k not in line, k
+    json.dumps(line)
+    o = outs[0]
+    assert o["ac"].shape == (256,) and o["ac"].dtype == np.float32
+    assert o["tc"].shape == (256,) and o["tc"].dtype == np.float64
+    assert o["seq_embed"].shape == (256, 256) and o["seq_embed"].dtype == np.float32
+    assert o["tc_windows"].shape == (256,) and o["tc_windows"].dtype == np.float32
+    assert all(np.isfinite(v).all() for v in o.values())
+    assert (o["ac"] >= 0).all() and (o["ac"] <= 2.0 + 1e-6).all() and np.abs(o["seq_embed"]).max() > 0
+    # one window per clip: a video's TC is its window's term (float32, widened)
+    assert np.array_equal(o["tc"], o["tc_windows"].astype(np.float64))
+    for n in o:
+        assert np.array_equal(o[n], outs[1][n]), n
