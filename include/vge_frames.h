@@ -1,0 +1,93 @@
+/* vge_frames.h -- the frame front end: baseline-JPEG frame folders decoded to uint8 RGB on the device.
+ *
+ * The reference never hands its extractors frames straight from a video: extract_mesh.py:47-82,200-209 writes every
+ * frame to frames/<action>/<video>/frame_%06d.jpg (cv2.imwrite, quality 95, 4:2:0) and reads the JPEGs back with
+ * cv2.imread, so the pixels its models see have been through libjpeg's decoder (the "islow" integer IDCT, fancy
+ * chroma upsampling, the 16-bit fixed-point YCbCr -> RGB).  This ABI reproduces those pixels exactly, split at the
+ * host/device line:
+ *   probe            headers only: size, component count, luma sampling factors
+ *   entropy decode   host threads: marker parsing + Huffman decoding -> int16 coefficients (natural order) and the
+ *                    uint16 quantisation tables, into caller-provided (normally pinned) buffers
+ *   reconstruct      device (HIP, caller's stream) or host (plain C++): dequantise, IDCT, upsample, colour convert
+ *                    -> uint8 [F, H, W, 3] RGB; grayscale is replicated to three channels (cv2.imread's default flag)
+ * Both reconstructs share their arithmetic through one host/device header (csrc/vge_jpeg_math.h).
+ *
+ * Supported streams: 8-bit baseline (SOF0), Huffman coded, 1 or 3 components, luma sampling 1x1, 2x1 or 2x2 with
+ * chroma 1x1 (4:4:4, 4:2:2, 4:2:0), restart intervals.  Everything else gets its own status below.  All frames of one
+ * call share H x W and sampling (a video's frames do); a frame that differs from the layout gets the shape status.
+ *
+ * Every call returns VGE_JPEG_OK or the first failing frame's code; per-frame codes go to status[] / info[].status;
+ * vge_last_error names the first failure.  No exceptions cross the ABI.  n_threads <= 0: vge_ingest_default_threads().
+ */
+#ifndef VGE_FRAMES_H
+#define VGE_FRAMES_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+enum {
+  VGE_JPEG_OK = 0,
+  VGE_JPEG_ERR_ARG = 1,           /* bad argument */
+  VGE_JPEG_ERR_HIP = 2,           /* a HIP call failed (device reconstruct) */
+  VGE_JPEG_ERR_IO = 7,            /* unreadable, truncated or corrupt stream (also: a coefficient block beyond
+                                     VGE_JPEG_BLOCK_L1_MAX, see below) */
+  VGE_JPEG_ERR_SHAPE = 8,         /* size / components / sampling differ from the call's layout */
+  VGE_JPEG_ERR_PROGRESSIVE = 20,  /* SOF2 (and the other non-baseline Huffman processes: SOF1, SOF3, SOF5-7) */
+  VGE_JPEG_ERR_ARITHMETIC = 21,   /* arithmetic coding (SOF9-11, SOF13-15) */
+  VGE_JPEG_ERR_PRECISION = 22,    /* sample precision other than 8 bits, or 16-bit quantisation tables */
+  VGE_JPEG_ERR_COMPONENTS = 23,   /* component count other than 1 or 3 (CMYK / YCCK) */
+  VGE_JPEG_ERR_SAMPLING = 24      /* sampling factors other than luma 1x1 / 2x1 / 2x2 with chroma 1x1 */
+};
+
+/* The reconstructs run the IDCT in 32-bit arithmetic.  With S = sum over a block of |coef * q|, no value the IDCT
+ * descales leaves int32 while S <= VGE_JPEG_BLOCK_L1_MAX (derivation: csrc/vge_jpeg_math.h); a stream encoded from
+ * 8-bit samples stays below 16,400.  The entropy decoder gives a frame with a block beyond the bound VGE_JPEG_ERR_IO,
+ * so host and device agree on every frame they accept. */
+#define VGE_JPEG_BLOCK_L1_MAX 32767
+
+typedef struct {
+  int32_t width, height;
+  int32_t n_comp;  /* 1 or 3 for supported streams */
+  int32_t h0, v0;  /* sampling factors of component 0 */
+  int32_t status;  /* VGE_JPEG_OK or a code above */
+} vge_jpeg_info;
+
+/* Where each component's blocks live inside one frame's coefficient buffer.  A component's plane is bw x bh blocks
+ * (whole MCUs), row-major, 64 int16 per block in natural order; component c starts at block off[c]; a frame is
+ * blocks_per_frame blocks.  Unused components are zero.  Computable from the probe result alone. */
+typedef struct {
+  int32_t width, height, n_comp, h0, v0;
+  int32_t mcus_x, mcus_y;
+  int32_t bw[3], bh[3], off[3];
+  int32_t blocks_per_frame;
+} vge_jpeg_layout;
+
+/* paths[n] -> info[n], reading the headers (up to the first SOS) only. */
+int vge_jpeg_probe(const char* const* paths, int n, int n_threads, vge_jpeg_info* info);
+
+/* Layout for frames of this size and sampling; VGE_JPEG_ERR_COMPONENTS / _SAMPLING / _ARG for unsupported ones. */
+int vge_jpeg_make_layout(int width, int height, int n_comp, int h0, int v0, vge_jpeg_layout* layout);
+
+/* Host, multithreaded over frames.  coef: int16 [n, blocks_per_frame, 64]; qtab: uint16 [n, 3, 64] (natural order,
+ * one table per component).  A frame that fails has its coefficients zeroed and its tables set to 1 and does not
+ * disturb the others.  status[n] may be NULL. */
+int vge_jpeg_entropy_decode(const char* const* paths, int n, int n_threads, const vge_jpeg_layout* layout,
+                            int16_t* coef, uint16_t* qtab, int32_t* status);
+
+/* Device: coef / qtab / rgb are device pointers, stream is a hipStream_t (NULL: the default stream); the launch is
+ * asynchronous.  rgb: uint8 [n_frames, height, width, 3]. */
+int vge_jpeg_reconstruct(const int16_t* coef, const uint16_t* qtab, const vge_jpeg_layout* layout, int n_frames,
+                         uint8_t* rgb, void* stream);
+
+/* Host: the same inputs and output in host memory, plain C++, multithreaded over frames. */
+int vge_jpeg_reconstruct_host(const int16_t* coef, const uint16_t* qtab, const vge_jpeg_layout* layout, int n_frames,
+                              int n_threads, uint8_t* rgb);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* VGE_FRAMES_H */

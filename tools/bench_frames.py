@@ -1,0 +1,186 @@
+"""Frames per second of vge.frames.load_frames on JPEG frame folders, split into its stages, beside Pillow.
+
+    python tools/bench_frames.py [--frames 1024] [--size 256] [--quality 95] [--threads 16] [--folder DIR]
+                                 [--out profiles/jpeg_decode.json]
+
+Writes its own JPEGs with Pillow (vge.synth.make_frames content, 4:2:0, quality 95: what cv2.imwrite writes) into a
+temporary folder, or reads the *.jpg files of --folder (cycled up to --frames).  Needs a GPU: there is no fallback.
+
+Stages, each warmed up and repeated, reported as median [min, max] over the repeats:
+  entropy   vge_jpeg_entropy_decode on --threads host threads into pinned memory   (host clock)
+  upload    the pinned coefficient + table buffers to the device                   (device events)
+  kernel    vge_jpeg_reconstruct, --inner launches per repeat                      (device events / launches)
+  e2e       load_frames(paths, device) ending in a device synchronise              (host clock)
+  pillow    PIL decode of the same files on --threads host threads                 (host clock; when Pillow imports)
+The kernel's HBM floor is (coefficient + table + RGB bytes) / 6.3 TB/s (the achievable rate of a float4 copy).
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+from concurrent.futures import ThreadPoolExecutor
+from pathlib import Path
+
+import numpy as np
+
+REPO = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(REPO / "video-gen-evals_amd"))
+
+HBM_ACHIEVABLE = 6.3e12  # bytes/s
+
+
+def spread(xs):
+    return {"median": statistics.median(xs), "min": min(xs), "max": max(xs), "n": len(xs)}
+
+
+def write_jpegs(folder: Path, n: int, size: int, quality: int):
+    from PIL import Image
+    from vge import synth
+    paths = []
+    for v in range((n + 63) // 64):
+        fr = synth.make_frames(1000 + v, min(64, n - 64 * v), h=size, w=size)
+        for f in range(fr.shape[0]):
+            p = folder / f"frame_{64 * v + f:06d}.jpg"
+            Image.fromarray(fr[f]).save(p, format="JPEG", quality=quality, subsampling=2)
+            paths.append(str(p))
+    return paths
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=1024)
+    ap.add_argument("--size", type=int, default=256)
+    ap.add_argument("--quality", type=int, default=95)
+    ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--folder", default=None)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--repeats", type=int, default=9)
+    ap.add_argument("--inner", type=int, default=50, help="kernel launches per timed repeat")
+    ap.add_argument("--out", default=str(REPO / "profiles" / "jpeg_decode.json"))
+    args = ap.parse_args(argv)
+
+    import torch
+    from vge import frames as FR
+    from vge import lib as L
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_frames.py needs a GPU")
+    dev = torch.device("cuda:0")
+    try:
+        import PIL
+        from PIL import Image
+    except ImportError:
+        PIL = None
+    tmp = None
+    if args.folder:
+        src = FR.list_frames(args.folder)
+        if not src:
+            raise SystemExit(f"no *.jpg in {args.folder}")
+        paths = [src[i % len(src)] for i in range(args.frames)]
+        source = f"{len(src)} files of {args.folder}, cycled"
+    else:
+        if PIL is None:
+            raise SystemExit("Pillow is not available: pass --folder with JPEG frames")
+        tmp = tempfile.TemporaryDirectory()
+        paths = write_jpegs(Path(tmp.name), args.frames, args.size, args.quality)
+        source = f"written here: vge.synth.make_frames {args.size}x{args.size}, 4:2:0, quality {args.quality}"
+    n = len(paths)
+    info = FR.probe(paths[:1], args.threads)[0]
+    lay = FR.make_layout(*[int(x) for x in info[:5]])
+    lib = L.load()
+    arr = (C.c_char_p * n)(*[os.fsencode(p) for p in paths])
+    coef = torch.empty((n, lay.blocks_per_frame, 64), dtype=torch.int16, pin_memory=True)
+    qtab = torch.empty((n, 3, 64), dtype=torch.int16, pin_memory=True)
+    status = np.zeros(n, np.int32)
+    out = torch.empty((n, lay.height, lay.width, 3), dtype=torch.uint8, device=dev)
+    coef_d, qtab_d = torch.empty_like(coef, device=dev), torch.empty_like(qtab, device=dev)
+    stream = torch.cuda.current_stream(dev)
+
+    def entropy():
+        t = time.perf_counter()
+        rc = lib.vge_jpeg_entropy_decode(arr, n, args.threads, C.byref(lay), coef.data_ptr(), qtab.data_ptr(),
+                                         status.ctypes.data)
+        dt = time.perf_counter() - t
+        assert rc == 0, L.load().vge_last_error()
+        return dt
+
+    def events(fn, inner=1):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(inner):
+            fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b) * 1e-3 / inner
+
+    def upload():
+        coef_d.copy_(coef, non_blocking=True)
+        qtab_d.copy_(qtab, non_blocking=True)
+
+    def kernel():
+        L.check(lib.vge_jpeg_reconstruct(coef_d.data_ptr(), qtab_d.data_ptr(), C.byref(lay), n, out.data_ptr(),
+                                         stream.cuda_stream), "vge_jpeg_reconstruct")
+
+    def e2e():
+        t = time.perf_counter()
+        fr, kept = FR.load_frames(paths, device=dev, threads=args.threads)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t
+        assert kept.size == n
+        return dt, fr
+
+    def pillow():
+        t = time.perf_counter()
+        with ThreadPoolExecutor(args.threads) as ex:
+            arrs = list(ex.map(lambda p: np.asarray(Image.open(p).convert("RGB")), paths))
+        return time.perf_counter() - t, arrs
+
+    res = {}
+    for _ in range(args.warmup):
+        entropy(); events(upload); events(kernel); e2e()
+    res["entropy_s"] = spread([entropy() for _ in range(args.repeats)])
+    res["upload_s"] = spread([events(upload) for _ in range(args.repeats)])
+    res["kernel_s"] = spread([events(kernel, args.inner) for _ in range(args.repeats)])
+    e = [e2e() for _ in range(args.repeats)]
+    res["e2e_s"] = spread([t for t, _ in e])
+    frames = e[-1][1]
+    exact = None
+    if PIL is not None:
+        for _ in range(args.warmup):
+            pillow()
+        p = [pillow() for _ in range(args.repeats)]
+        res["pillow_decode_s"] = spread([t for t, _ in p])
+        exact = bool(np.array_equal(frames.cpu().numpy(), np.stack(p[-1][1])))
+    coef_b, tab_b, rgb_b = coef.numel() * 2, qtab.numel() * 2, out.numel()
+    floor = (coef_b + tab_b + rgb_b) / HBM_ACHIEVABLE
+    k = res["kernel_s"]["median"]
+    report = {
+        "what": "vge.frames.load_frames stages, measured on the GPU by tools/bench_frames.py",
+        "device": torch.cuda.get_device_name(0), "frames": n, "width": lay.width, "height": lay.height,
+        "sampling": f"{lay.h0}x{lay.v0}", "threads": args.threads, "source": source,
+        "jpeg_bytes_per_frame": sum(os.path.getsize(p) for p in set(paths)) / len(set(paths)),
+        "stages": res,
+        "frames_per_s": {key[:-2]: n / v["median"] for key, v in res.items()},
+        "kernel_bytes": {"coefficients": coef_b, "tables": tab_b, "rgb": rgb_b,
+                         "per_frame": (coef_b + tab_b + rgb_b) / n},
+        "kernel_hbm_floor_s": floor, "kernel_time_over_floor": k / floor,
+        "kernel_bytes_per_s": (coef_b + tab_b + rgb_b) / k,
+        "equals_pillow": exact if exact is not None else "not measured (Pillow not importable)",
+        "pillow": getattr(PIL, "__version__", None),
+    }
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(report, f, indent=1)
+    print(json.dumps(report))
+    if tmp is not None:
+        tmp.cleanup()
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -1,7 +1,8 @@
 """Extraction drivers around the GPU extractors: the callers and on-disk formats either side of them.
 
-Mirrors the reference's extraction scripts, minus video decoding (cv2 is not part of this framework: callers pass
-decoded uint8 RGB frames):
+Mirrors the reference's extraction scripts, minus video container decoding (cv2 is not part of this framework): callers
+pass decoded uint8 RGB frames, or point extract_frame_tree / `python -m vge.extract` at the JPEG frame folders the
+reference writes (vge.frames decodes them on the GPU):
 
   mesh_generator.py:101-145   the TokenHMR front end: person detection (detectron2 Faster R-CNN X101-32x8d-FPN,
                               vge.frcnn), the single-person gate (exactly one person instance with score > 0.5 per
@@ -178,6 +179,79 @@ def extract_video(hmr, wholebody, frames, crops, action: str, video: str, mesh_r
     return {"npz": npz, "keypoints": kp}
 
 
+def _pack_passes(items, max_frames: int):
+    """The packing rule of extract_videos: items are (key, payload, n_frames) in order; consecutive items go into passes
+    of at most `max_frames` frames, a longer one is a pass of its own."""
+    passes, cur, n = [], [], 0
+    for it in items:
+        t = int(it[2])
+        if cur and n + t > max_frames:
+            passes.append(cur)
+            cur, n = [], 0
+        cur.append(it)
+        n += t
+    if cur:
+        passes.append(cur)
+    return passes
+
+
+def _run_pass(hmr, wholebody, detector, group, want_kp=None, crop=None):
+    """One pass of extract_videos / extract_frame_tree: group is [(key, uint8 [T, H, W, 3] device frames)]; the gate
+    detector and DWPose run once over all its frames, TokenHMR once over the crops of every kept frame of the accepted
+    videos.  want_kp: per video, whether keypoints are needed (None: all); crop: the person-crop function (None:
+    vge.hmr.crop_persons).  Returns per video (key, keypoint rows [T, 120] or None, kept frame indices or None for a
+    rejected video, {pose, betas, global_orient, vit} rows of the kept frames or None)."""
+    import torch
+    if crop is None:
+        from .hmr import crop_persons as crop
+    fr = group[0][1] if len(group) == 1 else torch.cat([f for _, f in group], 0)
+    det = detector.detect(fr)
+    lens = [int(f.shape[0]) for _, f in group]
+    starts = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    want = [True] * len(group) if want_kp is None else [bool(w) for w in want_kp]
+    kp_rows = [None] * len(group)
+    if all(want):
+        kp = wholebody(fr).cpu().numpy()
+        kp_rows = [kp[starts[i]:starts[i + 1]] for i in range(len(group))]
+    elif any(want):
+        sel = [i for i, w in enumerate(want) if w]
+        kp = wholebody(torch.cat([group[i][1] for i in sel], 0)).cpu().numpy()
+        o = 0
+        for i in sel:
+            kp_rows[i] = kp[o:o + lens[i]]
+            o += lens[i]
+    boxes = det["person"][:, 0, :4].cpu().numpy()
+    npers = det["n_person"].cpu().numpy()
+    kept, valids = [], []
+    for i in range(len(group)):
+        f0, t = int(starts[i]), lens[i]
+        valid = single_person_frames(np.where(gate_mask(npers[f0:f0 + t]), 1, 0))
+        valids.append(valid)
+        if valid is not None:
+            kept.append(valid + f0)
+    rows = None
+    if kept:
+        kf = np.concatenate(kept)
+        crops = crop(fr, boxes[kf], kf)
+        rows = {k: v.cpu().numpy() for k, v in hmr.extract(crops).items()}
+    out, r = [], 0
+    for i, (key, _) in enumerate(group):
+        valid = valids[i]
+        if valid is None:
+            out.append((key, kp_rows[i], None, None))
+            continue
+        out.append((key, kp_rows[i], valid, {k: rows[k][r:r + valid.size] for k in ("pose", "betas", "global_orient",
+                                                                                  "vit")}))
+        r += valid.size
+    return out
+
+
+def _mesh_info(frame_ids, rows) -> dict:
+    return {int(fi): {"pose": rows["pose"][j].reshape(23, 3, 3), "betas": rows["betas"][j],
+                      "global_orient": rows["global_orient"][j].reshape(1, 3, 3), "vit": rows["vit"][j]}
+            for j, fi in enumerate(frame_ids)}
+
+
 def extract_videos(hmr, wholebody, detector, videos, mesh_root, kp_root, max_frames: int = 1024) -> Dict[str, Optional[str]]:
     """extract_mesh.py:150-241 + process_video.py:59-94 over a list of videos, batched for the GPU: videos are
     (stem, uint8 [T, H, W, 3] device frames) of any lengths; consecutive videos are packed into passes of at most
@@ -188,47 +262,219 @@ def extract_videos(hmr, wholebody, detector, videos, mesh_root, kp_root, max_fra
     frames (extract_mesh.py:35-43; a rejected video gets none: the not-single list) and
     <kp_root>/<stem>/keypoints.npy of every frame (process_video.py writes them for every video).
     Returns {stem: npz path or None}."""
-    import torch
-    from .hmr import crop_persons
     out: Dict[str, Optional[str]] = {}
-    passes, cur, n = [], [], 0
-    for stem, fr in videos:
-        t = int(fr.shape[0])
-        if cur and n + t > max_frames:
-            passes.append(cur)
-            cur, n = [], 0
-        cur.append((stem, fr))
-        n += t
-    if cur:
-        passes.append(cur)
-    for group in passes:
-        fr = group[0][1] if len(group) == 1 else torch.cat([f for _, f in group], 0)
-        det = detector.detect(fr)
-        kp = wholebody(fr).cpu().numpy()
-        boxes = det["person"][:, 0, :4].cpu().numpy()
-        npers = det["n_person"].cpu().numpy()
-        kept, spans, f0 = [], [], 0
-        for stem, f in group:
-            t = int(f.shape[0])
-            valid = single_person_frames(np.where(gate_mask(npers[f0:f0 + t]), 1, 0))
-            spans.append((stem, f0, t, valid))
-            if valid is not None:
-                kept.append(valid + f0)
-            f0 += t
-        rows = None
-        if kept:
-            kf = np.concatenate(kept)
-            crops = crop_persons(fr, boxes[kf], kf)
-            rows = {k: v.cpu().numpy() for k, v in hmr.extract(crops).items()}
-        r = 0
-        for stem, f0, t, valid in spans:
-            save_keypoints(kp[f0:f0 + t], Path(kp_root), "", stem)
+    for group in _pack_passes([(stem, fr, int(fr.shape[0])) for stem, fr in videos], max_frames):
+        for stem, kp, valid, rows in _run_pass(hmr, wholebody, detector, [(s, f) for s, f, _ in group]):
+            save_keypoints(kp, Path(kp_root), "", stem)
             if valid is None:
                 out[stem] = None
                 continue
-            mesh_info = {int(fi): {"pose": rows["pose"][r + j].reshape(23, 3, 3), "betas": rows["betas"][r + j],
-                                   "global_orient": rows["global_orient"][r + j].reshape(1, 3, 3),
-                                   "vit": rows["vit"][r + j]} for j, fi in enumerate(valid)}
-            r += valid.size
-            out[stem] = save_video_npz(stem, mesh_info, out_root=mesh_root, meta={"video": stem})
+            out[stem] = save_video_npz(stem, _mesh_info(valid, rows), out_root=mesh_root, meta={"video": stem})
     return out
+
+
+# ---- the reference's extraction driver over frame folders (extract_mesh.py:115-241, process_video.py:59-94)
+
+def _load_json(path: Path, default):
+    """extract_mesh.py:131-144 load_list / load_dict: a missing or corrupted log starts fresh."""
+    if path.exists():
+        try:
+            with open(path, "r") as f:
+                return json.load(f)
+        except Exception:
+            print(f"[WARN] Corrupted {path}; starting fresh.")
+    return default
+
+
+def _save_json(path: Path, data) -> None:
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(data, f, indent=4)
+
+
+def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root, log_root, actions=None,
+                       max_frames: int = 1024, device=None, threads: int = 0, crop=None) -> Dict[str, Dict[str, list]]:
+    """extract_mesh.py:150-241 and process_video.py:59-94 together, over the frame folders the reference leaves on
+    disk: <frames_root>/<action>/<video>/*.jpg, decoded by vge.frames (the pixels cv2.imread gives the reference).
+
+    Per action, <log_root>/single/<action>.json and not_single/<action>.json (lists of video names) and
+    errors/<action>.json ({video: message}) are rewritten after every video.  A video already in the single or
+    not-single list is skipped; one in the error list is tried again (the reference's `processed` set leaves errors
+    out).  Keypoints are skipped when <kp_root>/<action>/<video>/keypoints.npy exists (process_video.py:73-76).  A video
+    whose folder has no frames, whose frames are all undecodable or whose processing raises gets its message recorded
+    under its name and the job goes on.  Videos are packed into passes by extract_videos' rule (on their listed frame
+    counts); a pass's videos are decoded in one call and validated before the models see them, and when a pass raises,
+    its videos are run again one by one so that one video's failure does not lose the others.
+
+    Outputs: <mesh_root>/<action>/<video>.npz (kept frames only; frame_idx indexes the folder's sorted *.jpg list, so
+    a frame that failed to decode shows as a gap; meta carries action / video / source_path) and
+    <kp_root>/<action>/<video>/keypoints.npy.  actions: None (every folder of frames_root), a name or a list of names.
+    Returns {action: {"single": [...], "not_single": [...], "errors": [...], "skipped": [...]}} for this run."""
+    from . import frames as FR
+    frames_root, log_root = Path(frames_root), Path(log_root)
+    all_actions = sorted(d.name for d in frames_root.iterdir() if d.is_dir())
+    if actions is None:
+        actions = all_actions
+    elif isinstance(actions, str):
+        actions = [actions]
+    for a in actions:
+        if a not in all_actions:
+            raise ValueError(f"Action '{a}' not found under {frames_root}")   # extract_mesh.py:170-171
+    summary: Dict[str, Dict[str, list]] = {}
+    for action in actions:
+        action_dir = frames_root / action
+        videos = sorted(d.name for d in action_dir.iterdir() if d.is_dir())
+        single_path = log_root / "single" / f"{action}.json"
+        not_path = log_root / "not_single" / f"{action}.json"
+        err_path = log_root / "errors" / f"{action}.json"
+        singles, nots = _load_json(single_path, []), _load_json(not_path, [])
+        errs = _load_json(err_path, {})
+        processed = set(singles) | set(nots)
+        done = summary.setdefault(action, {"single": [], "not_single": [], "errors": [], "skipped": []})
+
+        def fail(video, msg):
+            print(f"[WARN] Failed on {action_dir / video}: {msg}")
+            errs[video] = msg
+            _save_json(err_path, errs)
+            done["errors"].append(video)
+
+        def finish(video, frames_kept, kp, valid, rows):
+            """Write one video's outputs and move it to its list."""
+            if kp is not None:
+                save_keypoints(kp, kp_root, action, video)
+            if valid is None:
+                nots.append(video)
+                _save_json(not_path, nots)
+                done["not_single"].append(video)
+            else:
+                save_video_npz(str(Path(action) / video), _mesh_info(frames_kept[valid], rows), out_root=mesh_root,
+                               meta={"action": action, "video": video, "source_path": str(action_dir / video)})
+                singles.append(video)
+                _save_json(single_path, singles)
+                done["single"].append(video)
+            if errs.pop(video, None) is not None:
+                _save_json(err_path, errs)
+
+        todo = []
+        for video in videos:
+            if video in processed:
+                print(f"[SKIP] {action}/{video} (already processed)")
+                done["skipped"].append(video)
+                continue
+            todo.append((video, FR.list_frames(action_dir / video)))
+        for group in _pack_passes([(v, paths, len(paths)) for v, paths in todo], max_frames):
+            # decode and validate: one call for the pass; a video that makes it raise is found one by one
+            try:
+                decoded = FR.load_videos([paths for _, paths, _ in group], device=device, threads=threads)
+            except Exception:
+                decoded = []
+                for _, paths, _ in group:
+                    try:
+                        decoded.append(FR.load_frames(paths, device=device, threads=threads))
+                    except Exception as e:
+                        decoded.append(e)
+            good = []
+            for (video, paths, _), dec in zip(group, decoded):
+                if isinstance(dec, Exception):
+                    fail(video, str(dec))
+                elif not paths:
+                    fail(video, f"no frames (*.jpg) in {action_dir / video}")
+                elif dec[1].size == 0:
+                    fail(video, f"none of the {len(paths)} frames in {action_dir / video} could be decoded")
+                else:
+                    good.append((video, dec[0], np.asarray(dec[1], np.int64)))
+            if not good:
+                continue
+            # frames of one pass are stacked: consecutive videos of one frame size run together
+            runs = []
+            for g in good:
+                if runs and tuple(runs[-1][-1][1].shape[1:]) == tuple(g[1].shape[1:]):
+                    runs[-1].append(g)
+                else:
+                    runs.append([g])
+            for run in runs:
+                want_kp = [not (Path(kp_root) / action / v / "keypoints.npy").exists() for v, _, _ in run]
+                kept_of = {v: k for v, _, k in run}
+                try:
+                    results = _run_pass(hmr, wholebody, detector, [(v, f) for v, f, _ in run], want_kp, crop)
+                except Exception as e:
+                    results = []
+                    if len(run) == 1:
+                        fail(run[0][0], str(e))
+                    else:   # one video's failure must not lose the others of its pass
+                        for (v, f, _), w in zip(run, want_kp):
+                            try:
+                                results += _run_pass(hmr, wholebody, detector, [(v, f)], [w], crop)
+                            except Exception as e1:
+                                fail(v, str(e1))
+                for video, kp, valid, rows in results:
+                    try:
+                        finish(video, kept_of[video], kp, valid, rows)
+                    except Exception as e:
+                        fail(video, str(e))
+    return summary
+
+
+def _load_state_dict(path: str) -> Dict[str, np.ndarray]:
+    """A checkpoint file -> {name: float array}: torch.load(weights_only=True) of a plain state_dict or of a dict that
+    holds one under state_dict / model_state_dict / model (as vge.eval.load_model reads the scorer's)."""
+    import torch
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    for k in ("model_state_dict", "state_dict", "model"):
+        if isinstance(ck, dict) and isinstance(ck.get(k), dict):
+            ck = ck[k]
+            break
+    return {k: v.detach().cpu().numpy() for k, v in ck.items() if isinstance(v, torch.Tensor)}
+
+
+def main(argv=None) -> int:
+    """python -m vge.extract: the reference's extract_mesh.py + process_video.py over a tree of frame folders."""
+    import argparse
+    ap = argparse.ArgumentParser(description="TokenHMR meshes + DWPose keypoints from <frames-root>/<action>/<video>/*.jpg")
+    ap.add_argument("--frames-root", required=True)
+    ap.add_argument("--mesh-root", required=True)
+    ap.add_argument("--kp-root", required=True)
+    ap.add_argument("--log-root", required=True)
+    ap.add_argument("--action", default=None,
+                    help="Optional: only process this action (directory name). If not set, process all actions.")
+    ap.add_argument("--hmr-ckpt", help="TokenHMR state_dict")
+    ap.add_argument("--frcnn-ckpt", help="detectron2 Faster R-CNN X101-32x8d-FPN state_dict (the single-person gate)")
+    ap.add_argument("--yolox-ckpt", help="DWPose's YOLOX-L state_dict")
+    ap.add_argument("--rtmpose-ckpt", help="DWPose's RTMPose-l whole-body state_dict")
+    ap.add_argument("--synthetic-weights", action="store_true",
+                    help="deterministic random weights of the full-size models (vge.synth), for dry runs")
+    ap.add_argument("--max-frames", type=int, default=1024, help="frames per GPU pass")
+    ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--threads", type=int, default=0, help="JPEG entropy-decode threads (0: the ingest default)")
+    args = ap.parse_args(argv)
+    from . import synth
+    from .dwpose import RTMPOSE_L, YOLOX_L, DwposeExtractor, Wholebody, YoloxDetector
+    from .frcnn import FRCNN_X101, FrcnnDetector
+    from .hmr import TOKENHMR, HmrExtractor
+
+    def weights(path, make, what):
+        if path:
+            return _load_state_dict(path)
+        if args.synthetic_weights:
+            return make()
+        ap.error(f"--{what}-ckpt is required (or --synthetic-weights)")
+
+    dev, fc = args.device, args.max_frames
+    hmr = HmrExtractor(weights(args.hmr_ckpt, lambda: synth.make_hmr_state_dict(TOKENHMR), "hmr"), TOKENHMR,
+                       device=dev, max_frames=fc)
+    gdet = FrcnnDetector(weights(args.frcnn_ckpt, lambda: synth.make_gate_frcnn_state_dict(FRCNN_X101), "frcnn"),
+                         FRCNN_X101, device=dev, chunk=128)
+    wb = Wholebody(YoloxDetector(weights(args.yolox_ckpt, lambda: synth.make_gate_detector_state_dict(YOLOX_L), "yolox"),
+                                 YOLOX_L, device=dev, chunk=256),
+                   DwposeExtractor(weights(args.rtmpose_ckpt, lambda: synth.make_rtmpose_state_dict(RTMPOSE_L), "rtmpose"),
+                                   RTMPOSE_L, device=dev, max_instances=2 * fc))
+    summary = extract_frame_tree(hmr, wb, gdet, args.frames_root, args.mesh_root, args.kp_root, args.log_root,
+                                 actions=args.action, max_frames=fc, device=dev, threads=args.threads)
+    for action, d in summary.items():
+        print(f"[DONE] {action}: {len(d['single'])} single, {len(d['not_single'])} not single, "
+              f"{len(d['errors'])} errors, {len(d['skipped'])} skipped")
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -1,0 +1,146 @@
+"""The frame front end: folders of baseline-JPEG frames -> uint8 RGB frame tensors (include/vge_frames.h).
+
+The reference writes every frame of a video to frames/<action>/<video>/frame_%06d.jpg and reads the JPEGs back with
+cv2.imread (extract_mesh.py:47-82, 200-209), so its models see pixels that went through libjpeg's decoder.  load_frames
+gives the same pixels: Huffman decoding on host threads (vge_jpeg_entropy_decode) into pinned memory, one asynchronous
+upload on the caller's stream, and dequantise / IDCT / upsample / colour convert in one HIP kernel
+(vge_jpeg_reconstruct); without a GPU, or with device="cpu", the plain-C++ reconstruct with the same arithmetic.
+Channel order is RGB (the extractors here take RGB; cv2.imread's BGR is the same bytes reversed).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import logging
+import os
+from pathlib import Path
+from typing import List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+
+from . import lib as L
+
+log = logging.getLogger("vge.frames")
+
+PathLike = Union[str, os.PathLike]
+
+
+class UnsupportedJpegError(L.VgeError):
+    """A JPEG of a kind the decoder is not built for (progressive, arithmetic-coded, 12-bit, CMYK, other sampling
+    factors); the message names the kind and the file."""
+
+
+def list_frames(folder: PathLike) -> List[str]:
+    """extract_mesh.py:203-205: sorted(join(dir, f) for f in os.listdir(dir) if f.endswith('.jpg'))."""
+    folder = os.fspath(folder)
+    return sorted(os.path.join(folder, f) for f in os.listdir(folder) if f.endswith(".jpg"))
+
+
+def _paths_array(paths: Sequence[str]):
+    return (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
+
+
+def probe(paths: Sequence[PathLike], threads: int = 0) -> np.ndarray:
+    """Headers only: int32 [n, 6] rows of (width, height, components, h0, v0, status)."""
+    paths = [os.fspath(p) for p in paths]
+    info = (L.JpegInfo * max(len(paths), 1))()
+    if paths:
+        L.load().vge_jpeg_probe(_paths_array(paths), len(paths), int(threads), info)
+    return np.array([[i.width, i.height, i.n_comp, i.h0, i.v0, i.status] for i in info[:len(paths)]],
+                    dtype=np.int32).reshape(-1, 6)
+
+
+def make_layout(width: int, height: int, n_comp: int, h0: int, v0: int) -> L.JpegLayout:
+    lay = L.JpegLayout()
+    L.check(L.load().vge_jpeg_make_layout(int(width), int(height), int(n_comp), int(h0), int(v0), C.byref(lay)),
+            "vge_jpeg_make_layout")
+    return lay
+
+
+def _resolve_device(device):
+    import torch
+    if device is None:
+        return torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+    return torch.device(device)
+
+
+def _decode_group(paths: List[str], lay: L.JpegLayout, device, threads: int):
+    """One layout's frames -> (uint8 [n, H, W, 3] tensor on `device`, int32 status [n])."""
+    import torch
+    n = len(paths)
+    lib = L.load()
+    on_gpu = device.type == "cuda"
+    coef = torch.empty((n, lay.blocks_per_frame, 64), dtype=torch.int16, pin_memory=on_gpu)
+    qtab = torch.empty((n, 3, 64), dtype=torch.int16, pin_memory=on_gpu)  # uint16 bits
+    status = np.zeros(n, np.int32)
+    lib.vge_jpeg_entropy_decode(_paths_array(paths), n, int(threads), C.byref(lay), coef.data_ptr(), qtab.data_ptr(),
+                                status.ctypes.data)
+    out = torch.empty((n, lay.height, lay.width, 3), dtype=torch.uint8, device=device)
+    if on_gpu:
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device)
+            coef_d = coef.to(device, non_blocking=True)   # asynchronous, from pinned memory, ahead of the kernel
+            qtab_d = qtab.to(device, non_blocking=True)
+            L.check(lib.vge_jpeg_reconstruct(coef_d.data_ptr(), qtab_d.data_ptr(), C.byref(lay), n, out.data_ptr(),
+                                             stream.cuda_stream), "vge_jpeg_reconstruct")
+    else:
+        L.check(lib.vge_jpeg_reconstruct_host(coef.data_ptr(), qtab.data_ptr(), C.byref(lay), n, int(threads),
+                                              out.data_ptr()), "vge_jpeg_reconstruct_host")
+    return out, status
+
+
+def load_videos(videos: Sequence[Union[PathLike, Sequence[PathLike]]], device=None, threads: int = 0):
+    """Several videos in one go: each entry is a frame folder or a list of JPEG paths.  Videos of one frame size and
+    sampling share one entropy-decode call, one upload and one kernel launch.  Returns a list of (frames, kept) as
+    load_frames does."""
+    import torch
+    device = _resolve_device(device)
+    vids = [list_frames(v) if isinstance(v, (str, os.PathLike)) else [os.fspath(p) for p in v] for v in videos]
+    flat = [p for v in vids for p in v]
+    info = probe(flat, threads)
+    for p, row in zip(flat, info):
+        if int(row[5]) in L.JPEG_UNSUPPORTED:
+            raise UnsupportedJpegError(f"{p}: unsupported JPEG: {L.JPEG_UNSUPPORTED[int(row[5])]} "
+                                       f"({L.JPEG_STATUS[int(row[5])]})")
+    # a video's layout is its first readable frame's; frames of another size get the shape status and are dropped
+    groups, keys, f0 = {}, [], 0
+    for vi, v in enumerate(vids):
+        rows = info[f0:f0 + len(v)]
+        good = np.flatnonzero(rows[:, 5] == 0)
+        key = tuple(int(x) for x in rows[good[0], :5]) if good.size else None
+        keys.append(key)
+        if key is not None:
+            groups.setdefault(key, []).append(vi)
+        f0 += len(v)
+    results: List[Optional[Tuple]] = [None] * len(vids)
+    for key, members in groups.items():
+        lay = make_layout(*key)
+        paths = [p for vi in members for p in vids[vi]]
+        out, status = _decode_group(paths, lay, device, threads)
+        o = 0
+        for vi in members:
+            n = len(vids[vi])
+            st = status[o:o + n]
+            for p, s in zip(vids[vi], st):
+                if s != 0:
+                    log.warning("dropping frame %s: %s", p, L.JPEG_STATUS.get(int(s), int(s)))
+            kept = np.flatnonzero(st == 0)
+            fr = out[o:o + n]
+            if kept.size != n:
+                fr = fr[torch.as_tensor(kept, device=device)]
+            results[vi] = (fr, kept)
+            o += n
+    for vi, key in enumerate(keys):
+        if key is None:
+            for p in vids[vi]:
+                log.warning("dropping frame %s: unreadable", p)
+            results[vi] = (torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=device), np.zeros(0, np.int64))
+    return results
+
+
+def load_frames(paths_or_dir: Union[PathLike, Sequence[PathLike]], device=None, threads: int = 0):
+    """load_frames_from_images (extract_mesh.py:72-82) on the GPU.  paths_or_dir: a frame folder (its *.jpg files in
+    sorted order) or a list of JPEG paths.  Returns (frames, kept): uint8 [F', H, W, 3] RGB on `device` (default: the
+    current GPU when there is one, else the CPU) and the indices of the frames that decoded.  A frame that fails to
+    decode is dropped with a log message, as the reference drops a None from cv2.imread; an unsupported kind of JPEG
+    raises UnsupportedJpegError naming the kind and the file."""
+    return load_videos([paths_or_dir], device=device, threads=threads)[0]

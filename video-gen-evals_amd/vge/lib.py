@@ -31,7 +31,9 @@ EXPORTS = ["vge_featurize", "vge_featurize_layout", "vge_layout_feat_dim", "vge_
            "vge_hmr_crop",
            "vge_yolox_profile_begin", "vge_yolox_profile_read",
            "vge_frcnn_create", "vge_frcnn_reserve", "vge_frcnn_destroy", "vge_frcnn_shapes", "vge_frcnn_detect",
-           "vge_frcnn_profile_begin", "vge_frcnn_profile_read"]
+           "vge_frcnn_profile_begin", "vge_frcnn_profile_read",
+           "vge_jpeg_probe", "vge_jpeg_make_layout", "vge_jpeg_entropy_decode", "vge_jpeg_reconstruct",
+           "vge_jpeg_reconstruct_host"]
 
 
 class VgeError(RuntimeError):
@@ -62,6 +64,23 @@ class ClipInfo(C.Structure):  # include/vge_ingest.h vge_clip_info
 
 
 INGEST_STATUS = {0: "OK", 1: "ERR_ARG", 7: "ERR_IO", 8: "ERR_SHAPE", 9: "ERR_KP"}
+
+
+class JpegInfo(C.Structure):  # include/vge_frames.h vge_jpeg_info
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("n_comp", C.c_int32), ("h0", C.c_int32),
+                ("v0", C.c_int32), ("status", C.c_int32)]
+
+
+class JpegLayout(C.Structure):  # include/vge_frames.h vge_jpeg_layout
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("n_comp", C.c_int32), ("h0", C.c_int32),
+                ("v0", C.c_int32), ("mcus_x", C.c_int32), ("mcus_y", C.c_int32), ("bw", C.c_int32 * 3),
+                ("bh", C.c_int32 * 3), ("off", C.c_int32 * 3), ("blocks_per_frame", C.c_int32)]
+
+
+JPEG_STATUS = {0: "OK", 1: "ERR_ARG", 2: "ERR_HIP", 7: "ERR_IO", 8: "ERR_SHAPE", 20: "ERR_PROGRESSIVE",
+               21: "ERR_ARITHMETIC", 22: "ERR_PRECISION", 23: "ERR_COMPONENTS", 24: "ERR_SAMPLING"}
+JPEG_UNSUPPORTED = {20: "progressive (or another non-baseline process)", 21: "arithmetic-coded", 22: "not 8-bit",
+                    23: "neither 1 nor 3 components", 24: "sampling other than 4:4:4 / 4:2:2 / 4:2:0"}
 
 
 class FrameStoreC(C.Structure):
@@ -111,6 +130,11 @@ def load() -> C.CDLL:
         "vge_ingest_probe": [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), i32, i32, C.POINTER(ClipInfo)],
         "vge_ingest_decode": [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), i32, i32, vp, i32, vp, vp, vp, vp, vp,
                               vp],
+        "vge_jpeg_probe": [C.POINTER(C.c_char_p), i32, i32, C.POINTER(JpegInfo)],
+        "vge_jpeg_make_layout": [i32, i32, i32, i32, i32, C.POINTER(JpegLayout)],
+        "vge_jpeg_entropy_decode": [C.POINTER(C.c_char_p), i32, i32, C.POINTER(JpegLayout), vp, vp, vp],
+        "vge_jpeg_reconstruct": [vp, vp, C.POINTER(JpegLayout), i32, vp, vp],
+        "vge_jpeg_reconstruct_host": [vp, vp, C.POINTER(JpegLayout), i32, i32, vp],
     }
     for name, args in sig.items():
         f = getattr(lib, name)
