@@ -22,8 +22,10 @@ import torch.nn.functional as F
 
 class OracleEncoder:
     def __init__(self, sd: Dict[str, np.ndarray], dims_raw: Dict[str, int], dims_diff: Dict[str, int],
-                 d_model: int = 256, time_layers: int = 4, time_heads: int = 8):
-        self.p = {k: torch.as_tensor(np.asarray(v, np.float32)) for k, v in sd.items()}
+                 d_model: int = 256, time_layers: int = 4, time_heads: int = 8, dtype: torch.dtype = torch.float32):
+        # dtype torch.float64: the same float32 weights and input, every operation in double (the GPU tests' reference)
+        self.dtype = dtype
+        self.p = {k: torch.as_tensor(np.asarray(v, np.float32)).to(dtype) for k, v in sd.items()}
         self.mods: List[str] = list(dims_raw.keys())
         self.dims_raw = dims_raw
         self.dims_diff = dims_diff
@@ -81,6 +83,7 @@ class OracleEncoder:
     @torch.no_grad()
     def forward(self, x: torch.Tensor):
         """x [B,T,D_in] -> (seq_embed [B,d], frame_embeds [B,T+1,d], tokens [B,T+1,d])."""
+        x = x.to(self.dtype)
         B, T, _ = x.shape
         n_raw = sum(self.dims_raw[m] for m in self.mods)
         raw, diff = x[:, :, :n_raw], x[:, :, n_raw:]

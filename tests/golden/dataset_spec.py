@@ -25,6 +25,42 @@ NOKP_MODS = ("vit", "global", "pose", "beta")  # the keypoint-less model (keypoi
 SMALL_HP = {"d_model": 64, "time_layers": 2, "time_heads": 4}
 
 
+# every (d_model, time_heads, time_layers, modalities) the encoder tests run (tests/test_encoder_shapes.py), pinned
+# to the reference in golden_shapes.npz (make_golden.py shapes).  TILED: d_model 256 x 8 heads, all compute modes
+# (VGE_F16 up to 8 layers); GENERIC: the exact-f32 kernels of vge_encoder_gen.hip
+TILED_SHAPES = [(256, 8, l, 5) for l in (1, 2, 3, 4, 5, 8, 9, 12)] + [(256, 8, 2, 4)]
+GENERIC_SHAPES = [(32, 1, 1, 5), (32, 4, 2, 5), (96, 3, 3, 5), (96, 2, 2, 5), (160, 5, 2, 5), (192, 3, 2, 5),
+                  (224, 7, 1, 5), (256, 4, 2, 5), (256, 16, 2, 5), (96, 3, 2, 4)]
+SHAPES_SEED = 20240                # seed of the 3 randn windows behind every golden_shapes.npz entry
+SHAPES_WINDOWS = 3
+
+
+def shape_key(shape) -> str:
+    return "d%d_h%d_l%d_m%d" % tuple(shape)
+
+
+def shape_dims(n_mod: int):
+    """(dims_raw, dims_diff) of the 5-modality layout or its keypoint-less first 4."""
+    mods = list(synth.DIMS_RAW)[:n_mod]
+    return {m: synth.DIMS_RAW[m] for m in mods}, {m: synth.DIMS_DIFF[m] for m in mods}
+
+
+def shape_state_dict(shape, max_len: int = 5000):
+    """max_len: rows of pos_enc.pe (the reference's buffer holds 5000; the model reads the first 33, and no random
+    draw depends on it, so a short table gives the same weights faster)."""
+    d, _, layers, n_mod = shape
+    raw, diff = shape_dims(n_mod)
+    return synth.make_state_dict(raw, diff, d_model=d, time_layers=layers, max_len=max_len)
+
+
+def shape_windows(n_mod: int):
+    """The seeded randn windows [3, 32, feat_dim] of golden_shapes.npz (the same for every shape of one layout)."""
+    import torch
+    g = torch.Generator().manual_seed(SHAPES_SEED + n_mod)
+    raw, diff = shape_dims(n_mod)
+    return torch.randn(SHAPES_WINDOWS, 32, sum(raw.values()) + sum(diff.values()), generator=g)
+
+
 def golden_state_dict(layout: str = "kp"):
     """The golden checkpoint's weights: 5 modalities, or the keypoint-less 4 (same generator, no kp2d), or "small":
     5 modalities at SMALL_HP's shape."""

@@ -18,6 +18,9 @@ synthetic dataset and weights of vge.synth, and stores inputs/outputs as small f
   golden_flow_small.npz / golden_scores_small.json
                       the keypoint flow with a checkpoint of another shape (d_model 64, 2 layers, 4 heads;
                       dataset_spec.SMALL_HP) -- `python -B tests/golden/make_golden.py small` writes only these
+  golden_shapes.npz   HumanActionScorer on 3 seeded randn windows at every checkpoint shape of
+                      dataset_spec.TILED_SHAPES / GENERIC_SHAPES (seq_embed, the first window's frame_embeds; the same
+                      bytes on every run) -- `python -B tests/golden/make_golden.py shapes` writes only this
 
 Nothing from the reference is copied; only arrays and numbers it produced.  This script never runs
 on the GPU box (the reference is not there); tests regenerate the same synthetic inputs from seeds.
@@ -298,12 +301,51 @@ def main_small():
     print("small-checkpoint golden written to", HERE)
 
 
+def _write_npz_fixed(path, arrays):
+    """np.savez_compressed with fixed member timestamps: the same arrays give the same bytes on every run."""
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as zf:
+        for k in sorted(arrays):
+            zi = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            zi.compress_type = zipfile.ZIP_DEFLATED
+            zi.external_attr = 0o644 << 16
+            with zf.open(zi, "w") as f:
+                np.lib.format.write_array(f, np.ascontiguousarray(arrays[k]), allow_pickle=False)
+
+
+def main_shapes():
+    """HumanActionScorer at every checkpoint shape of dataset_spec.TILED_SHAPES / GENERIC_SHAPES (the shapes
+    vge_encoder_create accepts that tests/test_encoder_shapes.py runs): synth.make_state_dict of that shape loaded with
+    strict=True, 3 seeded randn windows -> float32 seq_embed [3, d] and the first window's frame_embeds [33, d]."""
+    from tests.golden.dataset_spec import (GENERIC_SHAPES, TILED_SHAPES, shape_dims, shape_key, shape_state_dict,
+                                           shape_windows)
+    sys.path.insert(0, REF)
+    from model import HumanActionScorer  # noqa
+    out = {}
+    for shape in TILED_SHAPES + GENERIC_SHAPES:
+        d, heads, layers, n_mod = shape
+        raw, diff = shape_dims(n_mod)
+        model = HumanActionScorer(raw, diff, d_model=d, time_layers=layers, time_heads=heads)
+        model.load_state_dict({k: torch.from_numpy(v) for k, v in shape_state_dict(shape).items()}, strict=True)
+        model.eval()
+        with torch.no_grad():
+            seq, frames, _ = model(shape_windows(n_mod))
+        assert seq.shape == (3, d) and frames.shape == (3, 33, d) and seq.dtype == torch.float32
+        out[shape_key(shape) + "_seq"] = seq.numpy()
+        out[shape_key(shape) + "_frames"] = frames[0].numpy()
+    _write_npz_fixed(HERE / "golden_shapes.npz", out)
+    print("checkpoint-shape golden written to", HERE, f"({(HERE / 'golden_shapes.npz').stat().st_size} bytes)")
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["nokp"]:
         main_nokp()
     elif sys.argv[1:] == ["small"]:
         main_small()
+    elif sys.argv[1:] == ["shapes"]:
+        main_shapes()
     else:
         main()
         main_nokp()
         main_small()
+        main_shapes()
