@@ -241,6 +241,48 @@ int vge_centroid_accumulate(const float* seq_embed, const int32_t* class_id, int
 int vge_centroid_finalize(const float* sums, const float* counts, int C, int d, float* centroids,
                           vge_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Held-out validation loss: the checkpoint-selection criterion of the reference's training loop
+ * (evaluate_test_set, train.py:286-333: TCL + 10 x SupConWithHardNegatives against shuffled, reversed and static
+ * windows; train.py:450-455 keeps the checkpoint with the lowest value).  Forward only.  Every reduction runs in an
+ * order fixed by the problem size (no floating-point atomics): two calls on the same input give the same bits.
+ *
+ * vge_time_gather: out[b,t,:] = feats[b, src[b,t], :] -- partial_shuffle_within_window, reverse_sequence and
+ *   get_static_window (utils.py:65-95) as one index table (reverse: src[t] = T-1-t; static: src[t] = 0).
+ *   feats / out: device float [B,T,D], 16-byte aligned, out must not alias feats; src: device int32 [B,T];
+ *   T = 32, D a multiple of 4.  A bit-exact copy.  The caller owns the contract 0 <= src < T: the table is not
+ *   validated on the device (an entry outside the range gives an unspecified row of the same window).
+ *
+ * vge_tcl_loss: TCL.forward (losses.py:6-34) with its [B,B] / [B] broadcast stated literally -- element (i,j) is
+ *   divided by the denominator of row j.  With e_ij = exp(<z_i,z_j> / temperature), P(i) the same-label rows without
+ *   i and N(i) the other-label rows:
+ *     den_j  = sum_{k in P(j)} e_jk + k1 sum_{k in P(j)} exp(-<z_j,z_k>) + k2 sum_{k in N(j)} e_jk
+ *     loss_i = (1 / |P(i)|) sum_{j in P(i)} -log(e_ij / den_j);   loss = mean_i loss_i
+ *   emb: device float [B,d] (16-byte aligned); labels: device int32 [B]; loss: device double [1];
+ *   1 <= B <= 8192; d a multiple of 32 in [32, 256]; workspace: device scratch of >= vge_tcl_workspace_bytes(B).
+ *   Dot products, exp / log and sums in f64.  A row whose label appears once in the batch has |P(i)| = 0: its loss
+ *   is 0/0 = NaN and so is the batch loss, exactly as in the reference, whose evaluate_test_set then skips the batch
+ *   (train.py:312-313); every other input with finite exponentials gives a finite loss.
+ *
+ * vge_hardneg_loss: SupConWithHardNegatives.forward(anchor, anchor, neg) (losses.py:37-56):
+ *   loss = mean_i [ logsumexp(s_ap, s_ah) - s_ap ], s_ap = <a_i,a_i> / temperature, s_ah = <a_i,n_i> / temperature
+ *   (s_ap is computed, not taken as 1 / temperature).  anchor / neg: device float [B,d], 16-byte aligned, d a
+ *   multiple of 4; loss: device double [1].
+ *   The reference's weight of 10 (train.py:516-521) is the caller's.
+ *
+ * vge_centroid_distance: evaluate_test_set_centroid_distance's per-sample term (train.py:366-378):
+ *   dist[i] = || normalize(emb_i) - centroids[labels[i]] ||_2 (F.normalize eps 1e-12), float32; a label outside
+ *   [0, C) gives NaN (the reference's `continue`).  emb [n,d], centroids [C,d], dist [n]: device float.
+ */
+int vge_time_gather(const float* feats, const int32_t* src, int B, int T, int D, float* out, vge_stream_t stream);
+size_t vge_tcl_workspace_bytes(int B);
+int vge_tcl_loss(const float* emb, const int32_t* labels, int B, int d, double temperature, double k1, double k2,
+                 void* workspace, size_t workspace_bytes, double* loss, vge_stream_t stream);
+int vge_hardneg_loss(const float* anchor, const float* neg, int B, int d, double temperature, double* loss,
+                     vge_stream_t stream);
+int vge_centroid_distance(const float* emb, const int32_t* labels, const float* centroids, int n, int C, int d,
+                          float* dist, vge_stream_t stream);
+
 const char* vge_last_error(void);
 const char* vge_version(void);
 

@@ -33,7 +33,8 @@ EXPORTS = ["vge_featurize", "vge_featurize_layout", "vge_layout_feat_dim", "vge_
            "vge_frcnn_create", "vge_frcnn_reserve", "vge_frcnn_destroy", "vge_frcnn_shapes", "vge_frcnn_detect",
            "vge_frcnn_profile_begin", "vge_frcnn_profile_read",
            "vge_jpeg_probe", "vge_jpeg_make_layout", "vge_jpeg_entropy_decode", "vge_jpeg_reconstruct",
-           "vge_jpeg_reconstruct_host"]
+           "vge_jpeg_reconstruct_host",
+           "vge_time_gather", "vge_tcl_workspace_bytes", "vge_tcl_loss", "vge_hardneg_loss", "vge_centroid_distance"]
 
 
 class VgeError(RuntimeError):
@@ -135,12 +136,18 @@ def load() -> C.CDLL:
         "vge_jpeg_entropy_decode": [C.POINTER(C.c_char_p), i32, i32, C.POINTER(JpegLayout), vp, vp, vp],
         "vge_jpeg_reconstruct": [vp, vp, C.POINTER(JpegLayout), i32, vp, vp],
         "vge_jpeg_reconstruct_host": [vp, vp, C.POINTER(JpegLayout), i32, i32, vp],
+        "vge_time_gather": [vp, vp, i32, i32, i32, vp, vp],
+        "vge_tcl_workspace_bytes": [i32],
+        "vge_tcl_loss": [vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, vp, C.c_size_t, vp, vp],
+        "vge_hardneg_loss": [vp, vp, i32, i32, C.c_double, vp, vp],
+        "vge_centroid_distance": [vp, vp, vp, i32, i32, i32, vp, vp],
     }
     for name, args in sig.items():
         f = getattr(lib, name)
         f.argtypes = args
         f.restype = C.c_int
     lib.vge_stats_workspace_bytes.restype = C.c_size_t
+    lib.vge_tcl_workspace_bytes.restype = C.c_size_t
     lib.vge_last_error.restype = C.c_char_p
     lib.vge_version.restype = C.c_char_p
     _lib = lib

@@ -303,3 +303,69 @@ def centroid_finalize(sums: torch.Tensor, counts: torch.Tensor) -> torch.Tensor:
     L.check(lib.vge_centroid_finalize(_ptr(sums), _ptr(counts), C_, d, _ptr(out), _stream(sums.device)),
             "vge_centroid_finalize")
     return out
+
+
+# ----------------------------------------------------------------------------- held-out validation loss (vge.validate)
+
+def time_gather(feats: torch.Tensor, src: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[b,t,:] = feats[b, src[b,t], :] (vge_time_gather): the shuffled / reversed / static windows of
+    utils.py:65-95 from one int32 [B,32] index table.  The table's range is checked here (the C caller owns that
+    contract): an entry outside [0, 32) is refused."""
+    lib = L.load()
+    B, T, D = feats.shape
+    if feats.dtype != torch.float32 or src.dtype != torch.int32 or tuple(src.shape) != (B, T):
+        raise L.VgeError(f"time_gather: feats must be float32 [B,T,D] and src int32 [{B},{T}]")
+    if B and (int(src.min()) < 0 or int(src.max()) >= T):
+        raise L.VgeError(f"time_gather: src entries must lie in [0, {T})")
+    if out is None:
+        out = torch.empty_like(feats)
+    elif tuple(out.shape) != (B, T, D) or out.dtype != torch.float32 or out.device != feats.device:
+        raise L.VgeError(f"time_gather: out must be a float32 [{B},{T},{D}] tensor on {feats.device}")
+    L.check(lib.vge_time_gather(_ptr(feats), _ptr(src), B, T, D, _ptr(out), _stream(feats.device)), "vge_time_gather")
+    return out
+
+
+def tcl_loss(emb: torch.Tensor, labels: torch.Tensor, temperature: float = 0.1, k1: float = 5000.0, k2: float = 1.0,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """TCL (losses.py:6-34) of emb [B,d] with int32 labels [B] -> device float64 [1]; NaN when a label appears once
+    in the batch, as the reference gives.  out: a float64 device tensor whose first element is written."""
+    lib = L.load()
+    B, d = emb.shape
+    if emb.dtype != torch.float32 or labels.dtype != torch.int32 or labels.numel() != B:
+        raise L.VgeError("tcl_loss: emb must be float32 [B,d] and labels int32 [B]")
+    if out is None:
+        out = torch.empty((1,), device=emb.device, dtype=torch.float64)
+    wsb = int(lib.vge_tcl_workspace_bytes(B))
+    ws = torch.empty(max(wsb, 8) // 8, dtype=torch.float64, device=emb.device)
+    L.check(lib.vge_tcl_loss(_ptr(emb), _ptr(labels), B, d, float(temperature), float(k1), float(k2), _ptr(ws), wsb,
+                             _ptr(out), _stream(emb.device)), "vge_tcl_loss")
+    return out
+
+
+def hardneg_loss(anchor: torch.Tensor, neg: torch.Tensor, temperature: float = 0.07,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """SupConWithHardNegatives(anchor, anchor, neg) (losses.py:37-56) -> device float64 [1], unweighted."""
+    lib = L.load()
+    B, d = anchor.shape
+    if anchor.dtype != torch.float32 or neg.dtype != torch.float32 or tuple(neg.shape) != (B, d):
+        raise L.VgeError("hardneg_loss: anchor and neg must be float32 [B,d]")
+    if out is None:
+        out = torch.empty((1,), device=anchor.device, dtype=torch.float64)
+    L.check(lib.vge_hardneg_loss(_ptr(anchor), _ptr(neg), B, d, float(temperature), _ptr(out),
+                                 _stream(anchor.device)), "vge_hardneg_loss")
+    return out
+
+
+def centroid_distance(emb: torch.Tensor, labels: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
+    """|| normalize(emb_i) - centroids[labels[i]] ||_2 (train.py:366-378) -> float32 [n]; NaN where the label is
+    outside [0, C)."""
+    lib = L.load()
+    n, d = emb.shape
+    C_ = int(centroids.shape[0])
+    if emb.dtype != torch.float32 or labels.dtype != torch.int32 or labels.numel() != n or \
+            centroids.dtype != torch.float32 or int(centroids.shape[1]) != d:
+        raise L.VgeError("centroid_distance: emb float32 [n,d], labels int32 [n], centroids float32 [C,d]")
+    out = torch.empty((n,), device=emb.device, dtype=torch.float32)
+    L.check(lib.vge_centroid_distance(_ptr(emb), _ptr(labels), _ptr(centroids), n, C_, d, _ptr(out),
+                                      _stream(emb.device)), "vge_centroid_distance")
+    return out
