@@ -18,6 +18,14 @@
  * Conventions as in vge.h: device pointers unless stated, asynchronous on the given stream, int status return.
  * Arithmetic: bf16 operands and activations, f32 accumulation / epilogues / box arithmetic, FrozenBN folded into the
  * conv weights at load.  Grouped 3x3 convolutions run as 64-channel block-diagonal slices of the implicit-GEMM conv.
+ *
+ * Frames are H x W with any aspect ratio; a detector takes a new frame size at any call (the workspace is rebuilt).
+ * Pinned against the oracle (tests/test_frcnn.py, tests/test_frcnn_shapes.py): resized sizes from 1 x 333 and 64 x 107
+ * to 800 x 800 and 750 x 1333, landscape and portrait, upscaled and downscaled, padded on either or both axes (padded
+ * 32 x 352 .. 768 x 1344, P5 from 1 x 11 and 2 x 4 to 25 x 25 and 24 x 42).  Refused with VGE_ERR_ARG by
+ * vge_frcnn_shapes / vge_frcnn_reserve / vge_frcnn_detect before any launch: a frame whose short edge rounds to 0
+ * pixels under the max_size cap (aspect ratio above ~2 max_size, e.g. 1 x 667 at max_size 333), and a chunk whose
+ * row or thread counts would pass 2^31.
  */
 #ifndef VGE_FRCNN_H
 #define VGE_FRCNN_H

@@ -355,6 +355,12 @@ int vge_frcnn_shapes(const vge_frcnn* m, int H, int W, int* out) {
   if (!m || !out || H <= 0 || W <= 0) return fail(VGE_ERR_ARG, "vge_frcnn_shapes: bad argument");
   int nh, nw;
   output_shape(H, W, m->c.min_size, m->c.max_size, nh, nw);
+  // an aspect ratio above ~2 max_size: the short edge rounds to 0 pixels under the max_size cap (PIL refuses to resize
+  // to an empty image); nothing downstream has a shape then
+  if (nh < 1 || nw < 1)
+    return fail(VGE_ERR_ARG, "vge_frcnn: " + std::to_string(H) + " x " + std::to_string(W) + " frames resize to " +
+                                 std::to_string(nh) + " x " + std::to_string(nw) + " under max_size " +
+                                 std::to_string(m->c.max_size) + ": an axis rounds to 0 pixels");
   const int hp = rup(nh, 32), wp = rup(nw, 32);
   out[0] = nh;
   out[1] = nw;
@@ -374,7 +380,7 @@ int vge_frcnn_reserve(vge_frcnn* m, int chunk, int H, int W) {
   if (!m || chunk <= 0 || H <= 0 || W <= 0) return fail(VGE_ERR_ARG, "vge_frcnn_reserve: bad argument");
   if (chunk <= m->chunk && H == m->rH && W == m->rW) return VGE_OK;
   int sh[15];
-  vge_frcnn_shapes(m, H, W, sh);
+  if (const int rc = vge_frcnn_shapes(m, H, W, sh); rc != VGE_OK) return rc;  // (a frame that resizes to nothing)
   {  // index widths: every kernel addresses activations through 64-bit offsets; what stays 32-bit is a layer's row
      // count (n x h x w, the GEMM M) and the thread count of the elementwise kernels (resize: one per padded pixel,
      // pool / upsample: one per 8 channels of a pixel) -- both must stay under 2^31 for the chunk
