@@ -87,6 +87,37 @@ int vge_jpeg_reconstruct(const int16_t* coef, const uint16_t* qtab, const vge_jp
 int vge_jpeg_reconstruct_host(const int16_t* coef, const uint16_t* qtab, const vge_jpeg_layout* layout, int n_frames,
                               int n_threads, uint8_t* rgb);
 
+/* ---- Encoding: the mirror images of the calls above, for frames that are already in memory.
+ *
+ * The reference's models only ever see pixels that went through cv2.imwrite (libjpeg's encoder: quality 95, 4:2:0) and
+ * cv2.imread.  Huffman coding is lossless, so those pixels are reconstruct(forward(frame)): the forward call below is
+ * the lossy half of libjpeg's encoder -- RGB -> YCbCr, edge expansion, box downsampling, the "islow" forward DCT,
+ * quantisation, the dummy blocks that fill the last MCU column / row -- and yields exactly the coefficients
+ * vge_jpeg_entropy_decode reads out of the file libjpeg would have written, in the same layout.  The entropy encoder
+ * writes that file (baseline JFIF, the standard Huffman tables, no restart markers, one interleaved scan), byte for byte.
+ * Only 3-component layouts are encoded (frames here are RGB): a 1-component layout gets VGE_JPEG_ERR_COMPONENTS. */
+
+/* libjpeg's tables for `quality` (clamped to 1..100; Annex K.1 / K.2 scaled and forced to baseline) -> qtab
+ * uint16 [3][64], natural order: component 0 the luminance table, components 1 and 2 the chrominance table. */
+int vge_jpeg_quant_tables(int quality, uint16_t* qtab);
+
+/* Device: rgb uint8 [n_frames, height, width, 3], qtab uint16 [3][64] (one set for the whole call, entries 1..255),
+ * coef int16 [n_frames, blocks_per_frame, 64] are device pointers (qtab and coef 16-byte aligned; rgb 4-byte aligned
+ * when the width is a multiple of 4, where it is read as dwords); stream
+ * is a hipStream_t (NULL: the default stream); the launch is asynchronous.  Every block of the layout is written. */
+int vge_jpeg_forward(const uint8_t* rgb, const vge_jpeg_layout* layout, int n_frames, const uint16_t* qtab,
+                     int16_t* coef, void* stream);
+
+/* Host: the same in host memory, plain C++, multithreaded over frames. */
+int vge_jpeg_forward_host(const uint8_t* rgb, const vge_jpeg_layout* layout, int n_frames, int n_threads,
+                          const uint16_t* qtab, int16_t* coef);
+
+/* Host, multithreaded over frames: frame i's coefficients -> a complete JPEG file at paths[i]; sizes[i] its length in
+ * bytes.  A frame whose file cannot be written gets VGE_JPEG_ERR_IO in status[i] (sizes[i] 0) and does not disturb the
+ * others.  sizes and status may be NULL. */
+int vge_jpeg_entropy_encode(const int16_t* coef, const uint16_t* qtab, const vge_jpeg_layout* layout, int n,
+                            int n_threads, const char* const* paths, int64_t* sizes, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

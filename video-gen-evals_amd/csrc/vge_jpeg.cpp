@@ -1,7 +1,8 @@
 // Host half of the JPEG frame front end (include/vge_frames.h): header probe, the baseline entropy decoder (marker
 // parsing + Huffman decoding into int16 coefficients, a pool of host threads over frames) and the plain-C++
 // reconstruct that the no-GPU path and the CPU tests use.  The device reconstruct is vge_jpeg.hip; both take their
-// arithmetic from vge_jpeg_math.h.
+// arithmetic from vge_jpeg_math.h.  Below them the mirror images for encoding: libjpeg's quantisation tables, the
+// plain-C++ forward transform (the device one is vge_jpeg_enc.hip) and the baseline Huffman encoder that writes files.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -425,9 +426,353 @@ void reconstruct_frame(const int16_t* coef, const uint16_t* qtab, const vge_jpeg
     }
 }
 
+// ------------------------------------------------------------------ encoding: the mirror images of the above
+// Annex K.1 / K.2 base tables, natural order.
+const uint8_t kBaseLuma[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,
+                               14, 13, 16, 24, 40,  57,  69,  56,  14, 17, 22, 29, 51,  87,  80,  62,
+                               18, 22, 37, 56, 68,  109, 103, 77,  24, 35, 55, 64, 81,  104, 113, 92,
+                               49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+const uint8_t kBaseChroma[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99,
+                                 99, 99, 47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
+                                 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+
+// Annex K.3 - K.6 Huffman tables: code counts per length, then the symbols.
+const uint8_t kDcLumaBits[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
+const uint8_t kDcChromaBits[16] = {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
+const uint8_t kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+const uint8_t kAcLumaBits[16] = {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125};
+const uint8_t kAcLumaVals[162] = {
+    1,   2,   3,   0,   4,   17,  5,   18,  33,  49,  65,  6,   19,  81,  97,  7,   34,  113, 20,  50,  129, 145, 161,
+    8,   35,  66,  177, 193, 21,  82,  209, 240, 36,  51,  98,  114, 130, 9,   10,  22,  23,  24,  25,  26,  37,  38,
+    39,  40,  41,  42,  52,  53,  54,  55,  56,  57,  58,  67,  68,  69,  70,  71,  72,  73,  74,  83,  84,  85,  86,
+    87,  88,  89,  90,  99,  100, 101, 102, 103, 104, 105, 106, 115, 116, 117, 118, 119, 120, 121, 122, 131, 132, 133,
+    134, 135, 136, 137, 138, 146, 147, 148, 149, 150, 151, 152, 153, 154, 162, 163, 164, 165, 166, 167, 168, 169, 170,
+    178, 179, 180, 181, 182, 183, 184, 185, 186, 194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211, 212, 213, 214,
+    215, 216, 217, 218, 225, 226, 227, 228, 229, 230, 231, 232, 233, 234, 241, 242, 243, 244, 245, 246, 247, 248, 249,
+    250};
+const uint8_t kAcChromaBits[16] = {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119};
+const uint8_t kAcChromaVals[162] = {
+    0,   1,   2,   3,   17,  4,   5,   33,  49,  6,   18,  65,  81,  7,   97,  113, 19,  34,  50,  129, 8,   20,  66,
+    145, 161, 177, 193, 9,   35,  51,  82,  240, 21,  98,  114, 209, 10,  22,  36,  52,  225, 37,  241, 23,  24,  25,
+    26,  38,  39,  40,  41,  42,  53,  54,  55,  56,  57,  58,  67,  68,  69,  70,  71,  72,  73,  74,  83,  84,  85,
+    86,  87,  88,  89,  90,  99,  100, 101, 102, 103, 104, 105, 106, 115, 116, 117, 118, 119, 120, 121, 122, 130, 131,
+    132, 133, 134, 135, 136, 137, 138, 146, 147, 148, 149, 150, 151, 152, 153, 154, 162, 163, 164, 165, 166, 167, 168,
+    169, 170, 178, 179, 180, 181, 182, 183, 184, 185, 186, 194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211, 212,
+    213, 214, 215, 216, 217, 218, 226, 227, 228, 229, 230, 231, 232, 233, 234, 242, 243, 244, 245, 246, 247, 248, 249,
+    250};
+
+struct EncHuff {
+  uint16_t code[256];
+  uint8_t len[256];  // 0: no code for the symbol
+  EncHuff(const uint8_t* bits, const uint8_t* vals) {
+    memset(len, 0, sizeof(len));
+    memset(code, 0, sizeof(code));
+    int c = 0, k = 0;
+    for (int l = 1; l <= 16; ++l) {
+      for (int i = 0; i < bits[l - 1]; ++i, ++k, ++c) {
+        code[vals[k]] = (uint16_t)c;
+        len[vals[k]] = (uint8_t)l;
+      }
+      c <<= 1;
+    }
+  }
+};
+
+struct EncTables {
+  EncHuff dc[2] = {EncHuff(kDcLumaBits, kDcVals), EncHuff(kDcChromaBits, kDcVals)};
+  EncHuff ac[2] = {EncHuff(kAcLumaBits, kAcLumaVals), EncHuff(kAcChromaBits, kAcChromaVals)};
+};
+
+struct BitWriter {
+  std::vector<uint8_t>& out;
+  uint64_t acc = 0;
+  int cnt = 0;
+  void byte(uint32_t b) {
+    out.push_back((uint8_t)b);
+    if (b == 0xFF) out.push_back(0);  // a stuffed FF
+  }
+  void put(uint32_t v, int n) {  // n <= 27
+    acc = (acc << n) | (v & ((1u << n) - 1));
+    cnt += n;
+    while (cnt >= 8) {
+      cnt -= 8;
+      byte((uint32_t)(acc >> cnt) & 0xFF);
+    }
+  }
+  void flush() {
+    if (cnt) put(0x7F, 8 - cnt);  // pad the final byte with 1 bits
+  }
+};
+
+inline int bit_length(int a) {
+  int n = 0;
+  while (a) {
+    ++n;
+    a >>= 1;
+  }
+  return n;
+}
+
+// False: a coefficient beyond what baseline Huffman coding can carry (DC difference > 11 bits, AC > 10 bits).
+bool encode_block(BitWriter& w, const EncHuff& dc, const EncHuff& ac, int& pred, const int16_t* blk) {
+  const int diff = (int)blk[0] - pred;
+  pred = blk[0];
+  int n = bit_length(std::abs(diff));
+  if (n > 11) return false;
+  w.put(dc.code[n], dc.len[n]);
+  if (n) w.put((uint32_t)(diff < 0 ? diff - 1 : diff), n);
+  int run = 0;
+  for (int k = 1; k < 64; ++k) {
+    const int v = blk[kZigzag[k]];
+    if (v == 0) {
+      ++run;
+      continue;
+    }
+    for (; run > 15; run -= 16) w.put(ac.code[0xF0], ac.len[0xF0]);
+    n = bit_length(std::abs(v));
+    if (n > 10) return false;
+    const int sym = (run << 4) | n;
+    w.put(ac.code[sym], ac.len[sym]);
+    w.put((uint32_t)(v < 0 ? v - 1 : v), n);
+    run = 0;
+  }
+  if (run) w.put(ac.code[0], ac.len[0]);  // EOB
+  return true;
+}
+
+void put_marker(std::vector<uint8_t>& o, int m, size_t payload) {
+  o.push_back(0xFF);
+  o.push_back((uint8_t)m);
+  o.push_back((uint8_t)((payload + 2) >> 8));
+  o.push_back((uint8_t)((payload + 2) & 255));
+}
+
+void put_dht(std::vector<uint8_t>& o, int id, const uint8_t* bits, const uint8_t* vals) {
+  size_t n = 0;
+  for (int l = 0; l < 16; ++l) n += bits[l];
+  put_marker(o, 0xC4, 17 + n);
+  o.push_back((uint8_t)id);
+  o.insert(o.end(), bits, bits + 16);
+  o.insert(o.end(), vals, vals + n);
+}
+
+// A complete baseline JFIF file, segment for segment what libjpeg writes with its defaults (jcmarker.c): SOI, APP0
+// (JFIF 1.01, no density unit, 1 x 1), one DQT per table, SOF0, one DHT per table, SOS, one interleaved scan, EOI.
+bool encode_file(const int16_t* coef, const uint16_t* qtab, const vge_jpeg_layout& L, const EncTables& T,
+                 std::vector<uint8_t>& o) {
+  o.clear();
+  o.reserve((size_t)L.blocks_per_frame * 24 + 1024);
+  o.push_back(0xFF);
+  o.push_back(0xD8);
+  put_marker(o, 0xE0, 14);
+  const uint8_t jfif[14] = {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+  o.insert(o.end(), jfif, jfif + 14);
+  for (int t = 0; t < 2; ++t) {  // component 0: table 0; components 1 and 2: table 1
+    put_marker(o, 0xDB, 65);
+    o.push_back((uint8_t)t);
+    for (int k = 0; k < 64; ++k) o.push_back((uint8_t)qtab[64 * t + kZigzag[k]]);
+  }
+  put_marker(o, 0xC0, 15);
+  const uint8_t sof[15] = {8,
+                           (uint8_t)(L.height >> 8),
+                           (uint8_t)(L.height & 255),
+                           (uint8_t)(L.width >> 8),
+                           (uint8_t)(L.width & 255),
+                           3,
+                           1,
+                           (uint8_t)((L.h0 << 4) | L.v0),
+                           0,
+                           2,
+                           0x11,
+                           1,
+                           3,
+                           0x11,
+                           1};
+  o.insert(o.end(), sof, sof + 15);
+  put_dht(o, 0x00, kDcLumaBits, kDcVals);
+  put_dht(o, 0x10, kAcLumaBits, kAcLumaVals);
+  put_dht(o, 0x01, kDcChromaBits, kDcVals);
+  put_dht(o, 0x11, kAcChromaBits, kAcChromaVals);
+  put_marker(o, 0xDA, 10);
+  const uint8_t sos[10] = {3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0};
+  o.insert(o.end(), sos, sos + 10);
+  BitWriter w{o};
+  int pred[3] = {0, 0, 0};
+  for (int my = 0; my < L.mcus_y; ++my)
+    for (int mx = 0; mx < L.mcus_x; ++mx)
+      for (int c = 0; c < 3; ++c) {
+        const int ch = c == 0 ? L.h0 : 1, cv = c == 0 ? L.v0 : 1, t = c == 0 ? 0 : 1;
+        for (int v = 0; v < cv; ++v)
+          for (int h = 0; h < ch; ++h) {
+            const int bx = mx * ch + h, by = my * cv + v;
+            const int16_t* blk = coef + ((size_t)L.off[c] + (size_t)by * L.bw[c] + bx) * 64;
+            if (!encode_block(w, T.dc[t], T.ac[t], pred[c], blk)) return false;
+          }
+      }
+  w.flush();
+  o.push_back(0xFF);
+  o.push_back(0xD9);
+  return true;
+}
+
+bool write_file(const char* path, const std::vector<uint8_t>& data) {
+  const int fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
+  if (fd < 0) return false;
+  size_t done = 0;
+  while (done < data.size()) {
+    const ssize_t k = ::write(fd, data.data() + done, data.size() - done);
+    if (k <= 0) break;
+    done += (size_t)k;
+  }
+  const bool ok = ::close(fd) == 0 && done == data.size();
+  return ok;
+}
+
+// The lossy half of libjpeg's encoder for one frame: colour conversion, edge expansion, downsampling, FDCT,
+// quantisation, dummy blocks (arithmetic and rules: vge_jpeg_math.h).
+void forward_frame(const uint8_t* rgb, const uint16_t* qtab, const vge_jpeg_layout& L, int16_t* coef) {
+  using namespace vge_jpeg;
+  const int W = L.width, H = L.height;
+  const int hs = L.h0 == 2 ? 1 : 0, vs = L.v0 == 2 ? 1 : 0;
+  std::vector<uint8_t> plane;
+  for (int c = 0; c < 3; ++c) {
+    const int pw = L.bw[c] * 8, ph = L.bh[c] * 8;
+    const int chs = c ? hs : 0, cvs = c ? vs : 0;
+    plane.resize((size_t)pw * ph);
+    auto comp = [&](int x, int y) {  // component c of input pixel (x, y); the right edge replicates the last column
+      const uint8_t* p = rgb + ((size_t)y * W + std::min(x, W - 1)) * 3;
+      int yy, cb, cr;
+      rgb_to_ycc(p[0], p[1], p[2], &yy, &cb, &cr);
+      return c == 0 ? yy : (c == 1 ? cb : cr);
+    };
+    for (int j = 0; j < ph; ++j) {
+      int r0 = std::min(j, H - 1), r1 = r0;
+      if (cvs) down_rows_v2(j, H, &r0, &r1);
+      for (int i = 0; i < pw; ++i) {
+        int s;
+        if (!chs)
+          s = comp(i, r0);
+        else if (!cvs)
+          s = down_h2v1(comp(2 * i, r0), comp(2 * i + 1, r0), i);
+        else
+          s = down_h2v2(comp(2 * i, r0), comp(2 * i + 1, r0), comp(2 * i, r1), comp(2 * i + 1, r1), i);
+        plane[(size_t)j * pw + i] = (uint8_t)s;
+      }
+    }
+    const int cw = (W + (1 << chs) - 1) >> chs, chh = (H + (1 << cvs) - 1) >> cvs;
+    const int rbw = (cw + 7) / 8, rbh = (chh + 7) / 8;
+    const uint16_t* q = qtab + 64 * c;
+    for (int by = 0; by < L.bh[c]; ++by)
+      for (int bx = 0; bx < L.bw[c]; ++bx) {
+        int sx = bx, sy = by;
+        const bool dummy = dummy_source(&sx, &sy, c == 0 ? L.h0 : 1, rbw, rbh);
+        int32_t ws[64], d[8], o[8];
+        for (int v = 0; v < 8; ++v) {  // rows
+          const uint8_t* src = plane.data() + (size_t)(sy * 8 + v) * pw + sx * 8;
+          for (int u = 0; u < 8; ++u) d[u] = (int32_t)src[u] - 128;
+          fdct_pass(d, o);
+          for (int u = 0; u < 8; ++u) ws[v * 8 + u] = fdct_row_out(o[u], u);
+        }
+        int16_t* dst = coef + ((size_t)L.off[c] + (size_t)by * L.bw[c] + bx) * 64;
+        for (int u = 0; u < 8; ++u) {  // columns
+          for (int v = 0; v < 8; ++v) d[v] = ws[v * 8 + u];
+          fdct_pass(d, o);
+          for (int v = 0; v < 8; ++v) {
+            const int k = v * 8 + u;
+            dst[k] = (dummy && k) ? (int16_t)0 : (int16_t)quantise(fdct_col_out(o[v], v), q[k]);
+          }
+        }
+      }
+  }
+}
+
+bool qtab_ok(const uint16_t* q) {
+  for (int k = 0; k < 192; ++k)
+    if (q[k] < 1 || q[k] > 255) return false;
+  return true;
+}
+
 }  // namespace
 
 extern "C" {
+
+int vge_jpeg_quant_tables(int quality, uint16_t* qtab) {
+  if (!qtab) {
+    set_last_error("vge_jpeg_quant_tables: bad argument");
+    return VGE_JPEG_ERR_ARG;
+  }
+  const int q = std::max(1, std::min(quality, 100));
+  const int scale = q < 50 ? 5000 / q : 200 - 2 * q;
+  for (int c = 0; c < 3; ++c)
+    for (int k = 0; k < 64; ++k) {
+      const int v = ((c == 0 ? kBaseLuma[k] : kBaseChroma[k]) * scale + 50) / 100;
+      qtab[64 * c + k] = (uint16_t)std::max(1, std::min(v, 255));
+    }
+  return VGE_JPEG_OK;
+}
+
+int vge_jpeg_forward_host(const uint8_t* rgb, const vge_jpeg_layout* layout, int n_frames, int n_threads,
+                          const uint16_t* qtab, int16_t* coef) {
+  if (n_frames < 0 || !layout_ok(layout) || !qtab || !qtab_ok(qtab) || (n_frames > 0 && (!rgb || !coef))) {
+    set_last_error("vge_jpeg_forward_host: bad argument (layout not from vge_jpeg_make_layout, null buffer, or a "
+                   "quantisation entry outside 1..255)");
+    return VGE_JPEG_ERR_ARG;
+  }
+  if (layout->n_comp != 3) {
+    set_last_error("vge_jpeg_forward_host: only 3-component (RGB) frames are encoded");
+    return VGE_JPEG_ERR_COMPONENTS;
+  }
+  const vge_jpeg_layout L = *layout;
+  const size_t per = (size_t)L.blocks_per_frame * 64, px = (size_t)L.width * L.height * 3;
+  parallel_for(n_frames, n_threads,
+               [&](int i) { forward_frame(rgb + px * (size_t)i, qtab, L, coef + per * (size_t)i); });
+  return VGE_JPEG_OK;
+}
+
+int vge_jpeg_entropy_encode(const int16_t* coef, const uint16_t* qtab, const vge_jpeg_layout* layout, int n,
+                            int n_threads, const char* const* paths, int64_t* sizes, int32_t* status) {
+  if (n < 0 || !layout_ok(layout) || !qtab || !qtab_ok(qtab) || (n > 0 && (!coef || !paths))) {
+    set_last_error("vge_jpeg_entropy_encode: bad argument");
+    return VGE_JPEG_ERR_ARG;
+  }
+  if (layout->n_comp != 3) {
+    set_last_error("vge_jpeg_entropy_encode: only 3-component (RGB) frames are encoded");
+    return VGE_JPEG_ERR_COMPONENTS;
+  }
+  const vge_jpeg_layout L = *layout;
+  const size_t per = (size_t)L.blocks_per_frame * 64;
+  const EncTables T;
+  std::vector<int32_t> st((size_t)n, VGE_JPEG_OK);
+  std::vector<int64_t> sz((size_t)n, 0);
+  parallel_for(n, n_threads, [&](int i) {
+    int s = VGE_JPEG_ERR_ARG;
+    try {
+      std::vector<uint8_t> buf;
+      if (!paths[i]) {
+        s = VGE_JPEG_ERR_ARG;
+      } else if (!encode_file(coef + per * (size_t)i, qtab, L, T, buf)) {
+        s = VGE_JPEG_ERR_ARG;  // a coefficient no baseline stream can carry: not the forward transform's output
+      } else if (!write_file(paths[i], buf)) {
+        s = VGE_JPEG_ERR_IO;
+      } else {
+        s = VGE_JPEG_OK;
+        sz[(size_t)i] = (int64_t)buf.size();
+      }
+    } catch (...) {
+      s = VGE_JPEG_ERR_IO;  // out of memory
+    }
+    st[(size_t)i] = s;
+  });
+  if (sizes) memcpy(sizes, sz.data(), (size_t)n * sizeof(int64_t));
+  if (status) memcpy(status, st.data(), (size_t)n * sizeof(int32_t));
+  for (int i = 0; i < n; ++i)
+    if (st[(size_t)i] != VGE_JPEG_OK) {
+      set_last_error(std::string("vge_jpeg_entropy_encode: ") + (paths[i] ? paths[i] : "(null)") + ": " +
+                     (st[(size_t)i] == VGE_JPEG_ERR_IO ? "cannot write the file" : "bad argument or coefficients"));
+      return st[(size_t)i];
+    }
+  return VGE_JPEG_OK;
+}
 
 int vge_jpeg_probe(const char* const* paths, int n, int n_threads, vge_jpeg_info* info) {
   if (n < 0 || (n > 0 && (!paths || !info))) {

@@ -252,7 +252,8 @@ def _mesh_info(frame_ids, rows) -> dict:
             for j, fi in enumerate(frame_ids)}
 
 
-def extract_videos(hmr, wholebody, detector, videos, mesh_root, kp_root, max_frames: int = 1024) -> Dict[str, Optional[str]]:
+def extract_videos(hmr, wholebody, detector, videos, mesh_root, kp_root, max_frames: int = 1024,
+                   jpeg_quality: Optional[int] = None) -> Dict[str, Optional[str]]:
     """extract_mesh.py:150-241 + process_video.py:59-94 over a list of videos, batched for the GPU: videos are
     (stem, uint8 [T, H, W, 3] device frames) of any lengths; consecutive videos are packed into passes of at most
     `max_frames` frames (a longer video is a pass of its own), and each pass runs the gate detector (detectron2 Faster
@@ -261,10 +262,18 @@ def extract_videos(hmr, wholebody, detector, videos, mesh_root, kp_root, max_fra
     time: the single-person gate and its 80 % rule (mesh_generator.py:101-117), <mesh_root>/<stem>.npz of the kept
     frames (extract_mesh.py:35-43; a rejected video gets none: the not-single list) and
     <kp_root>/<stem>/keypoints.npy of every frame (process_video.py writes them for every video).
+    jpeg_quality: None hands the frames to the models as they are; a quality (the reference's is 95) first sends each
+    pass's frames through vge.frames.jpeg_roundtrip on their device, so the gate detector, DWPose and the person crops
+    see the pixels the reference's models see, which only ever read frames back from its JPEG cache
+    (extract_mesh.py:47-82, 200-209: cv2.imwrite, then cv2.imread).
     Returns {stem: npz path or None}."""
     out: Dict[str, Optional[str]] = {}
     for group in _pack_passes([(stem, fr, int(fr.shape[0])) for stem, fr in videos], max_frames):
-        for stem, kp, valid, rows in _run_pass(hmr, wholebody, detector, [(s, f) for s, f, _ in group]):
+        members = [(s, f) for s, f, _ in group]
+        if jpeg_quality is not None:
+            from .frames import jpeg_roundtrip
+            members = [(s, jpeg_roundtrip(f, quality=jpeg_quality)) for s, f in members]
+        for stem, kp, valid, rows in _run_pass(hmr, wholebody, detector, members):
             save_keypoints(kp, Path(kp_root), "", stem)
             if valid is None:
                 out[stem] = None

@@ -6,6 +6,10 @@ gives the same pixels: Huffman decoding on host threads (vge_jpeg_entropy_decode
 upload on the caller's stream, and dequantise / IDCT / upsample / colour convert in one HIP kernel
 (vge_jpeg_reconstruct); without a GPU, or with device="cpu", the plain-C++ reconstruct with the same arithmetic.
 Channel order is RGB (the extractors here take RGB; cv2.imread's BGR is the same bytes reversed).
+
+The other direction, for frames that are already in memory: jpeg_roundtrip gives the pixels cv2.imwrite + cv2.imread
+would give without leaving the device (vge_jpeg_forward, then vge_jpeg_reconstruct), and save_frames writes the
+reference's frame_%06d.jpg cache byte for byte as libjpeg does (vge_jpeg_forward + vge_jpeg_entropy_encode).
 """
 from __future__ import annotations
 
@@ -86,6 +90,110 @@ def _decode_group(paths: List[str], lay: L.JpegLayout, device, threads: int):
         L.check(lib.vge_jpeg_reconstruct_host(coef.data_ptr(), qtab.data_ptr(), C.byref(lay), n, int(threads),
                                               out.data_ptr()), "vge_jpeg_reconstruct_host")
     return out, status
+
+
+SUBSAMPLING = {"420": (2, 2), "422": (2, 1), "444": (1, 1)}   # luma sampling factors (h0, v0)
+_qtab_cache: dict = {}   # (device, quality) -> int16-bits [3, 64] tensor on the device
+
+
+def quant_tables(quality: int) -> np.ndarray:
+    """libjpeg's quantisation tables for a quality: uint16 [3, 64], natural order (vge_jpeg_quant_tables)."""
+    q = np.zeros((3, 64), np.uint16)
+    L.check(L.load().vge_jpeg_quant_tables(int(quality), q.ctypes.data), "vge_jpeg_quant_tables")
+    return q
+
+
+def _check_rgb_frames(frames):
+    import torch
+    if not (isinstance(frames, torch.Tensor) and frames.dtype == torch.uint8 and frames.dim() == 4
+            and frames.shape[3] == 3 and frames.shape[1] > 0 and frames.shape[2] > 0):
+        raise ValueError("frames must be a uint8 [F, H, W, 3] RGB tensor")
+    return frames.contiguous()
+
+
+def _forward(frames, quality: int, subsampling: str, threads: int = 0):
+    """The lossy half of libjpeg's encoder: frames (contiguous uint8 [F, H, W, 3]) -> (layout, int16 coefficients
+    [F, blocks_per_frame, 64] and the tables as int16 bits [3, 64], both on the frames' device).  On a GPU tensor: the
+    HIP kernel on the current stream, nothing synchronises."""
+    import torch
+    if subsampling not in SUBSAMPLING:
+        raise ValueError(f"subsampling must be one of {sorted(SUBSAMPLING)}, not {subsampling!r}")
+    lib = L.load()
+    F, H, W = (int(v) for v in frames.shape[:3])
+    lay = make_layout(W, H, 3, *SUBSAMPLING[subsampling])
+    coef = torch.empty((F, lay.blocks_per_frame, 64), dtype=torch.int16, device=frames.device)
+    key = (str(frames.device), max(1, min(int(quality), 100)))
+    qtab = _qtab_cache.get(key)
+    if qtab is None:   # uploaded once per device and quality, so that later calls touch no host memory
+        qtab = torch.from_numpy(quant_tables(quality).view(np.int16)).to(frames.device)
+        if frames.device.type == "cuda":
+            torch.cuda.current_stream(frames.device).synchronize()   # any stream may use the cached copy afterwards
+        _qtab_cache[key] = qtab
+    if frames.device.type == "cuda":
+        with torch.cuda.device(frames.device):
+            L.check(lib.vge_jpeg_forward(frames.data_ptr(), C.byref(lay), F, qtab.data_ptr(), coef.data_ptr(),
+                                         torch.cuda.current_stream(frames.device).cuda_stream), "vge_jpeg_forward")
+    else:
+        L.check(lib.vge_jpeg_forward_host(frames.data_ptr(), C.byref(lay), F, int(threads), qtab.data_ptr(),
+                                          coef.data_ptr()), "vge_jpeg_forward_host")
+    return lay, coef, qtab
+
+
+def jpeg_roundtrip(frames, quality: int = 95, subsampling: str = "420", out=None):
+    """The pixels cv2.imread gives back after cv2.imwrite(frame, quality) -- what every model of the reference sees
+    (extract_mesh.py:47-82, 200-209) -- without writing a file: Huffman coding is lossless, so the round trip is the
+    encoder's lossy half (vge_jpeg_forward) followed by the decoder's (vge_jpeg_reconstruct).  frames: uint8
+    [F, H, W, 3] RGB; returns the same shape on the same device (`out`, when given).  On a GPU tensor both kernels run
+    on the current stream with no host synchronisation and no host copy; on a CPU tensor, the two host functions."""
+    import torch
+    frames = _check_rgb_frames(frames)
+    if out is None:
+        out = torch.empty_like(frames)
+    elif not (out.dtype == torch.uint8 and out.shape == frames.shape and out.device == frames.device
+              and out.is_contiguous()):
+        raise ValueError("out must be a contiguous uint8 tensor of the frames' shape on the frames' device")
+    F = int(frames.shape[0])
+    if F == 0:
+        return out
+    lay, coef, qtab = _forward(frames, quality, subsampling)
+    qtab_f = qtab.unsqueeze(0).expand(F, 3, 64).contiguous()   # the reconstruct takes one set of tables per frame
+    lib = L.load()
+    if frames.device.type == "cuda":
+        with torch.cuda.device(frames.device):
+            L.check(lib.vge_jpeg_reconstruct(coef.data_ptr(), qtab_f.data_ptr(), C.byref(lay), F, out.data_ptr(),
+                                             torch.cuda.current_stream(frames.device).cuda_stream),
+                    "vge_jpeg_reconstruct")
+    else:
+        L.check(lib.vge_jpeg_reconstruct_host(coef.data_ptr(), qtab_f.data_ptr(), C.byref(lay), F, 0, out.data_ptr()),
+                "vge_jpeg_reconstruct_host")
+    return out
+
+
+def save_frames(frames, folder: PathLike, quality: int = 95, subsampling: str = "420", start: int = 0,
+                threads: int = 0) -> List[str]:
+    """Write frames (uint8 [F, H, W, 3] RGB, GPU or CPU) as <folder>/frame_%06d.jpg numbered from `start`: the frame
+    cache extract_mesh.py:47-69 writes with cv2.imwrite, byte for byte what libjpeg writes.  The forward kernel, one
+    copy of the coefficients into pinned memory, then Huffman coding and file writing on host threads
+    (vge_jpeg_entropy_encode).  list_frames / load_frames read the folder back.  Returns the paths; raises VgeError
+    naming the first file that could not be written (the other files are written)."""
+    import torch
+    frames = _check_rgb_frames(frames)
+    folder = os.fspath(folder)
+    os.makedirs(folder, exist_ok=True)
+    F = int(frames.shape[0])
+    paths = [os.path.join(folder, f"frame_{int(start) + i:06d}.jpg") for i in range(F)]
+    if F == 0:
+        return paths
+    lay, coef, qtab = _forward(frames, quality, subsampling, threads)
+    if coef.device.type == "cuda":
+        host = torch.empty(coef.shape, dtype=torch.int16, pin_memory=True)
+        host.copy_(coef, non_blocking=True)
+        torch.cuda.current_stream(coef.device).synchronize()
+        coef = host
+    L.check(L.load().vge_jpeg_entropy_encode(coef.data_ptr(), quant_tables(quality).ctypes.data, C.byref(lay), F,
+                                             int(threads), _paths_array(paths), None, None),
+            "vge_jpeg_entropy_encode")
+    return paths
 
 
 def load_videos(videos: Sequence[Union[PathLike, Sequence[PathLike]]], device=None, threads: int = 0):

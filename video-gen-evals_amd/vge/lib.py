@@ -34,6 +34,7 @@ EXPORTS = ["vge_featurize", "vge_featurize_layout", "vge_layout_feat_dim", "vge_
            "vge_frcnn_profile_begin", "vge_frcnn_profile_read",
            "vge_jpeg_probe", "vge_jpeg_make_layout", "vge_jpeg_entropy_decode", "vge_jpeg_reconstruct",
            "vge_jpeg_reconstruct_host",
+           "vge_jpeg_quant_tables", "vge_jpeg_forward", "vge_jpeg_forward_host", "vge_jpeg_entropy_encode",
            "vge_time_gather", "vge_tcl_workspace_bytes", "vge_tcl_loss", "vge_hardneg_loss", "vge_centroid_distance"]
 
 
@@ -136,6 +137,10 @@ def load() -> C.CDLL:
         "vge_jpeg_entropy_decode": [C.POINTER(C.c_char_p), i32, i32, C.POINTER(JpegLayout), vp, vp, vp],
         "vge_jpeg_reconstruct": [vp, vp, C.POINTER(JpegLayout), i32, vp, vp],
         "vge_jpeg_reconstruct_host": [vp, vp, C.POINTER(JpegLayout), i32, i32, vp],
+        "vge_jpeg_quant_tables": [i32, vp],
+        "vge_jpeg_forward": [vp, C.POINTER(JpegLayout), i32, vp, vp, vp],
+        "vge_jpeg_forward_host": [vp, C.POINTER(JpegLayout), i32, i32, vp, vp],
+        "vge_jpeg_entropy_encode": [vp, vp, C.POINTER(JpegLayout), i32, i32, C.POINTER(C.c_char_p), vp, vp],
         "vge_time_gather": [vp, vp, i32, i32, i32, vp, vp],
         "vge_tcl_workspace_bytes": [i32],
         "vge_tcl_loss": [vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, vp, C.c_size_t, vp, vp],
