@@ -94,7 +94,8 @@ int vge_jpeg_reconstruct_host(const int16_t* coef, const uint16_t* qtab, const v
  * the lossy half of libjpeg's encoder -- RGB -> YCbCr, edge expansion, box downsampling, the "islow" forward DCT,
  * quantisation, the dummy blocks that fill the last MCU column / row -- and yields exactly the coefficients
  * vge_jpeg_entropy_decode reads out of the file libjpeg would have written, in the same layout.  The entropy encoder
- * writes that file (baseline JFIF, the standard Huffman tables, no restart markers, one interleaved scan), byte for byte.
+ * writes that file (baseline JFIF, the standard Huffman tables, no restart markers, one interleaved scan), byte for byte:
+ * on host threads to paths or into memory, or on the device into memory (plan / emit below).
  * Only 3-component layouts are encoded (frames here are RGB): a 1-component layout gets VGE_JPEG_ERR_COMPONENTS. */
 
 /* libjpeg's tables for `quality` (clamped to 1..100; Annex K.1 / K.2 scaled and forced to baseline) -> qtab
@@ -117,6 +118,42 @@ int vge_jpeg_forward_host(const uint8_t* rgb, const vge_jpeg_layout* layout, int
  * others.  sizes and status may be NULL. */
 int vge_jpeg_entropy_encode(const int16_t* coef, const uint16_t* qtab, const vge_jpeg_layout* layout, int n,
                             int n_threads, const char* const* paths, int64_t* sizes, int32_t* status);
+
+/* Host: the same files into memory.  out == NULL: sizes only.  Otherwise file i goes to out + offsets[i] (offsets are
+ * the caller's: files may be packed with gaps, no byte outside a file is touched); a file that does not fit into
+ * out_bytes gets VGE_JPEG_ERR_ARG.  A frame with a DC difference beyond 11 bits or an AC value beyond 10 bits (not the
+ * forward transform's output) gets VGE_JPEG_ERR_ARG and size 0 and does not disturb the others.  sizes and status may
+ * be NULL. */
+int vge_jpeg_entropy_encode_mem(const int16_t* coef, const uint16_t* qtab, const vge_jpeg_layout* layout, int n,
+                                int n_threads, const int64_t* offsets, uint8_t* out, int64_t out_bytes, int64_t* sizes,
+                                int32_t* status);
+
+/* Host, multithreaded over files: sizes[i] bytes at data + offsets[i] -> paths[i].  A file that cannot be written gets
+ * VGE_JPEG_ERR_IO in status[i] (may be NULL) and does not disturb the others. */
+int vge_jpeg_write_files(const uint8_t* data, const int64_t* offsets, const int64_t* sizes, int n, int n_threads,
+                         const char* const* paths, int32_t* status);
+
+/* Device entropy coder (csrc/vge_jpeg_huff.hip): the coefficient buffer exactly as vge_jpeg_forward leaves it -> the
+ * same files as above, on the device.  All pointers but the layout are device pointers (workspace 16-byte aligned,
+ * coef 2-byte, sizes / offsets 8-byte); the calls are asynchronous on `stream` and allocate nothing.  The split is at
+ * the only point where the host must learn something, the file sizes:
+ *   plan   codes every block (one wave per block, one lane per zigzag position), builds each frame's unstuffed scan in
+ *          the workspace and counts its FF bytes; sizes[i] is file i's length, status[i] VGE_JPEG_OK -- or size 0 and
+ *          VGE_JPEG_ERR_ARG for a frame baseline coding cannot carry.  It clears what it accumulates into itself, so
+ *          a workspace may be reused as it is.
+ *   emit   writes file i (headers, the scan with 00 stuffed after every FF, EOI) to out + offsets[i] and touches no
+ *          byte outside [offsets[i], offsets[i] + sizes[i]).  A refused frame writes nothing.  The offsets live on the
+ *          device, so the host cannot compare them with out_bytes: a negative out_bytes is VGE_JPEG_ERR_ARG before
+ *          any launch, and a file that would not lie inside [0, out_bytes) is left unwritten by the kernel.
+ * Frames of more than 2^31 / 1658 blocks are refused with VGE_JPEG_ERR_ARG (bit positions are 32-bit).
+ * vge_jpeg_entropy_segment_blocks: the scan blocks one workgroup codes -- a frame is ceil(blocks / that) independent
+ * work segments (exported for the tests, which make sure a case spans several). */
+size_t vge_jpeg_entropy_workspace_bytes(const vge_jpeg_layout* layout, int n_frames);
+int vge_jpeg_entropy_plan(const int16_t* coef, const vge_jpeg_layout* layout, int n_frames, void* workspace,
+                          int64_t* sizes, int32_t* status, void* stream);
+int vge_jpeg_entropy_emit(const void* workspace, const uint16_t* qtab, const vge_jpeg_layout* layout, int n_frames,
+                          const int64_t* offsets, uint8_t* out, int64_t out_bytes, void* stream);
+int vge_jpeg_entropy_segment_blocks(void);
 
 #ifdef __cplusplus
 }

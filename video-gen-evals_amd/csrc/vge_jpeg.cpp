@@ -2,7 +2,8 @@
 // parsing + Huffman decoding into int16 coefficients, a pool of host threads over frames) and the plain-C++
 // reconstruct that the no-GPU path and the CPU tests use.  The device reconstruct is vge_jpeg.hip; both take their
 // arithmetic from vge_jpeg_math.h.  Below them the mirror images for encoding: libjpeg's quantisation tables, the
-// plain-C++ forward transform (the device one is vge_jpeg_enc.hip) and the baseline Huffman encoder that writes files.
+// plain-C++ forward transform (the device one is vge_jpeg_enc.hip) and the baseline Huffman encoder, into files or into
+// memory (the device one is vge_jpeg_huff.hip; the Huffman tables both carry are vge_jpeg_huff_tables.h).
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -19,6 +20,7 @@
 
 #include "../../include/vge_frames.h"
 #include "../../include/vge_ingest.h"
+#include "vge_jpeg_huff_tables.h"
 #include "vge_jpeg_math.h"
 
 namespace vge {
@@ -71,9 +73,7 @@ void parallel_for(int n, int n_threads, Fn fn) {
   for (std::thread& th : pool) th.join();
 }
 
-const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+using vge_jpeg::kZigzag;  // vge_jpeg_huff_tables.h
 
 const char* status_name(int st) {
   switch (st) {
@@ -436,30 +436,14 @@ const uint8_t kBaseChroma[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66,
                                  99, 99, 47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
                                  99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
 
-// Annex K.3 - K.6 Huffman tables: code counts per length, then the symbols.
-const uint8_t kDcLumaBits[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
-const uint8_t kDcChromaBits[16] = {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
-const uint8_t kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
-const uint8_t kAcLumaBits[16] = {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125};
-const uint8_t kAcLumaVals[162] = {
-    1,   2,   3,   0,   4,   17,  5,   18,  33,  49,  65,  6,   19,  81,  97,  7,   34,  113, 20,  50,  129, 145, 161,
-    8,   35,  66,  177, 193, 21,  82,  209, 240, 36,  51,  98,  114, 130, 9,   10,  22,  23,  24,  25,  26,  37,  38,
-    39,  40,  41,  42,  52,  53,  54,  55,  56,  57,  58,  67,  68,  69,  70,  71,  72,  73,  74,  83,  84,  85,  86,
-    87,  88,  89,  90,  99,  100, 101, 102, 103, 104, 105, 106, 115, 116, 117, 118, 119, 120, 121, 122, 131, 132, 133,
-    134, 135, 136, 137, 138, 146, 147, 148, 149, 150, 151, 152, 153, 154, 162, 163, 164, 165, 166, 167, 168, 169, 170,
-    178, 179, 180, 181, 182, 183, 184, 185, 186, 194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211, 212, 213, 214,
-    215, 216, 217, 218, 225, 226, 227, 228, 229, 230, 231, 232, 233, 234, 241, 242, 243, 244, 245, 246, 247, 248, 249,
-    250};
-const uint8_t kAcChromaBits[16] = {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119};
-const uint8_t kAcChromaVals[162] = {
-    0,   1,   2,   3,   17,  4,   5,   33,  49,  6,   18,  65,  81,  7,   97,  113, 19,  34,  50,  129, 8,   20,  66,
-    145, 161, 177, 193, 9,   35,  51,  82,  240, 21,  98,  114, 209, 10,  22,  36,  52,  225, 37,  241, 23,  24,  25,
-    26,  38,  39,  40,  41,  42,  53,  54,  55,  56,  57,  58,  67,  68,  69,  70,  71,  72,  73,  74,  83,  84,  85,
-    86,  87,  88,  89,  90,  99,  100, 101, 102, 103, 104, 105, 106, 115, 116, 117, 118, 119, 120, 121, 122, 130, 131,
-    132, 133, 134, 135, 136, 137, 138, 146, 147, 148, 149, 150, 151, 152, 153, 154, 162, 163, 164, 165, 166, 167, 168,
-    169, 170, 178, 179, 180, 181, 182, 183, 184, 185, 186, 194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211, 212,
-    213, 214, 215, 216, 217, 218, 226, 227, 228, 229, 230, 231, 232, 233, 234, 242, 243, 244, 245, 246, 247, 248, 249,
-    250};
+// Annex K.3 - K.6 Huffman tables: vge_jpeg_huff_tables.h, shared with the device coder (vge_jpeg_huff.hip).
+using vge_jpeg::kAcChromaBits;
+using vge_jpeg::kAcChromaVals;
+using vge_jpeg::kAcLumaBits;
+using vge_jpeg::kAcLumaVals;
+using vge_jpeg::kDcChromaBits;
+using vge_jpeg::kDcLumaBits;
+using vge_jpeg::kDcVals;
 
 struct EncHuff {
   uint16_t code[256];
@@ -615,16 +599,16 @@ bool encode_file(const int16_t* coef, const uint16_t* qtab, const vge_jpeg_layou
   return true;
 }
 
-bool write_file(const char* path, const std::vector<uint8_t>& data) {
+bool write_file(const char* path, const uint8_t* data, size_t size) {
   const int fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
   if (fd < 0) return false;
   size_t done = 0;
-  while (done < data.size()) {
-    const ssize_t k = ::write(fd, data.data() + done, data.size() - done);
+  while (done < size) {
+    const ssize_t k = ::write(fd, data + done, size - done);
     if (k <= 0) break;
     done += (size_t)k;
   }
-  const bool ok = ::close(fd) == 0 && done == data.size();
+  const bool ok = ::close(fd) == 0 && done == size;
   return ok;
 }
 
@@ -752,7 +736,7 @@ int vge_jpeg_entropy_encode(const int16_t* coef, const uint16_t* qtab, const vge
         s = VGE_JPEG_ERR_ARG;
       } else if (!encode_file(coef + per * (size_t)i, qtab, L, T, buf)) {
         s = VGE_JPEG_ERR_ARG;  // a coefficient no baseline stream can carry: not the forward transform's output
-      } else if (!write_file(paths[i], buf)) {
+      } else if (!write_file(paths[i], buf.data(), buf.size())) {
         s = VGE_JPEG_ERR_IO;
       } else {
         s = VGE_JPEG_OK;
@@ -769,6 +753,77 @@ int vge_jpeg_entropy_encode(const int16_t* coef, const uint16_t* qtab, const vge
     if (st[(size_t)i] != VGE_JPEG_OK) {
       set_last_error(std::string("vge_jpeg_entropy_encode: ") + (paths[i] ? paths[i] : "(null)") + ": " +
                      (st[(size_t)i] == VGE_JPEG_ERR_IO ? "cannot write the file" : "bad argument or coefficients"));
+      return st[(size_t)i];
+    }
+  return VGE_JPEG_OK;
+}
+
+int vge_jpeg_entropy_encode_mem(const int16_t* coef, const uint16_t* qtab, const vge_jpeg_layout* layout, int n,
+                                int n_threads, const int64_t* offsets, uint8_t* out, int64_t out_bytes, int64_t* sizes,
+                                int32_t* status) {
+  if (n < 0 || !layout_ok(layout) || !qtab || !qtab_ok(qtab) || (n > 0 && !coef) ||
+      (out && (out_bytes < 0 || (n > 0 && !offsets)))) {
+    set_last_error("vge_jpeg_entropy_encode_mem: bad argument");
+    return VGE_JPEG_ERR_ARG;
+  }
+  if (layout->n_comp != 3) {
+    set_last_error("vge_jpeg_entropy_encode_mem: only 3-component (RGB) frames are encoded");
+    return VGE_JPEG_ERR_COMPONENTS;
+  }
+  const vge_jpeg_layout L = *layout;
+  const size_t per = (size_t)L.blocks_per_frame * 64;
+  const EncTables T;
+  std::vector<int32_t> st((size_t)n, VGE_JPEG_OK);
+  std::vector<int64_t> sz((size_t)n, 0);
+  parallel_for(n, n_threads, [&](int i) {
+    int s = VGE_JPEG_ERR_ARG;
+    try {
+      std::vector<uint8_t> buf;
+      if (encode_file(coef + per * (size_t)i, qtab, L, T, buf)) {  // else: a coefficient no baseline stream can carry
+        const int64_t len = (int64_t)buf.size();
+        if (!out) {
+          s = VGE_JPEG_OK;
+        } else if (offsets[i] >= 0 && offsets[i] <= out_bytes && len <= out_bytes - offsets[i]) {
+          memcpy(out + offsets[i], buf.data(), buf.size());
+          s = VGE_JPEG_OK;
+        }
+        if (s == VGE_JPEG_OK) sz[(size_t)i] = len;
+      }
+    } catch (...) {
+      s = VGE_JPEG_ERR_IO;  // out of memory
+    }
+    st[(size_t)i] = s;
+  });
+  if (sizes) memcpy(sizes, sz.data(), (size_t)n * sizeof(int64_t));
+  if (status) memcpy(status, st.data(), (size_t)n * sizeof(int32_t));
+  for (int i = 0; i < n; ++i)
+    if (st[(size_t)i] != VGE_JPEG_OK) {
+      set_last_error("vge_jpeg_entropy_encode_mem: frame " + std::to_string(i) +
+                     (st[(size_t)i] == VGE_JPEG_ERR_IO ? ": out of memory"
+                                                       : ": coefficients beyond baseline coding, or no room in out"));
+      return st[(size_t)i];
+    }
+  return VGE_JPEG_OK;
+}
+
+int vge_jpeg_write_files(const uint8_t* data, const int64_t* offsets, const int64_t* sizes, int n, int n_threads,
+                         const char* const* paths, int32_t* status) {
+  if (n < 0 || (n > 0 && (!data || !offsets || !sizes || !paths))) {
+    set_last_error("vge_jpeg_write_files: bad argument");
+    return VGE_JPEG_ERR_ARG;
+  }
+  std::vector<int32_t> st((size_t)n, VGE_JPEG_OK);
+  parallel_for(n, n_threads, [&](int i) {
+    if (!paths[i] || offsets[i] < 0 || sizes[i] < 0)
+      st[(size_t)i] = VGE_JPEG_ERR_ARG;
+    else if (!write_file(paths[i], data + offsets[i], (size_t)sizes[i]))
+      st[(size_t)i] = VGE_JPEG_ERR_IO;
+  });
+  if (status) memcpy(status, st.data(), (size_t)n * sizeof(int32_t));
+  for (int i = 0; i < n; ++i)
+    if (st[(size_t)i] != VGE_JPEG_OK) {
+      set_last_error(std::string("vge_jpeg_write_files: ") + (paths[i] ? paths[i] : "(null)") + ": " +
+                     (st[(size_t)i] == VGE_JPEG_ERR_IO ? "cannot write the file" : "bad argument"));
       return st[(size_t)i];
     }
   return VGE_JPEG_OK;

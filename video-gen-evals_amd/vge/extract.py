@@ -253,7 +253,7 @@ def _mesh_info(frame_ids, rows) -> dict:
 
 
 def extract_videos(hmr, wholebody, detector, videos, mesh_root, kp_root, max_frames: int = 1024,
-                   jpeg_quality: Optional[int] = None) -> Dict[str, Optional[str]]:
+                   jpeg_quality: Optional[int] = None, frame_cache=None) -> Dict[str, Optional[str]]:
     """extract_mesh.py:150-241 + process_video.py:59-94 over a list of videos, batched for the GPU: videos are
     (stem, uint8 [T, H, W, 3] device frames) of any lengths; consecutive videos are packed into passes of at most
     `max_frames` frames (a longer video is a pass of its own), and each pass runs the gate detector (detectron2 Faster
@@ -266,8 +266,18 @@ def extract_videos(hmr, wholebody, detector, videos, mesh_root, kp_root, max_fra
     pass's frames through vge.frames.jpeg_roundtrip on their device, so the gate detector, DWPose and the person crops
     see the pixels the reference's models see, which only ever read frames back from its JPEG cache
     (extract_mesh.py:47-82, 200-209: cv2.imwrite, then cv2.imread).
+    frame_cache: when given, each video's frames are also written to <frame_cache>/<stem>/frame_%06d.jpg at
+    `jpeg_quality` (95 when that is None) by vge.frames.save_frames -- GPU frames are Huffman-coded on the device, CPU
+    frames on the host -- so an in-memory extraction leaves the cache extract_frame_tree and the reference's
+    extract_mesh.py resume from.
     Returns {stem: npz path or None}."""
     out: Dict[str, Optional[str]] = {}
+    if frame_cache is not None:
+        from .frames import save_frames
+        videos = list(videos)
+        for stem, fr in videos:
+            save_frames(fr, Path(frame_cache) / stem, quality=95 if jpeg_quality is None else jpeg_quality,
+                        entropy="device" if fr.device.type == "cuda" else "host")
     for group in _pack_passes([(stem, fr, int(fr.shape[0])) for stem, fr in videos], max_frames):
         members = [(s, f) for s, f, _ in group]
         if jpeg_quality is not None:

@@ -10,6 +10,9 @@ Channel order is RGB (the extractors here take RGB; cv2.imread's BGR is the same
 The other direction, for frames that are already in memory: jpeg_roundtrip gives the pixels cv2.imwrite + cv2.imread
 would give without leaving the device (vge_jpeg_forward, then vge_jpeg_reconstruct), and save_frames writes the
 reference's frame_%06d.jpg cache byte for byte as libjpeg does (vge_jpeg_forward + vge_jpeg_entropy_encode).
+encode_frames gives the same files in memory; on a GPU tensor it also Huffman-codes on the device
+(vge_jpeg_entropy_plan / vge_jpeg_entropy_emit, csrc/vge_jpeg_huff.hip), and save_frames(entropy="device") writes
+its bytes.
 """
 from __future__ import annotations
 
@@ -169,27 +172,114 @@ def jpeg_roundtrip(frames, quality: int = 95, subsampling: str = "420", out=None
     return out
 
 
-def save_frames(frames, folder: PathLike, quality: int = 95, subsampling: str = "420", start: int = 0,
-                threads: int = 0) -> List[str]:
-    """Write frames (uint8 [F, H, W, 3] RGB, GPU or CPU) as <folder>/frame_%06d.jpg numbered from `start`: the frame
-    cache extract_mesh.py:47-69 writes with cv2.imwrite, byte for byte what libjpeg writes.  The forward kernel, one
-    copy of the coefficients into pinned memory, then Huffman coding and file writing on host threads
-    (vge_jpeg_entropy_encode).  list_frames / load_frames read the folder back.  Returns the paths; raises VgeError
-    naming the first file that could not be written (the other files are written)."""
+def _coefficients_on_host(coef):
+    """The coefficient tensor in host memory: one copy into pinned memory when it is on a GPU."""
+    import torch
+    if coef.device.type != "cuda":
+        return coef
+    host = torch.empty(coef.shape, dtype=torch.int16, pin_memory=True)
+    host.copy_(coef, non_blocking=True)
+    torch.cuda.current_stream(coef.device).synchronize()
+    return host
+
+
+def encode_frames(frames, quality: int = 95, subsampling: str = "420", entropy: Optional[str] = None,
+                  threads: int = 0, keep_on_device: bool = False):
+    """frames (uint8 [F, H, W, 3] RGB, GPU or CPU) -> (data, offsets): the complete JPEG files save_frames writes, in
+    memory.  data is a uint8 tensor, offsets int64 [F + 1]; file i is data[offsets[i]:offsets[i + 1]].
+    entropy "device" (the default for a GPU tensor): the forward kernel, vge_jpeg_entropy_plan, one copy of the F file
+    sizes to the host (the call's only host synchronisation before the result), an exclusive scan, and
+    vge_jpeg_entropy_emit; then one copy of the files into pinned memory, or none with keep_on_device=True (data is then
+    a tensor on the frames' device).  entropy "host" (the default, and the only choice, for a CPU tensor): the
+    coefficients are copied to the host and coded there (vge_jpeg_entropy_encode_mem: once for the sizes, once for the
+    bytes).  Raises VgeError for a frame that cannot be coded."""
     import torch
     frames = _check_rgb_frames(frames)
+    on_gpu = frames.device.type == "cuda"
+    if entropy is None:
+        entropy = "device" if on_gpu else "host"
+    if entropy not in ("host", "device"):
+        raise ValueError(f"entropy must be 'host' or 'device', not {entropy!r}")
+    if entropy == "device" and not on_gpu:
+        raise ValueError("entropy='device' needs frames on a GPU")
+    F = int(frames.shape[0])
+    offsets = np.zeros(F + 1, np.int64)
+    if F == 0:
+        if subsampling not in SUBSAMPLING:
+            raise ValueError(f"subsampling must be one of {sorted(SUBSAMPLING)}, not {subsampling!r}")
+        dev = frames.device if keep_on_device else "cpu"
+        return torch.empty(0, dtype=torch.uint8, device=dev), torch.from_numpy(offsets)
+    lib = L.load()
+    lay, coef, qtab = _forward(frames, quality, subsampling, threads)
+    if entropy == "host":
+        coef = _coefficients_on_host(coef)
+        q = quant_tables(quality)
+        sizes = np.zeros(F, np.int64)
+        L.check(lib.vge_jpeg_entropy_encode_mem(coef.data_ptr(), q.ctypes.data, C.byref(lay), F, int(threads), None,
+                                                None, 0, sizes.ctypes.data, None), "vge_jpeg_entropy_encode_mem")
+        np.cumsum(sizes, out=offsets[1:])
+        data = torch.empty(int(offsets[F]), dtype=torch.uint8, pin_memory=on_gpu and keep_on_device)
+        L.check(lib.vge_jpeg_entropy_encode_mem(coef.data_ptr(), q.ctypes.data, C.byref(lay), F, int(threads),
+                                                offsets.ctypes.data, data.data_ptr(), int(offsets[F]), None, None),
+                "vge_jpeg_entropy_encode_mem")
+        if keep_on_device and on_gpu:
+            data = data.to(frames.device)
+        return data, torch.from_numpy(offsets)
+    dev = frames.device
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        ws = torch.empty(int(lib.vge_jpeg_entropy_workspace_bytes(C.byref(lay), F)), dtype=torch.uint8, device=dev)
+        sizes_d = torch.empty(F, dtype=torch.int64, device=dev)
+        status_d = torch.empty(F, dtype=torch.int32, device=dev)
+        L.check(lib.vge_jpeg_entropy_plan(coef.data_ptr(), C.byref(lay), F, ws.data_ptr(), sizes_d.data_ptr(),
+                                          status_d.data_ptr(), stream.cuda_stream), "vge_jpeg_entropy_plan")
+        sizes = sizes_d.cpu().numpy()   # the host has to learn the sizes before it can place the files
+        if (sizes <= 0).any():          # a refused frame has size 0 (status VGE_JPEG_ERR_ARG)
+            raise L.VgeError(f"vge_jpeg_entropy_plan: frame {int(np.flatnonzero(sizes <= 0)[0])} holds a coefficient "
+                             "baseline Huffman coding cannot carry")
+        np.cumsum(sizes, out=offsets[1:])
+        offsets_d = torch.from_numpy(offsets[:F]).to(dev, non_blocking=True)
+        data = torch.empty(int(offsets[F]), dtype=torch.uint8, device=dev)
+        L.check(lib.vge_jpeg_entropy_emit(ws.data_ptr(), qtab.data_ptr(), C.byref(lay), F, offsets_d.data_ptr(),
+                                          data.data_ptr(), int(offsets[F]), stream.cuda_stream),
+                "vge_jpeg_entropy_emit")
+        if not keep_on_device:
+            host = torch.empty(data.shape, dtype=torch.uint8, pin_memory=True)
+            host.copy_(data, non_blocking=True)
+            stream.synchronize()
+            data = host
+    return data, torch.from_numpy(offsets)
+
+
+def save_frames(frames, folder: PathLike, quality: int = 95, subsampling: str = "420", start: int = 0,
+                threads: int = 0, entropy: str = "host") -> List[str]:
+    """Write frames (uint8 [F, H, W, 3] RGB, GPU or CPU) as <folder>/frame_%06d.jpg numbered from `start`: the frame
+    cache extract_mesh.py:47-69 writes with cv2.imwrite, byte for byte what libjpeg writes.  entropy "host": the forward
+    kernel, one copy of the coefficients into pinned memory, then Huffman coding and file writing on host threads
+    (vge_jpeg_entropy_encode).  entropy "device" (GPU frames only): encode_frames codes the files on the device, one
+    copy of the finished files, and the host threads only write them (vge_jpeg_write_files).  list_frames /
+    load_frames read the folder back.  Returns the paths; raises VgeError naming the first file that could not be
+    written (the other files are written)."""
+    frames = _check_rgb_frames(frames)
+    if entropy not in ("host", "device"):
+        raise ValueError(f"entropy must be 'host' or 'device', not {entropy!r}")
+    if entropy == "device" and frames.device.type != "cuda":
+        raise ValueError("entropy='device' needs frames on a GPU")
     folder = os.fspath(folder)
     os.makedirs(folder, exist_ok=True)
     F = int(frames.shape[0])
     paths = [os.path.join(folder, f"frame_{int(start) + i:06d}.jpg") for i in range(F)]
     if F == 0:
         return paths
+    if entropy == "device":
+        data, offsets = encode_frames(frames, quality, subsampling, entropy="device", threads=threads)
+        off = offsets.numpy()
+        sizes = np.ascontiguousarray(np.diff(off))
+        L.check(L.load().vge_jpeg_write_files(data.data_ptr(), off.ctypes.data, sizes.ctypes.data, F, int(threads),
+                                              _paths_array(paths), None), "vge_jpeg_write_files")
+        return paths
     lay, coef, qtab = _forward(frames, quality, subsampling, threads)
-    if coef.device.type == "cuda":
-        host = torch.empty(coef.shape, dtype=torch.int16, pin_memory=True)
-        host.copy_(coef, non_blocking=True)
-        torch.cuda.current_stream(coef.device).synchronize()
-        coef = host
+    coef = _coefficients_on_host(coef)
     L.check(L.load().vge_jpeg_entropy_encode(coef.data_ptr(), quant_tables(quality).ctypes.data, C.byref(lay), F,
                                              int(threads), _paths_array(paths), None, None),
             "vge_jpeg_entropy_encode")

@@ -35,6 +35,8 @@ EXPORTS = ["vge_featurize", "vge_featurize_layout", "vge_layout_feat_dim", "vge_
            "vge_jpeg_probe", "vge_jpeg_make_layout", "vge_jpeg_entropy_decode", "vge_jpeg_reconstruct",
            "vge_jpeg_reconstruct_host",
            "vge_jpeg_quant_tables", "vge_jpeg_forward", "vge_jpeg_forward_host", "vge_jpeg_entropy_encode",
+           "vge_jpeg_entropy_encode_mem", "vge_jpeg_write_files", "vge_jpeg_entropy_workspace_bytes",
+           "vge_jpeg_entropy_plan", "vge_jpeg_entropy_emit", "vge_jpeg_entropy_segment_blocks",
            "vge_time_gather", "vge_tcl_workspace_bytes", "vge_tcl_loss", "vge_hardneg_loss", "vge_centroid_distance"]
 
 
@@ -141,6 +143,12 @@ def load() -> C.CDLL:
         "vge_jpeg_forward": [vp, C.POINTER(JpegLayout), i32, vp, vp, vp],
         "vge_jpeg_forward_host": [vp, C.POINTER(JpegLayout), i32, i32, vp, vp],
         "vge_jpeg_entropy_encode": [vp, vp, C.POINTER(JpegLayout), i32, i32, C.POINTER(C.c_char_p), vp, vp],
+        "vge_jpeg_entropy_encode_mem": [vp, vp, C.POINTER(JpegLayout), i32, i32, vp, vp, C.c_int64, vp, vp],
+        "vge_jpeg_write_files": [vp, vp, vp, i32, i32, C.POINTER(C.c_char_p), vp],
+        "vge_jpeg_entropy_workspace_bytes": [C.POINTER(JpegLayout), i32],
+        "vge_jpeg_entropy_plan": [vp, C.POINTER(JpegLayout), i32, vp, vp, vp, vp],
+        "vge_jpeg_entropy_emit": [vp, vp, C.POINTER(JpegLayout), i32, vp, vp, C.c_int64, vp],
+        "vge_jpeg_entropy_segment_blocks": [],
         "vge_time_gather": [vp, vp, i32, i32, i32, vp, vp],
         "vge_tcl_workspace_bytes": [i32],
         "vge_tcl_loss": [vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, vp, C.c_size_t, vp, vp],
@@ -153,6 +161,7 @@ def load() -> C.CDLL:
         f.restype = C.c_int
     lib.vge_stats_workspace_bytes.restype = C.c_size_t
     lib.vge_tcl_workspace_bytes.restype = C.c_size_t
+    lib.vge_jpeg_entropy_workspace_bytes.restype = C.c_size_t
     lib.vge_last_error.restype = C.c_char_p
     lib.vge_version.restype = C.c_char_p
     _lib = lib
