@@ -15,102 +15,8 @@
 #include <atomic>
 
 #include "../../include/vge.h"
-
-namespace vge {
-// launchers (vge_featurize.hip / vge_encoder.hip / vge_score.hip)
-hipError_t launch_featurize_tiles(const float*, const float*, const float*, const float*, const float*, const int*,
-                                  const void*, const int*, int, const float*, const float*, float*, int, hipStream_t);
-hipError_t launch_stats_colsum(const float*, const void*, int, int, int, double*, double*, hipStream_t);
-hipError_t launch_stats_finalize(const double*, long long, long long, float*, float*, int, hipStream_t);
-struct EncDescHost {
-  const float* stem; const float* conv; const float* proj; const float* gn_w; const float* gn_b;
-  int in_col, d_in, n_stem_panels, ld;
-};
-struct FuseParamsHost {
-  const float* kv_w; const float* kv_b; const float* u;
-  float inv_tau[8]; float bias[8]; int n_mod; int has_motion[8];
-};
-struct GemmArgsHost {
-  const float* A; int lda; const float* W; float* out; int ldo; int M, K, N;
-  const float* bias; const float* res; int ldr; const float* ln_w; const float* ln_b; const float* pe; const float* cls;
-};
-hipError_t encoder_kernel_setup();
-hipError_t encoder_x3_kernel_setup();
-hipError_t launch_pack_x3(const float* W, int N, int K_real, int ldk, int conv, int nch, int* sh, float* cs, int* bad,
-                          _Float16* out, hipStream_t s);
-struct EncDescX3Host {
-  const _Float16* stem; const _Float16* conv; const _Float16* proj; const float* gn_w; const float* gn_b;
-  const float* cs; const float* fold;
-  int in_col, d_in, n_stem_panels, ld;
-  float gn_gmax[4], gn_bmax[4];  // max |gamma|, max |beta| per GroupNorm
-};
-struct GemmArgsX3Host {
-  const float* A; int lda; const _Float16* W; float* out; int ldo; int M, K, N;
-  const float* bias; const float* res; int ldr; const float* ln_w; const float* ln_b; const float* pe; const float* cls;
-  const float* cs;
-};
-hipError_t launch_conv_encoders_x3(const float*, int, const void*, int, unsigned, float*, bool, bool, hipStream_t);
-hipError_t encoder_x3s_kernel_setup();
-hipError_t launch_conv_encoders_x3s(const float*, int, const void*, int, unsigned, float*, int*, bool, hipStream_t);
-
-bool conv_f16w_plan(int n_windows, int n_enc, int wmax, int& G, int& R, int& U);
-hipError_t launch_conv_f16w_table(int n_windows, int n_enc, int G, int R, int U, int* d_table, hipStream_t s);
-hipError_t launch_conv_encoders_f16w(const float*, int, const void*, float*, const int*, int, int, hipStream_t);
-hipError_t launch_gemm_x3(int, const GemmArgsX3Host&, hipStream_t);
-struct FfnArgsX3Host {
-  const float* X1; float* out; int M;
-  const _Float16* W1; const float* cs1; const float* b1;
-  const _Float16* W2; const float* cs2; const float* b2;
-  const float* ln_w; const float* ln_b;
-};
-hipError_t launch_ffn_x3(const FfnArgsX3Host&, hipStream_t);
-struct TxLayerX3Host {  // vge_transformer_x3.hip
-  const _Float16* in_w;  const float* in_cs; const float* in_b;
-  const _Float16* out_w; const float* out_cs; const float* out_b;
-  const float* n1_w; const float* n1_b;
-  const _Float16* l1_w; const float* l1_cs; const float* l1_b;
-  const _Float16* l2_w; const float* l2_cs; const float* l2_b;
-  const float* n2_w; const float* n2_b;
-  int e_x1, e_x2, e_h, pad;  // static split exponents of LN1 / LN2 outputs and of the FFN hidden
-};
-struct TxArgsX3Host {
-  const float* pooled; int n_windows, n_layers;
-  const _Float16* ov_w; const float* ov_cs;
-  const float* cls; const float* pe;
-  const TxLayerX3Host* layers;  // host array [n_layers], n_layers <= 8 (passed as kernel arguments)
-  float* seq; float* frame; float* tc;
-};
-hipError_t transformer_x3_kernel_setup();
-hipError_t launch_transformer_x3(const TxArgsX3Host&, int, hipStream_t);
-hipError_t launch_conv_encoders(const float*, int, const void*, int, float*, hipStream_t);
-hipError_t launch_fuse(const float*, int, const FuseParamsHost&, float*, hipStream_t);
-hipError_t launch_gemm(int, const GemmArgsHost&, hipStream_t);
-hipError_t launch_attn(const float*, int, float*, hipStream_t);
-hipError_t launch_embed_tc(const float*, int, float*, float*, float*, hipStream_t);
-// the generic-shape exact-f32 path (vge_encoder_gen.hip)
-struct GenFuseHost {
-  const float* kv_w; const float* kv_b; const float* u;
-  float inv_tau[8], bias[8];
-  int n_mod, d;
-  int has_motion[8];
-};
-hipError_t launch_gen_conv(const float* x, int ldx, int xcol, int cin, const float* W, int cout, int taps, int dil, int epi,
-                           const float* res, float* out, int n_windows, hipStream_t s);
-hipError_t launch_gen_groupnorm(float* x, int n_windows, int d, const float* g, const float* b, hipStream_t s);
-hipError_t launch_gen_fuse(const float* enc_out, int n_rows, const GenFuseHost& f, float* pooled_pre, hipStream_t s);
-hipError_t launch_gen_gemm(const float* A, int lda, const float* W, int M, int N, int K, const float* bias, int epi,
-                           const float* res, const float* pe, const float* cls, float* out, int ldo, hipStream_t s);
-hipError_t launch_gen_attn(const float* qkv, int n_windows, int d, int heads, float* out, hipStream_t s);
-hipError_t launch_gen_add_ln(const float* a, const float* b, int rows, int d, const float* g, const float* be, float* out,
-                             hipStream_t s);
-hipError_t launch_gen_embed_tc(const float* x, int n_windows, int d, float* seq, float* frame, float* tc, hipStream_t s);
-hipError_t launch_centroid_accum(const float*, const int*, int, int, int, float*, float*, hipStream_t);
-hipError_t launch_centroid_final(const float*, const float*, int, int, float*, hipStream_t);
-hipError_t launch_tc_windows(const float*, int, int, int, float*, hipStream_t);
-hipError_t launch_score_videos(const float*, const float*, const int*, const int*, const float*, int, int, float*,
-                               double*, hipStream_t);
-enum { EPI_TOKENS = 0, EPI_BIAS = 1, EPI_BIAS_RELU = 2, EPI_BIAS_RES_LN = 3 };
-}  // namespace vge
+#include "vge_core.h"
+#include "vge_error.h"
 
 namespace {
 
@@ -242,7 +148,7 @@ struct GenModel {
     int in_col, d_in;
   };
   std::vector<Enc> encs;
-  vge::GenFuseHost fuse{};
+  vge::GenFuse fuse{};
   const float *Wov = nullptr, *cls = nullptr, *pe = nullptr;
   struct Lyr {
     const float *in_w, *in_b, *out_w, *out_b, *n1w, *n1b, *l1w, *l1b, *l2w, *l2b, *n2w, *n2b;
@@ -268,8 +174,9 @@ struct vge_encoder {
   float* wbuf = nullptr;
   _Float16* hbuf = nullptr;
   size_t n_half = 0, n_f32 = 0;   // element counts of hbuf / wbuf (vge_debug_encoder_images)
-  void* d_encs = nullptr;         // EncDescHost[10] or EncDescX3Host[10]
-  std::vector<vge::TxLayerX3Host> tx_layers;  // x3: the fused transformer kernel's layer table
+  vge::EncDesc* d_encs = nullptr;       // f32: the conv encoders' descriptors [n_enc]
+  vge::EncDescX3* d_encs_x3 = nullptr;  // x3: the same for the 3xfp16 / fp16 kernels
+  vge::TxArgsX3 tx{};             // x3: the fused transformer kernel's arguments (vge_encode adds the per-call fields)
   bool tx_fused = true;           // x3: one fused transformer launch (VGE_X3_UNFUSED=1: per-layer kernels)
   unsigned stem_heavy = 0;        // bit e: encoder e's stem spans more than one 256-wide K panel (vit)
   bool x3s = false;               // VGE_F32X3: the staggered conv kernel on GroupNorm-folded weights (VGE_X3S=0: off)
@@ -297,7 +204,7 @@ struct vge_encoder {
   hipStream_t tail = nullptr;
   bool tail_set = false, tail_pending = false;
   hipEvent_t fuse_done = nullptr, tail_done = nullptr;
-  vge::FuseParamsHost fuse{};
+  vge::FuseParams fuse{};
   const void* Wov = nullptr;      // packed (f32 chunks or fp16 chunks)
   const float* Wov_cs = nullptr;  // x3: its column scales
   struct Layer {
@@ -322,8 +229,693 @@ struct vge_encoder {
 };
 
 namespace vge {
-void set_last_error(const std::string& msg) { g_err = msg; }  // vge_hmr.cpp
+void set_last_error(const std::string& msg) { g_err = msg; }  // vge_error.h
 }  // namespace vge
+
+// ------------------------------------------------------------------ vge_encoder_create: its parts
+namespace {
+
+// The A/B switches of the encoder, read from the environment once per vge_encoder_create.
+struct EncEnv {
+  bool x3s;         // VGE_X3S: VGE_F32X3 on the staggered conv kernel (default; 0: off)
+  bool f16_x3s;     // VGE_F16_X3S: VGE_F16 on the staggered conv kernel where the stem is unsplit (default; 0: off)
+  int f16_mix;      // VGE_F16_MIX: VGE_F16 stages kept in 3xfp16 (bit 0 stem, bit 1 transformer; default 2)
+  int f16w;         // VGE_F16W: windows per unit of the unit-table conv kernel (default 6; 0: the quad / pair kernel)
+  bool x3_unfused;  // VGE_X3_UNFUSED=1: VGE_F32X3 on the per-layer transformer kernels
+  bool host_pack;   // VGE_HOST_PACK=1: the fp16 image packed on host threads (A/B check of the device packing)
+};
+
+EncEnv read_enc_env() {
+  auto is = [](const char* name, char c) {
+    const char* v = getenv(name);
+    return v && v[0] == c;
+  };
+  auto num = [](const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v ? atoi(v) : dflt;
+  };
+  return EncEnv{!is("VGE_X3S", '0'), !is("VGE_F16_X3S", '0'), num("VGE_F16_MIX", 2), num("VGE_F16W", 6),
+                is("VGE_X3_UNFUSED", '1'), is("VGE_HOST_PACK", '1')};
+}
+
+// Weight lookup by state_dict name with a shape check; `err` keeps the first failure.
+struct Weights {
+  std::unordered_map<std::string, const vge_tensor_view*> wm;
+  std::string err;
+
+  Weights(const vge_tensor_view* weights, int n_weights) {
+    for (int i = 0; i < n_weights; ++i)
+      if (weights[i].name) wm[weights[i].name] = &weights[i];
+  }
+  const float* get(const std::string& k, std::initializer_list<int64_t> shape) {
+    auto it = wm.find(k);
+    if (it == wm.end()) {
+      if (err.empty()) err = "missing weight: " + k;
+      return nullptr;
+    }
+    const vge_tensor_view* t = it->second;
+    int i = 0;
+    bool ok = t->ndim == (int)shape.size() && t->data != nullptr;
+    for (int64_t sh : shape) ok = ok && i < t->ndim && t->shape[i++] == sh;
+    if (!ok && err.empty()) err = "bad shape for weight: " + k;
+    return ok ? t->data : nullptr;
+  }
+  // pos_enc.pe [1][max_len][d]: any max_len that covers the 33 tokens
+  const float* get_pe(int d) {
+    auto it = wm.find("pos_enc.pe");
+    if (it == wm.end()) {
+      if (err.empty()) err = "missing weight: pos_enc.pe";
+      return nullptr;
+    }
+    const vge_tensor_view* t = it->second;
+    if (t->ndim == 3 && t->shape[0] == 1 && t->shape[1] >= 33 && t->shape[2] == d && t->data) return t->data;
+    if (err.empty()) err = "bad shape for weight: pos_enc.pe";
+    return nullptr;
+  }
+  bool ok() const { return err.empty(); }
+  int bail() const { return fail(err.rfind("missing", 0) == 0 ? VGE_ERR_MISSING_WEIGHT : VGE_ERR_WEIGHT_SHAPE, err); }
+};
+
+// The fusion's and the token assembly's weights (model.py:61-98, 184-188) at d_model d.
+struct FusionW {
+  const float *latent, *qw, *qb, *kvw, *kvb, *Wq, *Wk, *Wv, *Wo, *ltemp, *lbias, *cls, *pe;
+};
+
+FusionW get_fusion(Weights& w, int d, int M) {
+  FusionW f;
+  f.latent = w.get("fusion.latent", {1, 1, d});
+  f.qw = w.get("fusion.q_ln.weight", {d});
+  f.qb = w.get("fusion.q_ln.bias", {d});
+  f.kvw = w.get("fusion.kv_ln.weight", {d});
+  f.kvb = w.get("fusion.kv_ln.bias", {d});
+  f.Wq = w.get("fusion.Wq.weight", {d, d});
+  f.Wk = w.get("fusion.Wk.weight", {d, d});
+  f.Wv = w.get("fusion.Wv.weight", {d, d});
+  f.Wo = w.get("fusion.Wo.weight", {d, d});
+  f.ltemp = w.get("fusion.logit_temp", {M});
+  f.lbias = w.get("fusion.logit_bias", {M});
+  f.cls = w.get("cls", {1, 1, d});
+  f.pe = w.get_pe(d);
+  return f;
+}
+
+// fusion fold (double): q = q_ln(latent), u = Wk^T Wq q; Wov = Wo Wv (model.py:79-98)
+void fold_fusion(int d, const FusionW& f, std::vector<float>& u, std::vector<float>& wov) {
+  std::vector<double> q(d), Q(d);
+  double mu = 0, var = 0;
+  for (int i = 0; i < d; ++i) mu += f.latent[i];
+  mu /= d;
+  for (int i = 0; i < d; ++i) var += (f.latent[i] - mu) * (f.latent[i] - mu);
+  var /= d;
+  const double rstd = 1.0 / std::sqrt(var + 1e-5);
+  for (int i = 0; i < d; ++i) q[i] = (f.latent[i] - mu) * rstd * f.qw[i] + f.qb[i];
+  for (int j = 0; j < d; ++j) {
+    double a = 0;
+    for (int i = 0; i < d; ++i) a += q[i] * f.Wq[(size_t)j * d + i];
+    Q[j] = a;
+  }
+  u.resize(d);
+  for (int i = 0; i < d; ++i) {
+    double a = 0;
+    for (int j = 0; j < d; ++j) a += Q[j] * f.Wk[(size_t)j * d + i];
+    u[i] = (float)a;
+  }
+  wov.resize((size_t)d * d);
+  parallel_for(d, [&](int i) {
+    for (int j = 0; j < d; ++j) {
+      double a = 0;
+      for (int k = 0; k < d; ++k) a += (double)f.Wo[(size_t)i * d + k] * f.Wv[(size_t)k * d + j];
+      wov[(size_t)i * d + j] = (float)a;
+    }
+  });
+}
+
+// per-modality logit scale and bias of the fusion's softmax (FuseParams / GenFuse)
+template <class Fuse>
+void fill_modalities(Fuse& fp, int M, const FusionW& f) {
+  fp.n_mod = M;
+  for (int m = 0; m < M; ++m) {
+    const float x = f.ltemp[m];
+    const float sp = x > 20.0f ? x : log1pf(expf(x));  // F.softplus (beta 1, threshold 20)
+    fp.inv_tau[m] = 1.0f / (sp + 1e-3f);
+    fp.bias[m] = f.lbias[m];
+    fp.has_motion[m] = 1;
+  }
+}
+
+int hip_fail(vge_encoder* enc, hipError_t he) {
+  vge_encoder_destroy(enc);
+  return fail(VGE_ERR_HIP, std::string("vge_encoder_create: ") + hipGetErrorString(he));
+}
+
+// ---- the generic-shape exact-f32 model: reference weights uploaded as they are (+ the fusion fold)
+struct GenStage {
+  std::vector<float> hw;                                  // host image
+  std::vector<std::pair<const float**, size_t>> fix;      // device pointers resolved after the upload
+  void put(const float* src, size_t n, const float** dst) {
+    fix.push_back({dst, hw.size()});
+    hw.insert(hw.end(), src, src + n);
+    hw.resize((hw.size() + 63) / 64 * 64, 0.f);
+  }
+};
+
+void gen_stage_encoders(Weights& w, GenStage& st, GenModel& gm) {
+  const int d = gm.d, M = gm.M;
+  gm.encs.resize(2 * M);
+  int col_raw = 0, col_diff = M == 5 ? VGE_RAW_DIM : VGE_RAW_DIM_NOKP;
+  for (int kind = 0; kind < 2; ++kind)
+    for (int m = 0; m < M; ++m) {
+      GenModel::Enc& E = gm.encs[kind * M + m];
+      const std::string pre = std::string(kind == 0 ? "state_enc." : "motion_enc.") + kMods[m];
+      const int d_in = kind == 0 ? kDimsRaw[m] : kDimsDiff[m];
+      E.d_in = d_in;
+      E.in_col = kind == 0 ? col_raw : col_diff;
+      if (kind == 0) col_raw += d_in; else col_diff += d_in;
+      const float* stem = w.get(pre + ".stem.weight", {d, d_in, 1});
+      if (stem) st.put(stem, (size_t)d * d_in, &E.stem);
+      for (int b = 0; b < 4; ++b) {
+        const std::string blk = pre + ".blocks." + std::to_string(b);
+        for (int cv = 0; cv < 2; ++cv) {
+          const float* cw = w.get(blk + ".conv" + std::to_string(cv + 1) + ".weight", {d, d, 5});
+          if (cw) st.put(cw, (size_t)d * d * 5, &E.conv[b * 2 + cv]);
+        }
+        const float* g = w.get(blk + ".norm.weight", {d});
+        const float* be = w.get(blk + ".norm.bias", {d});
+        if (g && be) {
+          st.put(g, d, &E.gw[b]);
+          st.put(be, d, &E.gb[b]);
+        }
+      }
+      const float* pj = w.get(pre + ".proj.weight", {d, d});
+      if (pj) st.put(pj, (size_t)d * d, &E.proj);
+    }
+}
+
+int create_generic(const vge_dims* dims, Weights& w, vge_encoder** out) {
+  const int d = dims->d_model, M = dims->n_modalities, L = dims->time_layers;
+  const int ffn = 4 * d;  // model.py:145: dim_feedforward = 4 * d_model
+  GenStage st;
+  std::unique_ptr<GenModel> gm(new GenModel());
+  gm->d = d; gm->heads = dims->time_heads; gm->layers = L; gm->ffn = ffn; gm->M = M;
+  gen_stage_encoders(w, st, *gm);
+  const FusionW f = get_fusion(w, d, M);
+  std::vector<const float*> lw;
+  for (int l = 0; l < L; ++l) {
+    const std::string p = "temporal.layers." + std::to_string(l);
+    lw.push_back(w.get(p + ".self_attn.in_proj_weight", {3 * d, d}));
+    lw.push_back(w.get(p + ".self_attn.in_proj_bias", {3 * d}));
+    lw.push_back(w.get(p + ".self_attn.out_proj.weight", {d, d}));
+    lw.push_back(w.get(p + ".self_attn.out_proj.bias", {d}));
+    lw.push_back(w.get(p + ".norm1.weight", {d}));
+    lw.push_back(w.get(p + ".norm1.bias", {d}));
+    lw.push_back(w.get(p + ".linear1.weight", {ffn, d}));
+    lw.push_back(w.get(p + ".linear1.bias", {ffn}));
+    lw.push_back(w.get(p + ".linear2.weight", {d, ffn}));
+    lw.push_back(w.get(p + ".linear2.bias", {d}));
+    lw.push_back(w.get(p + ".norm2.weight", {d}));
+    lw.push_back(w.get(p + ".norm2.bias", {d}));
+  }
+  if (!w.ok()) return w.bail();
+  std::vector<float> u, wov;
+  fold_fusion(d, f, u, wov);
+  st.put(u.data(), d, &gm->fuse.u);
+  st.put(f.kvw, d, &gm->fuse.kv_w);
+  st.put(f.kvb, d, &gm->fuse.kv_b);
+  st.put(wov.data(), (size_t)d * d, &gm->Wov);
+  st.put(f.cls, d, &gm->cls);
+  st.put(f.pe, (size_t)33 * d, &gm->pe);
+  fill_modalities(gm->fuse, M, f);
+  gm->fuse.d = d;
+  gm->L.resize(L);
+  for (int l = 0; l < L; ++l) {
+    GenModel::Lyr& Y = gm->L[l];
+    const float* const* p = lw.data() + 12 * l;
+    st.put(p[0], (size_t)3 * d * d, &Y.in_w);
+    st.put(p[1], (size_t)3 * d, &Y.in_b);
+    st.put(p[2], (size_t)d * d, &Y.out_w);
+    st.put(p[3], d, &Y.out_b);
+    st.put(p[4], d, &Y.n1w);
+    st.put(p[5], d, &Y.n1b);
+    st.put(p[6], (size_t)ffn * d, &Y.l1w);
+    st.put(p[7], ffn, &Y.l1b);
+    st.put(p[8], (size_t)d * ffn, &Y.l2w);
+    st.put(p[9], d, &Y.l2b);
+    st.put(p[10], d, &Y.n2w);
+    st.put(p[11], d, &Y.n2b);
+  }
+  hipError_t he = hipMalloc(&gm->wbuf, st.hw.size() * sizeof(float));
+  if (he == hipSuccess) he = hipMemcpy(gm->wbuf, st.hw.data(), st.hw.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (he != hipSuccess) return fail(VGE_ERR_HIP, std::string("vge_encoder_create: ") + hipGetErrorString(he));
+  for (auto& x : st.fix) *x.first = gm->wbuf + x.second;
+  vge_encoder* enc = new vge_encoder();
+  enc->gen = gm.release();
+  enc->mode = VGE_F32;
+  enc->n_mod = M;
+  enc->n_enc = 2 * M;
+  enc->feat_dim = M == 5 ? VGE_FEAT_DIM : VGE_FEAT_DIM_NOKP;
+  enc->n_layers = L;
+  he = hipEventCreateWithFlags(&enc->conv_done, hipEventDisableTiming);
+  if (he == hipSuccess) he = hipEventCreateWithFlags(&enc->fuse_done, hipEventDisableTiming);
+  if (he == hipSuccess) he = hipEventCreateWithFlags(&enc->tail_done, hipEventDisableTiming);
+  if (he != hipSuccess) return hip_fail(enc, he);
+  *out = enc;
+  return VGE_OK;
+}
+
+// ---- the 256 x 8 model: the host image of its weights
+struct Mat { size_t off, cs; };  // packed matrix (pk or fp16 image offset); x3: column scales at pk[cs]
+// x3: the fp16 hi/lo image is packed on the device after the upload (launch_pack_x3, one job per matrix; the column
+// scales land in pk's placeholders); VGE_HOST_PACK=1 packs it on host threads instead (A/B check)
+struct PackJob { const float* W; int N, K_real, ldk, conv, nch; size_t off, cs; };
+
+struct HostImage {
+  bool x3 = false;            // matrices go to the fp16 image (3xfp16 / fp16 modes), else packed into pk
+  std::vector<float> pk;      // f32 device image
+  std::vector<PackJob> jobs;
+  size_t ph_n = 0;            // fp16 image size (elements)
+  std::vector<std::vector<float>> copies;  // folded / permuted weight copies, alive until packed
+
+  size_t put(const float* src, size_t n) {
+    const size_t o = pk.size();
+    pk.insert(pk.end(), src, src + n);
+    return o;
+  }
+  Mat add_job(const float* W, int N, int K_real, int ldk, int conv, int chunk_mult) {
+    const int nch = ((K_real + 15) / 16 + chunk_mult - 1) / chunk_mult * chunk_mult;
+    const Mat m{ph_n, pk.size()};
+    jobs.push_back(PackJob{W, N, K_real, ldk, conv, nch, ph_n, pk.size()});
+    pk.resize(pk.size() + N, 0.f);
+    ph_n += (size_t)(N / 256) * nch * 8192;
+    return m;
+  }
+  Mat pack_lin(const float* W, int N, int K_real, int ldk, int P) {
+    // the x3 kernels stream weights in groups of 8 chunks (zero chunks pad a short last panel)
+    if (x3) return add_job(W, N, K_real, ldk, 0, 8);
+    const size_t o = pk.size();
+    pack_linear(W, N, K_real, ldk, P, pk);
+    return {o, 0};
+  }
+  Mat pack_cv(const float* W) {
+    if (x3) return add_job(W, 256, 5 * 256, 0, 1, 1);  // K index = tap * 256 + ci (tap-major panels)
+    const size_t o = pk.size();
+    pack_conv(W, pk);
+    return {o, 0};
+  }
+};
+
+struct EncOff { Mat stem, conv, proj; size_t gnw, gnb, fold; int in_col, d_in, P; };
+struct FusionOff { size_t u, kvw, kvb, cls, pe; Mat wov; };
+struct LayerOff { Mat in_w, out_w, l1_w, l2_w; size_t in_b, out_b, l1_b, l2_b, n1_w, n1_b, n2_w, n2_b; int e_x1, e_x2, e_h; };
+
+// The staggered conv kernel (vge_encoder_x3s.hip) runs on GroupNorm-folded weights: each block's GroupNorm is folded
+// into the next GEMM -- conv1 of blocks 1..3 and proj packed as W diag(gamma) -- plus the per-row corrections (sums of
+// W gamma and W beta over the taps that fall inside the window; double, then f32).  Replaces cw[2], cw[4], cw[6] and
+// projw by the folded copies and returns the corrections' offset in pk.
+size_t fold_groupnorms(HostImage& im, const float* const gw[4], const float* const gb[4], const float* cw[8],
+                       const float*& projw) {
+  std::vector<float>& pk = im.pk;
+  pk.resize((pk.size() + 63) / 64 * 64, 0.f);  // 256-B aligned: the kernel reads 16-B vectors
+  const size_t fold = pk.size();
+  pk.resize(pk.size() + 3 * 256 * 16 + 512, 0.f);
+  const float* proj = projw;
+  for (int b = 1; b <= 4; ++b) {  // GroupNorm b-1 folded into block b's conv1 (b < 4) or the proj (b == 4)
+    const float* g = gw[b - 1];
+    const float* be = gb[b - 1];
+    const float* src = b < 4 ? cw[2 * b] : proj;
+    const int ntap = b < 4 ? 5 : 1;
+    im.copies.emplace_back((size_t)256 * 256 * ntap);
+    float* f = im.copies.back().data();
+    for (size_t q = 0; q < im.copies.back().size(); ++q) f[q] = src[q] * g[(q / ntap) & 255];
+    parallel_for(256, [&](int n) {
+      double sg[5] = {0, 0, 0, 0, 0}, sb[5] = {0, 0, 0, 0, 0};
+      for (int ci = 0; ci < 256; ++ci)
+        for (int tap = 0; tap < ntap; ++tap) {
+          const size_t q = ((size_t)n * 256 + ci) * ntap + tap;
+          sg[tap] += f[q];
+          sb[tap] += (double)src[q] * be[ci];
+        }
+      if (b == 4) {
+        pk[fold + 3 * 256 * 16 + n * 2] = (float)sg[0];
+        pk[fold + 3 * 256 * 16 + n * 2 + 1] = (float)sb[0];
+        return;
+      }
+      // per-tap sums: the kernel adds the taps that fall inside the window for each of its rows
+      for (int tap = 0; tap < 5; ++tap) {
+        pk[fold + ((size_t)(b - 1) * 256 + n) * 16 + tap] = (float)sg[tap];
+        pk[fold + ((size_t)(b - 1) * 256 + n) * 16 + 8 + tap] = (float)sb[tap];
+      }
+    });
+    if (b < 4) cw[2 * b] = f;
+    else projw = f;
+  }
+  return fold;
+}
+
+// conv encoders (state then motion, modality order), with the GroupNorm fold where the staggered kernel runs (x3s)
+bool pack_conv_encoders(Weights& w, HostImage& im, int M, bool x3s, std::vector<EncOff>& eoff) {
+  eoff.resize(2 * M);
+  int col_raw = 0, col_diff = M == 5 ? VGE_RAW_DIM : VGE_RAW_DIM_NOKP;
+  for (int kind = 0; kind < 2; ++kind) {
+    for (int m = 0; m < M; ++m) {
+      const std::string pre = std::string(kind == 0 ? "state_enc." : "motion_enc.") + kMods[m];
+      const int d_in = kind == 0 ? kDimsRaw[m] : kDimsDiff[m];
+      EncOff& o = eoff[kind * M + m];
+      o.d_in = d_in;
+      o.P = (d_in + 255) / 256;
+      o.in_col = kind == 0 ? col_raw : col_diff;
+      if (kind == 0) col_raw += d_in; else col_diff += d_in;
+      const float* stem = w.get(pre + ".stem.weight", {256, d_in, 1});
+      const float* cw[8];
+      for (int b = 0; b < 4; ++b)
+        for (int cv = 0; cv < 2; ++cv)
+          cw[b * 2 + cv] = w.get(pre + ".blocks." + std::to_string(b) + ".conv" + std::to_string(cv + 1) + ".weight", {256, 256, 5});
+      const float* projw = w.get(pre + ".proj.weight", {256, 256});
+      const float *gw[4], *gb[4];
+      for (int b = 0; b < 4; ++b) {
+        gw[b] = w.get(pre + ".blocks." + std::to_string(b) + ".norm.weight", {256});
+        gb[b] = w.get(pre + ".blocks." + std::to_string(b) + ".norm.bias", {256});
+      }
+      if (!w.ok()) return false;
+      o.fold = x3s ? fold_groupnorms(im, gw, gb, cw, projw) : 0;
+      o.stem = im.pack_lin(stem, 256, d_in, d_in, o.P);
+      o.conv = im.pack_cv(cw[0]);
+      for (int c = 1; c < 8; ++c) im.pack_cv(cw[c]);
+      o.proj = im.pack_lin(projw, 256, 256, 256, 1);
+      o.gnw = im.pk.size();
+      for (int b = 0; b < 4; ++b) im.put(gw[b], 256);
+      o.gnb = im.pk.size();
+      for (int b = 0; b < 4; ++b) im.put(gb[b], 256);
+    }
+  }
+  return true;
+}
+
+// fusion: fold the constant query  u = Wk^T (Wq q_ln(latent)),  Wov = Wo Wv
+FusionOff pack_fusion(HostImage& im, const FusionW& f) {
+  std::vector<float> u, wov;
+  fold_fusion(256, f, u, wov);
+  FusionOff o;
+  o.u = im.put(u.data(), 256);
+  o.kvw = im.put(f.kvw, 256);
+  o.kvb = im.put(f.kvb, 256);
+  im.copies.push_back(std::move(wov));  // x3: packed after the upload
+  o.wov = im.pack_lin(im.copies.back().data(), 256, 256, 256, 1);
+  o.cls = im.put(f.cls, 256);
+  o.pe = im.put(f.pe, 33 * 256);
+  return o;
+}
+
+// the fused transformer (vge_transformer_x3.hip) reads in_proj's outputs in head order: output block j, wave w, tile t
+// <- the original block (q | k | v) and head half of kInPerm[j][t], rows 64 w + 32 half .. + 31; the per-layer kernels
+// of the unfused path keep q | k | v
+int in_perm_row(int nr) {
+  static const int kInPerm[3][2][2] = {{{0, 0}, {1, 0}}, {{2, 0}, {0, 1}}, {{1, 1}, {2, 1}}};  // {block, half}
+  const int j = nr >> 8, c = nr & 255, w = c >> 6, t = (c >> 5) & 1, i = c & 31;
+  return kInPerm[j][t][0] * 256 + 64 * w + 32 * kInPerm[j][t][1] + i;
+}
+
+// static operand scales of the fused x3 transformer (vge_transformer_x3.hip): a LayerNorm output is bounded by
+// 16 max|gamma| + max|beta| (sum_j z_j^2 <= 256), ReLU(X1 W1^T + b1) by max_n sum_k |W1[n][k]| * that + |b1[n]|
+void layer_range_exps(const float* n1w, const float* n1b, const float* n2w, const float* n2b, const float* l1w,
+                      const float* l1b, LayerOff& o) {
+  auto ln_bound = [](const float* g, const float* b) {
+    double mg = 0.0, mb = 0.0;
+    for (int j = 0; j < 256; ++j) {
+      mg = std::max(mg, (double)std::fabs(g[j]));
+      mb = std::max(mb, (double)std::fabs(b[j]));
+    }
+    return 16.0 * mg + mb;
+  };
+  const double b1 = ln_bound(n1w, n1b), b2 = ln_bound(n2w, n2b);
+  double bh = 0.0;
+  for (int n = 0; n < 1024; ++n) {
+    double a = 0.0;
+    for (int k = 0; k < 256; ++k) a += std::fabs((double)l1w[(size_t)n * 256 + k]);
+    bh = std::max(bh, a * b1 + std::fabs((double)l1b[n]));
+  }
+  o.e_x1 = range_exp(b1);
+  o.e_x2 = range_exp(b2);
+  o.e_h = range_exp(bh);
+}
+
+// transformer layers; tx_fused: in_proj permuted for the fused kernel
+bool pack_layers(Weights& w, HostImage& im, int L, bool tx_fused, std::vector<LayerOff>& loff) {
+  loff.resize(L);
+  for (int l = 0; l < L; ++l) {
+    const std::string p = "temporal.layers." + std::to_string(l);
+    const float* inw = w.get(p + ".self_attn.in_proj_weight", {768, 256});
+    const float* inb = w.get(p + ".self_attn.in_proj_bias", {768});
+    const float* ow = w.get(p + ".self_attn.out_proj.weight", {256, 256});
+    const float* ob = w.get(p + ".self_attn.out_proj.bias", {256});
+    const float* l1w = w.get(p + ".linear1.weight", {1024, 256});
+    const float* l1b = w.get(p + ".linear1.bias", {1024});
+    const float* l2w = w.get(p + ".linear2.weight", {256, 1024});
+    const float* l2b = w.get(p + ".linear2.bias", {256});
+    const float* n1w = w.get(p + ".norm1.weight", {256});
+    const float* n1b = w.get(p + ".norm1.bias", {256});
+    const float* n2w = w.get(p + ".norm2.weight", {256});
+    const float* n2b = w.get(p + ".norm2.bias", {256});
+    if (!w.ok()) return false;
+    LayerOff& o = loff[l];
+    if (tx_fused) {
+      im.copies.emplace_back((size_t)768 * 257);
+      float* pw = im.copies.back().data();
+      for (int nr = 0; nr < 768; ++nr) {
+        std::copy(inw + (size_t)in_perm_row(nr) * 256, inw + (size_t)in_perm_row(nr) * 256 + 256, pw + (size_t)nr * 256);
+        pw[768 * 256 + nr] = inb[in_perm_row(nr)];
+      }
+      inw = pw;
+      inb = pw + 768 * 256;
+    }
+    o.in_w = im.pack_lin(inw, 768, 256, 256, 1);
+    o.out_w = im.pack_lin(ow, 256, 256, 256, 1);
+    o.l1_w = im.pack_lin(l1w, 1024, 256, 256, 1);
+    o.l2_w = im.pack_lin(l2w, 256, 1024, 1024, 4);
+    o.in_b = im.put(inb, 768);
+    o.out_b = im.put(ob, 256);
+    o.l1_b = im.put(l1b, 1024);
+    o.l2_b = im.put(l2b, 256);
+    o.n1_w = im.put(n1w, 256);
+    o.n1_b = im.put(n1b, 256);
+    o.n2_w = im.put(n2w, 256);
+    o.n2_b = im.put(n2b, 256);
+    layer_range_exps(n1w, n1b, n2w, n2b, l1w, l1b, o);
+  }
+  return true;
+}
+
+const char* const kNonFinite = "vge_encoder_create: non-finite weight, not representable by the 3xfp16 split; use VGE_F32";
+
+// VGE_HOST_PACK=1: the fp16 image and its column scales (into pk's placeholders) on host threads; false if a weight
+// is not finite (column scaling keeps every finite weight in the fp16 planes' range; a non-finite one cannot be split)
+bool host_pack_x3(HostImage& im, std::vector<_Float16>& ph) {
+  for (const PackJob& j : im.jobs) {
+    std::vector<float> cs;
+    const float* W = j.W;
+    const int ldk = j.ldk;
+    if (j.conv)
+      pack_linear_x3([&](int n, int k) { return W[((size_t)n * 256 + (k & 255)) * 5 + (k >> 8)]; }, j.N, j.K_real, ph,
+                     cs, 1);
+    else
+      pack_linear_x3([&](int n, int k) { return W[(size_t)n * ldk + k]; }, j.N, j.K_real, ph, cs, 8);
+    std::copy(cs.begin(), cs.end(), im.pk.begin() + j.cs);
+  }
+  for (const _Float16 v : ph)
+    if (!std::isfinite((float)v)) return false;
+  return true;
+}
+
+// raw f32 weights staged in HBM (one buffer), then packed by launch_pack_x3 straight into hbuf / wbuf; bad: a weight
+// was not finite
+hipError_t device_pack_x3(vge_encoder* enc, const std::vector<PackJob>& jobs, int& bad) {
+  size_t raw = 0, ncol = 0;
+  std::vector<size_t> roff(jobs.size());
+  for (size_t i = 0; i < jobs.size(); ++i) {
+    roff[i] = raw;
+    raw += (size_t)jobs[i].N * (jobs[i].conv ? 1280 : jobs[i].ldk);
+    ncol = std::max(ncol, (size_t)jobs[i].N);
+  }
+  float* d_raw = nullptr;
+  int* d_sh = nullptr;  // [jobs][ncol] column exponents, then the non-finite flag
+  hipError_t he = hipMalloc(&d_raw, raw * sizeof(float));
+  if (he == hipSuccess) he = hipMalloc(&d_sh, (jobs.size() * ncol + 1) * sizeof(int));
+  if (he == hipSuccess) he = hipMemset(d_sh + jobs.size() * ncol, 0, sizeof(int));
+  for (size_t i = 0; i < jobs.size() && he == hipSuccess; ++i) {
+    const PackJob& j = jobs[i];
+    he = hipMemcpyAsync(d_raw + roff[i], j.W, (size_t)j.N * (j.conv ? 1280 : j.ldk) * sizeof(float),
+                        hipMemcpyHostToDevice, nullptr);
+    if (he == hipSuccess)
+      he = vge::launch_pack_x3(d_raw + roff[i], j.N, j.K_real, j.ldk, j.conv, j.nch, d_sh + i * ncol, enc->wbuf + j.cs,
+                               d_sh + jobs.size() * ncol, enc->hbuf + j.off, nullptr);
+  }
+  bad = 0;
+  if (he == hipSuccess) he = hipMemcpy(&bad, d_sh + jobs.size() * ncol, sizeof(int), hipMemcpyDeviceToHost);
+  if (d_raw) (void)hipFree(d_raw);
+  if (d_sh) (void)hipFree(d_sh);
+  return he;
+}
+
+// upload and device packing: wbuf (f32 image), hbuf (x3: the fp16 image).  Destroys enc on failure.
+int upload_image(vge_encoder* enc, HostImage& im, bool host_pack) {
+  std::vector<_Float16> ph;
+  if (host_pack && !host_pack_x3(im, ph)) {
+    vge_encoder_destroy(enc);
+    return fail(VGE_ERR_ARG, kNonFinite);
+  }
+  hipError_t he = im.x3 ? vge::encoder_x3_kernel_setup() : vge::encoder_kernel_setup();
+  if (he == hipSuccess && enc->x3s) he = vge::encoder_x3s_kernel_setup();
+  if (he == hipSuccess) he = hipMalloc(&enc->wbuf, im.pk.size() * sizeof(float));
+  if (he == hipSuccess) he = hipMemcpy(enc->wbuf, im.pk.data(), im.pk.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (he == hipSuccess && im.x3) he = hipMalloc(&enc->hbuf, im.ph_n * sizeof(_Float16));
+  if (he == hipSuccess && host_pack) he = hipMemcpy(enc->hbuf, ph.data(), im.ph_n * sizeof(_Float16), hipMemcpyHostToDevice);
+  if (he != hipSuccess) return hip_fail(enc, he);
+  enc->n_half = im.x3 ? im.ph_n : 0;
+  enc->n_f32 = im.pk.size();
+  if (im.x3 && !host_pack) {
+    int bad = 0;
+    he = device_pack_x3(enc, im.jobs, bad);
+    if (he != hipSuccess) return hip_fail(enc, he);
+    if (bad) {
+      vge_encoder_destroy(enc);
+      return fail(VGE_ERR_ARG, kNonFinite);
+    }
+  }
+  return VGE_OK;
+}
+
+// descriptor tables of the conv encoders (device) into enc->d_encs / d_encs_x3
+hipError_t upload_enc_descs(vge_encoder* enc, const HostImage& im, const std::vector<EncOff>& eoff) {
+  float* wb = enc->wbuf;
+  _Float16* hb = enc->hbuf;
+  const int n_enc = enc->n_enc;
+  if (!im.x3) {
+    std::vector<vge::EncDesc> descs(n_enc);
+    for (int e = 0; e < n_enc; ++e)
+      descs[e] = vge::EncDesc{wb + eoff[e].stem.off, wb + eoff[e].conv.off, wb + eoff[e].proj.off, wb + eoff[e].gnw,
+                              wb + eoff[e].gnb, eoff[e].in_col, eoff[e].d_in, eoff[e].P, enc->feat_dim};
+    hipError_t he = hipMalloc(&enc->d_encs, sizeof(vge::EncDesc) * n_enc);
+    if (he == hipSuccess) he = hipMemcpy(enc->d_encs, descs.data(), sizeof(vge::EncDesc) * n_enc, hipMemcpyHostToDevice);
+    return he;
+  }
+  std::vector<vge::EncDescX3> descs(n_enc);
+  for (int e = 0; e < n_enc; ++e) {
+    descs[e] = vge::EncDescX3{hb + eoff[e].stem.off, hb + eoff[e].conv.off, hb + eoff[e].proj.off,
+                              wb + eoff[e].gnw, wb + eoff[e].gnb, wb + eoff[e].stem.cs,  // [10][256] scales
+                              enc->x3s ? wb + eoff[e].fold : nullptr, eoff[e].in_col, eoff[e].d_in, eoff[e].P,
+                              enc->feat_dim, {}, {}};
+    for (int b = 0; b < 4; ++b) {
+      float gm = 0.f, bm = 0.f;
+      for (int c = 0; c < 256; ++c) {
+        gm = std::max(gm, std::fabs(im.pk[eoff[e].gnw + b * 256 + c]));
+        bm = std::max(bm, std::fabs(im.pk[eoff[e].gnb + b * 256 + c]));
+      }
+      descs[e].gn_gmax[b] = gm;
+      descs[e].gn_bmax[b] = bm;
+    }
+    if (eoff[e].P > 1) enc->stem_heavy |= 1u << e;
+  }
+  hipError_t he = hipMalloc(&enc->d_encs_x3, sizeof(vge::EncDescX3) * n_enc);
+  if (he == hipSuccess)
+    he = hipMemcpy(enc->d_encs_x3, descs.data(), sizeof(vge::EncDescX3) * n_enc, hipMemcpyHostToDevice);
+  return he;
+}
+
+// device pointers of the fusion, the token assembly and the transformer layers (and the fused kernel's arguments)
+void set_tail_tables(vge_encoder* enc, bool x3, const FusionOff& fo, const std::vector<LayerOff>& loff) {
+  float* wb = enc->wbuf;
+  _Float16* hb = enc->hbuf;
+  auto mat = [&](const Mat& m) -> const void* { return x3 ? (const void*)(hb + m.off) : (const void*)(wb + m.off); };
+  auto csp = [&](const Mat& m) -> const float* { return x3 ? wb + m.cs : nullptr; };
+  enc->fuse.kv_w = wb + fo.kvw;
+  enc->fuse.kv_b = wb + fo.kvb;
+  enc->fuse.u = wb + fo.u;
+  enc->Wov = mat(fo.wov);
+  enc->Wov_cs = csp(fo.wov);
+  enc->cls = wb + fo.cls;
+  enc->pe = wb + fo.pe;
+  const int L = (int)loff.size();
+  enc->layers.resize(L);
+  for (int l = 0; l < L; ++l) {
+    const LayerOff& o = loff[l];
+    enc->layers[l] = vge_encoder::Layer{mat(o.in_w), mat(o.out_w), mat(o.l1_w), mat(o.l2_w), wb + o.in_b, wb + o.out_b,
+                                        wb + o.l1_b, wb + o.l2_b, wb + o.n1_w, wb + o.n1_b, wb + o.n2_w, wb + o.n2_b,
+                                        csp(o.in_w), csp(o.out_w), csp(o.l1_w), csp(o.l2_w), o.e_x1, o.e_x2, o.e_h};
+  }
+  if (!x3 || L > vge::TX_MAX_LAYERS) return;  // more layers: the per-layer kernels (tx_fused is off)
+  vge::TxArgsX3& t = enc->tx;
+  t.n_layers = L;
+  t.ov_w = (const _Float16*)enc->Wov;
+  t.ov_cs = enc->Wov_cs;
+  t.cls = enc->cls;
+  t.pe = enc->pe;
+  for (int l = 0; l < L; ++l) {
+    const vge_encoder::Layer& y = enc->layers[l];
+    t.layers[l] = vge::TxLayerX3{(const _Float16*)y.in_w, y.in_cs, y.in_b, (const _Float16*)y.out_w, y.out_cs, y.out_b,
+                                 y.n1_w, y.n1_b, (const _Float16*)y.l1_w, y.l1_cs, y.l1_b, (const _Float16*)y.l2_w,
+                                 y.l2_cs, y.l2_b, y.n2_w, y.n2_b, y.e_x1, y.e_x2, y.e_h, 0};
+  }
+}
+
+// the 256 x 8 model on the tiled MFMA kernels (exact f32, 3xfp16 or fp16)
+int create_tiled(const vge_dims* dims, Weights& w, vge_dtype compute, const EncEnv& env, vge_encoder** out) {
+  if (compute == VGE_F16 && dims->time_layers > 8)
+    return fail(VGE_ERR_UNSUPPORTED, "vge_encoder_create: VGE_F16 runs the fused transformer, at most 8 layers");
+  const int M = dims->n_modalities, L = dims->time_layers;
+  // VGE_F16 shares the 3xfp16 weight image (its kernels read the hi planes only)
+  const bool x3 = compute == VGE_F32X3 || compute == VGE_F16;
+  // VGE_F32X3 runs the staggered conv kernel (vge_encoder_x3s.hip) unless VGE_X3S=0; VGE_F16 (with the stem unsplit):
+  // the same staggered kernel in single fp16 (hi planes only) unless VGE_F16_X3S=0 selects conv_encoder_f16w_kernel
+  // (1..6-window units): conv 0.512 -> 0.489 ms at 256 windows, 6.95-6.99 -> 6.58-6.65 ms per 4,096-window chunk
+  // (profiles/ab_r05x_f16_conv.json, ab_r05w_cfg5.json)
+  const bool f16_x3s = compute == VGE_F16 && env.f16_x3s && !(env.f16_mix & 1);
+  const bool x3s = (compute == VGE_F32X3 && env.x3s) || f16_x3s;
+  // the fused transformer: x3 modes, <= 8 layers, unless VGE_X3_UNFUSED=1 (the f16 mode has the fused kernel only)
+  const bool tx_fused = x3 && (!env.x3_unfused || compute == VGE_F16) && L <= 8;
+
+  HostImage im;
+  im.x3 = x3;
+  std::vector<EncOff> eoff;
+  if (!pack_conv_encoders(w, im, M, x3s, eoff)) return w.bail();
+  const FusionW f = get_fusion(w, 256, M);
+  if (!w.ok()) return w.bail();
+  const FusionOff fo = pack_fusion(im, f);
+  std::vector<LayerOff> loff;
+  if (!pack_layers(w, im, L, tx_fused, loff)) return w.bail();
+
+  vge_encoder* enc = new vge_encoder();
+  enc->mode = compute;
+  enc->n_mod = M;
+  enc->n_enc = 2 * M;
+  enc->feat_dim = M == 5 ? VGE_FEAT_DIM : VGE_FEAT_DIM_NOKP;
+  if (compute == VGE_F16) {  // default: the transformer keeps the split (most of the f16 error, ~10% of the FLOPs)
+    enc->f16_mix = env.f16_mix;
+    enc->f16w = env.f16w;
+  }
+  enc->n_layers = L;
+  enc->x3s = x3s;
+  if (const int r = upload_image(enc, im, x3 && env.host_pack)) return r;
+  hipError_t he = upload_enc_descs(enc, im, eoff);
+  if (he != hipSuccess) return hip_fail(enc, he);
+  fill_modalities(enc->fuse, M, f);
+  set_tail_tables(enc, x3, fo, loff);
+  if (x3) {
+    enc->tx_fused = tx_fused;
+    he = vge::transformer_x3_kernel_setup();
+    if (he != hipSuccess) return hip_fail(enc, he);
+  }
+  he = hipEventCreateWithFlags(&enc->conv_done, hipEventDisableTiming);
+  if (he != hipSuccess) return hip_fail(enc, he);
+  he = hipHostMalloc(reinterpret_cast<void**>(&enc->status_h), sizeof(int), hipHostMallocMapped | hipHostMallocCoherent);
+  if (he == hipSuccess) {
+    *enc->status_h = 0;
+    he = hipHostGetDevicePointer(reinterpret_cast<void**>(&enc->status_d), enc->status_h, 0);
+  }
+  if (he != hipSuccess) return hip_fail(enc, he);
+  *out = enc;
+  return VGE_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -425,8 +1017,7 @@ int vge_encoder_create(const vge_dims* dims, const vge_tensor_view* weights, int
   *out = nullptr;
   if (compute != VGE_F32 && compute != VGE_F32X3 && compute != VGE_F16)
     return fail(VGE_ERR_ARG, "vge_encoder_create: unsupported compute dtype");
-  // VGE_F16 shares the 3xfp16 weight image (its kernels read the hi planes only)
-  const bool x3 = compute == VGE_F32X3 || compute == VGE_F16;
+  const EncEnv env = read_enc_env();
   if (dims->time_layers < 1) return fail(VGE_ERR_ARG, "vge_encoder_create: time_layers must be >= 1");
   // 5 modalities (keypoint_dir given) or the keypoint-less 4 (utils.py:496-514; infer_dims_from_stats, eval.py:104-133)
   const int M = dims->n_modalities;
@@ -446,606 +1037,8 @@ int vge_encoder_create(const vge_dims* dims, const vge_tensor_view* weights, int
   for (int m = 0; m < M; ++m)
     if (dims->dims_raw[m] != kDimsRaw[m] || dims->dims_diff[m] != kDimsDiff[m])
       return fail(VGE_ERR_UNSUPPORTED, std::string("vge_encoder_create: unsupported dims for modality ") + kMods[m]);
-
-  std::unordered_map<std::string, const vge_tensor_view*> wm;
-  for (int i = 0; i < n_weights; ++i)
-    if (weights[i].name) wm[weights[i].name] = &weights[i];
-  std::string err;
-  auto get = [&](const std::string& k, std::initializer_list<int64_t> shape) -> const float* {
-    auto it = wm.find(k);
-    if (it == wm.end()) {
-      if (err.empty()) err = "missing weight: " + k;
-      return nullptr;
-    }
-    const vge_tensor_view* t = it->second;
-    int i = 0;
-    bool ok = t->ndim == (int)shape.size() && t->data != nullptr;
-    for (int64_t sh : shape) ok = ok && i < t->ndim && t->shape[i++] == sh;
-    if (!ok && err.empty()) err = "bad shape for weight: " + k;
-    return ok ? t->data : nullptr;
-  };
-  auto bail = [&]() { return fail(err.rfind("missing", 0) == 0 ? VGE_ERR_MISSING_WEIGHT : VGE_ERR_WEIGHT_SHAPE, err); };
-
-  if (generic) {  // ---- the generic-shape exact-f32 model: reference weights uploaded as they are (+ the fusion fold)
-    const int d = Dm, L = dims->time_layers, ffn = 4 * d;   // model.py:145: dim_feedforward = 4 * d_model
-    std::vector<float> hw;
-    std::vector<std::pair<const float**, size_t>> fix;      // device pointers resolved after the upload
-    auto put = [&](const float* src, size_t n, const float** dst) {
-      fix.push_back({dst, hw.size()});
-      hw.insert(hw.end(), src, src + n);
-      hw.resize((hw.size() + 63) / 64 * 64, 0.f);
-    };
-    auto* gm = new GenModel();
-    std::unique_ptr<GenModel> guard(gm);
-    gm->d = d; gm->heads = Hn; gm->layers = L; gm->ffn = ffn; gm->M = M;
-    gm->encs.resize(2 * M);
-    int col_raw = 0, col_diff = M == 5 ? VGE_RAW_DIM : VGE_RAW_DIM_NOKP;
-    for (int kind = 0; kind < 2; ++kind)
-      for (int m = 0; m < M; ++m) {
-        GenModel::Enc& E = gm->encs[kind * M + m];
-        const std::string pre = std::string(kind == 0 ? "state_enc." : "motion_enc.") + kMods[m];
-        const int d_in = kind == 0 ? kDimsRaw[m] : kDimsDiff[m];
-        E.d_in = d_in;
-        E.in_col = kind == 0 ? col_raw : col_diff;
-        if (kind == 0) col_raw += d_in; else col_diff += d_in;
-        const float* st = get(pre + ".stem.weight", {d, d_in, 1});
-        if (st) put(st, (size_t)d * d_in, &E.stem);
-        for (int b = 0; b < 4; ++b) {
-          for (int cv = 0; cv < 2; ++cv) {
-            const float* w = get(pre + ".blocks." + std::to_string(b) + ".conv" + std::to_string(cv + 1) + ".weight",
-                                 {d, d, 5});
-            if (w) put(w, (size_t)d * d * 5, &E.conv[b * 2 + cv]);
-          }
-          const float* g = get(pre + ".blocks." + std::to_string(b) + ".norm.weight", {d});
-          const float* be = get(pre + ".blocks." + std::to_string(b) + ".norm.bias", {d});
-          if (g && be) {
-            put(g, d, &E.gw[b]);
-            put(be, d, &E.gb[b]);
-          }
-        }
-        const float* pj = get(pre + ".proj.weight", {d, d});
-        if (pj) put(pj, (size_t)d * d, &E.proj);
-      }
-    const float* latent = get("fusion.latent", {1, 1, d});
-    const float* qw = get("fusion.q_ln.weight", {d});
-    const float* qb = get("fusion.q_ln.bias", {d});
-    const float* kvw = get("fusion.kv_ln.weight", {d});
-    const float* kvb = get("fusion.kv_ln.bias", {d});
-    const float* Wq = get("fusion.Wq.weight", {d, d});
-    const float* Wk = get("fusion.Wk.weight", {d, d});
-    const float* Wv = get("fusion.Wv.weight", {d, d});
-    const float* Wo = get("fusion.Wo.weight", {d, d});
-    const float* ltemp = get("fusion.logit_temp", {M});
-    const float* lbias = get("fusion.logit_bias", {M});
-    const float* clsw = get("cls", {1, 1, d});
-    const float* pe = nullptr;
-    {
-      auto it = wm.find("pos_enc.pe");
-      if (it == wm.end()) {
-        if (err.empty()) err = "missing weight: pos_enc.pe";
-      } else if (it->second->ndim == 3 && it->second->shape[0] == 1 && it->second->shape[1] >= 33 &&
-                 it->second->shape[2] == d && it->second->data) {
-        pe = it->second->data;
-      } else if (err.empty()) {
-        err = "bad shape for weight: pos_enc.pe";
-      }
-    }
-    std::vector<const float*> lw;
-    for (int l = 0; l < L; ++l) {
-      const std::string p = "temporal.layers." + std::to_string(l);
-      lw.push_back(get(p + ".self_attn.in_proj_weight", {3 * d, d}));
-      lw.push_back(get(p + ".self_attn.in_proj_bias", {3 * d}));
-      lw.push_back(get(p + ".self_attn.out_proj.weight", {d, d}));
-      lw.push_back(get(p + ".self_attn.out_proj.bias", {d}));
-      lw.push_back(get(p + ".norm1.weight", {d}));
-      lw.push_back(get(p + ".norm1.bias", {d}));
-      lw.push_back(get(p + ".linear1.weight", {ffn, d}));
-      lw.push_back(get(p + ".linear1.bias", {ffn}));
-      lw.push_back(get(p + ".linear2.weight", {d, ffn}));
-      lw.push_back(get(p + ".linear2.bias", {d}));
-      lw.push_back(get(p + ".norm2.weight", {d}));
-      lw.push_back(get(p + ".norm2.bias", {d}));
-    }
-    if (!err.empty()) return bail();
-    // fusion fold (double): q = q_ln(latent), u = Wk^T Wq q; Wov = Wo Wv (model.py:79-98)
-    std::vector<double> q(d), Q(d);
-    {
-      double mu = 0, var = 0;
-      for (int i = 0; i < d; ++i) mu += latent[i];
-      mu /= d;
-      for (int i = 0; i < d; ++i) var += (latent[i] - mu) * (latent[i] - mu);
-      var /= d;
-      const double rstd = 1.0 / std::sqrt(var + 1e-5);
-      for (int i = 0; i < d; ++i) q[i] = (latent[i] - mu) * rstd * qw[i] + qb[i];
-      for (int j = 0; j < d; ++j) {
-        double a = 0;
-        for (int i = 0; i < d; ++i) a += q[i] * Wq[(size_t)j * d + i];
-        Q[j] = a;
-      }
-    }
-    std::vector<float> u(d), wov((size_t)d * d);
-    for (int i = 0; i < d; ++i) {
-      double a = 0;
-      for (int j = 0; j < d; ++j) a += Q[j] * Wk[(size_t)j * d + i];
-      u[i] = (float)a;
-    }
-    for (int i = 0; i < d; ++i)
-      for (int j = 0; j < d; ++j) {
-        double a = 0;
-        for (int k = 0; k < d; ++k) a += (double)Wo[(size_t)i * d + k] * Wv[(size_t)k * d + j];
-        wov[(size_t)i * d + j] = (float)a;
-      }
-    put(u.data(), d, &gm->fuse.u);
-    put(kvw, d, &gm->fuse.kv_w);
-    put(kvb, d, &gm->fuse.kv_b);
-    put(wov.data(), (size_t)d * d, &gm->Wov);
-    put(clsw, d, &gm->cls);
-    put(pe, (size_t)33 * d, &gm->pe);
-    gm->fuse.n_mod = M;
-    gm->fuse.d = d;
-    for (int m = 0; m < M; ++m) {
-      const float x = ltemp[m];
-      const float sp = x > 20.0f ? x : log1pf(expf(x));  // F.softplus (beta 1, threshold 20)
-      gm->fuse.inv_tau[m] = 1.0f / (sp + 1e-3f);
-      gm->fuse.bias[m] = lbias[m];
-      gm->fuse.has_motion[m] = 1;
-    }
-    gm->L.resize(L);
-    for (int l = 0; l < L; ++l) {
-      GenModel::Lyr& Y = gm->L[l];
-      const float* const* w = lw.data() + 12 * l;
-      put(w[0], (size_t)3 * d * d, &Y.in_w);
-      put(w[1], (size_t)3 * d, &Y.in_b);
-      put(w[2], (size_t)d * d, &Y.out_w);
-      put(w[3], d, &Y.out_b);
-      put(w[4], d, &Y.n1w);
-      put(w[5], d, &Y.n1b);
-      put(w[6], (size_t)ffn * d, &Y.l1w);
-      put(w[7], ffn, &Y.l1b);
-      put(w[8], (size_t)d * ffn, &Y.l2w);
-      put(w[9], d, &Y.l2b);
-      put(w[10], d, &Y.n2w);
-      put(w[11], d, &Y.n2b);
-    }
-    hipError_t he = hipMalloc(&gm->wbuf, hw.size() * sizeof(float));
-    if (he == hipSuccess) he = hipMemcpy(gm->wbuf, hw.data(), hw.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (he != hipSuccess) return fail(VGE_ERR_HIP, std::string("vge_encoder_create: ") + hipGetErrorString(he));
-    for (auto& f : fix) *f.first = gm->wbuf + f.second;
-    vge_encoder* enc = new vge_encoder();
-    enc->gen = guard.release();
-    enc->mode = VGE_F32;
-    enc->n_mod = M;
-    enc->n_enc = 2 * M;
-    enc->feat_dim = M == 5 ? VGE_FEAT_DIM : VGE_FEAT_DIM_NOKP;
-    enc->n_layers = L;
-    he = hipEventCreateWithFlags(&enc->conv_done, hipEventDisableTiming);
-    if (he == hipSuccess) he = hipEventCreateWithFlags(&enc->fuse_done, hipEventDisableTiming);
-    if (he == hipSuccess) he = hipEventCreateWithFlags(&enc->tail_done, hipEventDisableTiming);
-    if (he != hipSuccess) {
-      vge_encoder_destroy(enc);
-      return fail(VGE_ERR_HIP, std::string("vge_encoder_create: ") + hipGetErrorString(he));
-    }
-    *out = enc;
-    return VGE_OK;
-  }
-
-  if (compute == VGE_F16 && dims->time_layers > 8)
-    return fail(VGE_ERR_UNSUPPORTED, "vge_encoder_create: VGE_F16 runs the fused transformer, at most 8 layers");
-  const int L = dims->time_layers;
-  std::vector<float> pk;      // f32 device image
-  // x3: the fp16 hi/lo image is packed on the device after the upload (launch_pack_x3, one job per matrix; the
-  // column scales land in pk's placeholders); VGE_HOST_PACK=1 packs it on host threads instead (A/B check)
-  struct PackJob { const float* W; int N, K_real, ldk, conv, nch; size_t off, cs; };
-  std::vector<PackJob> jobs;
-  size_t ph_n = 0;
-  // a packed matrix lives in pk (f32 mode) or the fp16 image (x3 mode)
-  struct Mat { size_t off, cs; };  // packed matrix (pk or fp16 image offset); x3: column scales at pk[cs]
-  auto add_job = [&](const float* W, int N, int K_real, int ldk, int conv, int chunk_mult) -> Mat {
-    const int nch = ((K_real + 15) / 16 + chunk_mult - 1) / chunk_mult * chunk_mult;
-    const Mat m{ph_n, pk.size()};
-    jobs.push_back(PackJob{W, N, K_real, ldk, conv, nch, ph_n, pk.size()});
-    pk.resize(pk.size() + N, 0.f);
-    ph_n += (size_t)(N / 256) * nch * 8192;
-    return m;
-  };
-  auto pack_lin = [&](const float* W, int N, int K_real, int ldk, int P) -> Mat {
-    // the x3 kernels stream weights in groups of 8 chunks (zero chunks pad a short last panel)
-    if (x3) return add_job(W, N, K_real, ldk, 0, 8);
-    const size_t o = pk.size();
-    pack_linear(W, N, K_real, ldk, P, pk);
-    return {o, 0};
-  };
-  auto pack_cv = [&](const float* W) -> Mat {
-    if (x3) return add_job(W, 256, 5 * 256, 0, 1, 1);  // K index = tap * 256 + ci (tap-major panels)
-    const size_t o = pk.size();
-    pack_conv(W, pk);
-    return {o, 0};
-  };
-
-  // VGE_F32X3 runs the staggered conv kernel (vge_encoder_x3s.hip) unless VGE_X3S=0: each block's GroupNorm is folded
-  // into the next GEMM -- conv1 of blocks 1..3 and proj packed as W diag(gamma) -- plus the per-row corrections
-  // (sums of W gamma and W beta over the taps that fall inside the window; double, then f32)
-  // VGE_F16 (with the stem unsplit): the same staggered kernel in single fp16 (hi planes only) unless VGE_F16_X3S=0
-  // selects conv_encoder_f16w_kernel (1..6-window units): conv 0.512 -> 0.489 ms at 256 windows, 6.95-6.99 -> 6.58-6.65
-  // ms per 4,096-window chunk (profiles/ab_r05x_f16_conv.json, ab_r05w_cfg5.json)
-  const char* x3s_env = getenv("VGE_X3S");
-  const char* f16s_env = getenv("VGE_F16_X3S");
-  const char* mix_env = getenv("VGE_F16_MIX");
-  const bool f16_x3s = compute == VGE_F16 && !(f16s_env && f16s_env[0] == '0') && !((mix_env ? atoi(mix_env) : 2) & 1);
-  const bool x3s = (compute == VGE_F32X3 && !(x3s_env && x3s_env[0] == '0')) || f16_x3s;
-  std::vector<std::vector<float>> folded;  // folded weight copies, alive until packed
-  struct Off { Mat stem, conv, proj; size_t gnw, gnb, fold; int in_col, d_in, P; };
-  const int n_enc = 2 * M;
-  const int feat_dim = M == 5 ? VGE_FEAT_DIM : VGE_FEAT_DIM_NOKP;
-  std::vector<Off> eoff(n_enc);
-  int col_raw = 0, col_diff = M == 5 ? VGE_RAW_DIM : VGE_RAW_DIM_NOKP;
-  for (int kind = 0; kind < 2; ++kind) {
-    for (int m = 0; m < M; ++m) {
-      const int e = kind * M + m;
-      const std::string pre = std::string(kind == 0 ? "state_enc." : "motion_enc.") + kMods[m];
-      const int d_in = kind == 0 ? kDimsRaw[m] : kDimsDiff[m];
-      Off& o = eoff[e];
-      o.d_in = d_in;
-      o.P = (d_in + 255) / 256;
-      o.in_col = kind == 0 ? col_raw : col_diff;
-      if (kind == 0) col_raw += d_in; else col_diff += d_in;
-      const float* stem = get(pre + ".stem.weight", {256, d_in, 1});
-      const float* cw[8];
-      for (int b = 0; b < 4; ++b)
-        for (int cv = 0; cv < 2; ++cv)
-          cw[b * 2 + cv] = get(pre + ".blocks." + std::to_string(b) + ".conv" + std::to_string(cv + 1) + ".weight", {256, 256, 5});
-      const float* proj = get(pre + ".proj.weight", {256, 256});
-      const float *gw[4], *gb[4];
-      for (int b = 0; b < 4; ++b) {
-        gw[b] = get(pre + ".blocks." + std::to_string(b) + ".norm.weight", {256});
-        gb[b] = get(pre + ".blocks." + std::to_string(b) + ".norm.bias", {256});
-      }
-      if (!err.empty()) return bail();
-      const float* projw = proj;
-      o.fold = 0;
-      if (x3s) {
-        pk.resize((pk.size() + 63) / 64 * 64, 0.f);  // 256-B aligned: the kernel reads 16-B vectors
-        o.fold = pk.size();
-        pk.resize(pk.size() + 3 * 256 * 16 + 512, 0.f);
-        for (int b = 1; b <= 4; ++b) {  // GroupNorm b-1 folded into block b's conv1 (b < 4) or the proj (b == 4)
-          const float* g = gw[b - 1];
-          const float* be = gb[b - 1];
-          const float* src = b < 4 ? cw[2 * b] : proj;
-          const int ntap = b < 4 ? 5 : 1;
-          folded.emplace_back((size_t)256 * 256 * ntap);
-          float* f = folded.back().data();
-          for (size_t q = 0; q < folded.back().size(); ++q) f[q] = src[q] * g[(q / ntap) & 255];
-          parallel_for(256, [&](int n) {
-            double sg[5] = {0, 0, 0, 0, 0}, sb[5] = {0, 0, 0, 0, 0};
-            for (int ci = 0; ci < 256; ++ci)
-              for (int tap = 0; tap < ntap; ++tap) {
-                const size_t q = ((size_t)n * 256 + ci) * ntap + tap;
-                sg[tap] += f[q];
-                sb[tap] += (double)src[q] * be[ci];
-              }
-            if (b == 4) {
-              pk[o.fold + 3 * 256 * 16 + n * 2] = (float)sg[0];
-              pk[o.fold + 3 * 256 * 16 + n * 2 + 1] = (float)sb[0];
-              return;
-            }
-            // per-tap sums: the kernel adds the taps that fall inside the window for each of its rows
-            for (int tap = 0; tap < 5; ++tap) {
-              pk[o.fold + ((size_t)(b - 1) * 256 + n) * 16 + tap] = (float)sg[tap];
-              pk[o.fold + ((size_t)(b - 1) * 256 + n) * 16 + 8 + tap] = (float)sb[tap];
-            }
-          });
-          if (b < 4) cw[2 * b] = f;
-          else projw = f;
-        }
-      }
-      o.stem = pack_lin(stem, 256, d_in, d_in, o.P);
-      o.conv = pack_cv(cw[0]);
-      for (int c = 1; c < 8; ++c) pack_cv(cw[c]);
-      o.proj = pack_lin(projw, 256, 256, 256, 1);
-      o.gnw = pk.size();
-      for (int b = 0; b < 4; ++b) pk.insert(pk.end(), gw[b], gw[b] + 256);
-      o.gnb = pk.size();
-      for (int b = 0; b < 4; ++b) pk.insert(pk.end(), gb[b], gb[b] + 256);
-    }
-  }
-  // fusion: fold the constant query  u = Wk^T (Wq q_ln(latent)),  Wov = Wo Wv
-  const float* latent = get("fusion.latent", {1, 1, 256});
-  const float* qw = get("fusion.q_ln.weight", {256});
-  const float* qb = get("fusion.q_ln.bias", {256});
-  const float* kvw = get("fusion.kv_ln.weight", {256});
-  const float* kvb = get("fusion.kv_ln.bias", {256});
-  const float* Wq = get("fusion.Wq.weight", {256, 256});
-  const float* Wk = get("fusion.Wk.weight", {256, 256});
-  const float* Wv = get("fusion.Wv.weight", {256, 256});
-  const float* Wo = get("fusion.Wo.weight", {256, 256});
-  const float* ltemp = get("fusion.logit_temp", {M});
-  const float* lbias = get("fusion.logit_bias", {M});
-  const float* cls = get("cls", {1, 1, 256});
-  auto pe_it = wm.find("pos_enc.pe");
-  if (pe_it == wm.end() && err.empty()) err = "missing weight: pos_enc.pe";
-  const float* pe = nullptr;
-  if (pe_it != wm.end()) {
-    const vge_tensor_view* t = pe_it->second;
-    if (t->ndim == 3 && t->shape[0] == 1 && t->shape[1] >= 33 && t->shape[2] == 256 && t->data) pe = t->data;
-    else if (err.empty()) err = "bad shape for weight: pos_enc.pe";
-  }
-  if (!err.empty()) return bail();
-
-  std::vector<double> q(256), Q(256);
-  {
-    double mu = 0, var = 0;
-    for (int i = 0; i < 256; ++i) mu += latent[i];
-    mu /= 256;
-    for (int i = 0; i < 256; ++i) var += (latent[i] - mu) * (latent[i] - mu);
-    var /= 256;
-    const double rstd = 1.0 / std::sqrt(var + 1e-5);
-    for (int i = 0; i < 256; ++i) q[i] = (latent[i] - mu) * rstd * qw[i] + qb[i];
-    for (int j = 0; j < 256; ++j) {
-      double a = 0;
-      for (int i = 0; i < 256; ++i) a += q[i] * Wq[(size_t)j * 256 + i];
-      Q[j] = a;
-    }
-  }
-  const size_t off_u = pk.size();
-  for (int i = 0; i < 256; ++i) {
-    double a = 0;
-    for (int j = 0; j < 256; ++j) a += Q[j] * Wk[(size_t)j * 256 + i];
-    pk.push_back((float)a);
-  }
-  const size_t off_kvw = pk.size();
-  pk.insert(pk.end(), kvw, kvw + 256);
-  const size_t off_kvb = pk.size();
-  pk.insert(pk.end(), kvb, kvb + 256);
-  std::vector<float> wov(256 * 256);
-  parallel_for(256, [&](int i) {
-    for (int j = 0; j < 256; ++j) {
-      double a = 0;
-      for (int k = 0; k < 256; ++k) a += (double)Wo[(size_t)i * 256 + k] * Wv[(size_t)k * 256 + j];
-      wov[(size_t)i * 256 + j] = (float)a;
-    }
-  });
-  const Mat m_wov = pack_lin(wov.data(), 256, 256, 256, 1);
-  const size_t off_cls = pk.size();
-  pk.insert(pk.end(), cls, cls + 256);
-  const size_t off_pe = pk.size();
-  pk.insert(pk.end(), pe, pe + 33 * 256);
-
-  struct LOff { Mat in_w, out_w, l1_w, l2_w; size_t in_b, out_b, l1_b, l2_b, n1_w, n1_b, n2_w, n2_b; int e_x1, e_x2, e_h; };
-  std::vector<LOff> loff(L);
-  // the fused transformer (x3 modes, <= 8 layers, unless VGE_X3_UNFUSED=1) reads in_proj's outputs in head order
-  // (vge_transformer_x3.hip): output block j, wave w, tile t <- the original block (q | k | v) and head half of
-  // kInPerm[j][t], rows 64 w + 32 half .. + 31; the per-layer kernels of the unfused path keep q | k | v
-  const char* uf_env = getenv("VGE_X3_UNFUSED");
-  const bool tx_fused = x3 && (!(uf_env && uf_env[0] == '1') || compute == VGE_F16) && L <= 8;
-  static const int kInPerm[3][2][2] = {{{0, 0}, {1, 0}}, {{2, 0}, {0, 1}}, {{1, 1}, {2, 1}}};  // {block, half}
-  auto in_perm_row = [](int nr) {
-    const int j = nr >> 8, c = nr & 255, w = c >> 6, t = (c >> 5) & 1, i = c & 31;
-    return kInPerm[j][t][0] * 256 + 64 * w + 32 * kInPerm[j][t][1] + i;
-  };
-  std::vector<std::vector<float>> in_perm;  // permuted in_proj copies, alive until packed
-  for (int l = 0; l < L; ++l) {
-    const std::string p = "temporal.layers." + std::to_string(l);
-    const float* inw = get(p + ".self_attn.in_proj_weight", {768, 256});
-    const float* inb = get(p + ".self_attn.in_proj_bias", {768});
-    const float* ow = get(p + ".self_attn.out_proj.weight", {256, 256});
-    const float* ob = get(p + ".self_attn.out_proj.bias", {256});
-    const float* l1w = get(p + ".linear1.weight", {1024, 256});
-    const float* l1b = get(p + ".linear1.bias", {1024});
-    const float* l2w = get(p + ".linear2.weight", {256, 1024});
-    const float* l2b = get(p + ".linear2.bias", {256});
-    const float* n1w = get(p + ".norm1.weight", {256});
-    const float* n1b = get(p + ".norm1.bias", {256});
-    const float* n2w = get(p + ".norm2.weight", {256});
-    const float* n2b = get(p + ".norm2.bias", {256});
-    if (!err.empty()) return bail();
-    LOff& o = loff[l];
-    if (tx_fused) {
-      in_perm.emplace_back((size_t)768 * 257);
-      float* pw = in_perm.back().data();
-      for (int nr = 0; nr < 768; ++nr) {
-        std::copy(inw + (size_t)in_perm_row(nr) * 256, inw + (size_t)in_perm_row(nr) * 256 + 256, pw + (size_t)nr * 256);
-        pw[768 * 256 + nr] = inb[in_perm_row(nr)];
-      }
-      inw = pw;
-      inb = pw + 768 * 256;
-    }
-    o.in_w = pack_lin(inw, 768, 256, 256, 1);
-    o.out_w = pack_lin(ow, 256, 256, 256, 1);
-    o.l1_w = pack_lin(l1w, 1024, 256, 256, 1);
-    o.l2_w = pack_lin(l2w, 256, 1024, 1024, 4);
-    o.in_b = pk.size(); pk.insert(pk.end(), inb, inb + 768);
-    o.out_b = pk.size(); pk.insert(pk.end(), ob, ob + 256);
-    o.l1_b = pk.size(); pk.insert(pk.end(), l1b, l1b + 1024);
-    o.l2_b = pk.size(); pk.insert(pk.end(), l2b, l2b + 256);
-    o.n1_w = pk.size(); pk.insert(pk.end(), n1w, n1w + 256);
-    o.n1_b = pk.size(); pk.insert(pk.end(), n1b, n1b + 256);
-    o.n2_w = pk.size(); pk.insert(pk.end(), n2w, n2w + 256);
-    o.n2_b = pk.size(); pk.insert(pk.end(), n2b, n2b + 256);
-    // static operand scales of the fused x3 transformer (vge_transformer_x3.hip): a LayerNorm output is
-    // bounded by 16 max|gamma| + max|beta| (sum_j z_j^2 <= 256), ReLU(X1 W1^T + b1) by
-    // max_n sum_k |W1[n][k]| * that + |b1[n]|
-    auto ln_bound = [](const float* g, const float* b) {
-      double mg = 0.0, mb = 0.0;
-      for (int j = 0; j < 256; ++j) {
-        mg = std::max(mg, (double)std::fabs(g[j]));
-        mb = std::max(mb, (double)std::fabs(b[j]));
-      }
-      return 16.0 * mg + mb;
-    };
-    const double b1 = ln_bound(n1w, n1b), b2 = ln_bound(n2w, n2b);
-    double bh = 0.0;
-    for (int n = 0; n < 1024; ++n) {
-      double a = 0.0;
-      for (int k = 0; k < 256; ++k) a += std::fabs((double)l1w[(size_t)n * 256 + k]);
-      bh = std::max(bh, a * b1 + std::fabs((double)l1b[n]));
-    }
-    o.e_x1 = range_exp(b1);
-    o.e_x2 = range_exp(b2);
-    o.e_h = range_exp(bh);
-  }
-
-  vge_encoder* enc = new vge_encoder();
-  enc->mode = compute;
-  enc->n_mod = M;
-  enc->n_enc = n_enc;
-  enc->feat_dim = feat_dim;
-  if (compute == VGE_F16) {  // default: the transformer keeps the split (most of the f16 error, ~10% of the FLOPs)
-    const char* mx = getenv("VGE_F16_MIX");
-    enc->f16_mix = mx ? atoi(mx) : 2;
-    const char* fw = getenv("VGE_F16W");
-    enc->f16w = fw ? atoi(fw) : 6;
-  }
-  enc->n_layers = L;
-  auto hipfail = [&](hipError_t he) {
-    vge_encoder_destroy(enc);
-    return fail(VGE_ERR_HIP, std::string("vge_encoder_create: ") + hipGetErrorString(he));
-  };
-  // column scaling keeps every finite weight in the fp16 planes' range; a non-finite one cannot be split
-  const char* hp_env = getenv("VGE_HOST_PACK");
-  const bool host_pack = x3 && hp_env && hp_env[0] == '1';
-  std::vector<_Float16> ph;
-  if (host_pack) {
-    for (const PackJob& j : jobs) {
-      std::vector<float> cs;
-      const float* W = j.W;
-      const int ldk = j.ldk;
-      if (j.conv)
-        pack_linear_x3([&](int n, int k) { return W[((size_t)n * 256 + (k & 255)) * 5 + (k >> 8)]; }, j.N, j.K_real,
-                       ph, cs, 1);
-      else
-        pack_linear_x3([&](int n, int k) { return W[(size_t)n * ldk + k]; }, j.N, j.K_real, ph, cs, 8);
-      std::copy(cs.begin(), cs.end(), pk.begin() + j.cs);
-    }
-    for (const _Float16 v : ph)
-      if (!std::isfinite((float)v)) {
-        vge_encoder_destroy(enc);
-        return fail(VGE_ERR_ARG, "vge_encoder_create: non-finite weight, not representable by the 3xfp16 split; use VGE_F32");
-      }
-  }
-  enc->x3s = x3s;
-  hipError_t he = x3 ? vge::encoder_x3_kernel_setup() : vge::encoder_kernel_setup();
-  if (he == hipSuccess && x3s) he = vge::encoder_x3s_kernel_setup();
-
-  if (he == hipSuccess) he = hipMalloc(&enc->wbuf, pk.size() * sizeof(float));
-  if (he == hipSuccess) he = hipMemcpy(enc->wbuf, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (he == hipSuccess && x3) he = hipMalloc(&enc->hbuf, ph_n * sizeof(_Float16));
-  if (he == hipSuccess && host_pack) he = hipMemcpy(enc->hbuf, ph.data(), ph_n * sizeof(_Float16), hipMemcpyHostToDevice);
-  if (he != hipSuccess) return hipfail(he);
-  enc->n_half = x3 ? ph_n : 0;
-  enc->n_f32 = pk.size();
-  if (x3 && !host_pack) {
-    // raw f32 weights staged in HBM (one buffer), then packed by launch_pack_x3 straight into hbuf / wbuf
-    size_t raw = 0, ncol = 0;
-    std::vector<size_t> roff(jobs.size());
-    for (size_t i = 0; i < jobs.size(); ++i) {
-      roff[i] = raw;
-      raw += (size_t)jobs[i].N * (jobs[i].conv ? 1280 : jobs[i].ldk);
-      ncol = std::max(ncol, (size_t)jobs[i].N);
-    }
-    float* d_raw = nullptr;
-    int* d_sh = nullptr;  // [jobs][ncol] column exponents, then the non-finite flag
-    he = hipMalloc(&d_raw, raw * sizeof(float));
-    if (he == hipSuccess) he = hipMalloc(&d_sh, (jobs.size() * ncol + 1) * sizeof(int));
-    if (he == hipSuccess) he = hipMemset(d_sh + jobs.size() * ncol, 0, sizeof(int));
-    for (size_t i = 0; i < jobs.size() && he == hipSuccess; ++i) {
-      const PackJob& j = jobs[i];
-      he = hipMemcpyAsync(d_raw + roff[i], j.W, (size_t)j.N * (j.conv ? 1280 : j.ldk) * sizeof(float),
-                          hipMemcpyHostToDevice, nullptr);
-      if (he == hipSuccess)
-        he = vge::launch_pack_x3(d_raw + roff[i], j.N, j.K_real, j.ldk, j.conv, j.nch, d_sh + i * ncol,
-                                 enc->wbuf + j.cs, d_sh + jobs.size() * ncol, enc->hbuf + j.off, nullptr);
-    }
-    int bad = 0;
-    if (he == hipSuccess) he = hipMemcpy(&bad, d_sh + jobs.size() * ncol, sizeof(int), hipMemcpyDeviceToHost);
-    if (d_raw) (void)hipFree(d_raw);
-    if (d_sh) (void)hipFree(d_sh);
-    if (he != hipSuccess) return hipfail(he);
-    if (bad) {
-      vge_encoder_destroy(enc);
-      return fail(VGE_ERR_ARG, "vge_encoder_create: non-finite weight, not representable by the 3xfp16 split; use VGE_F32");
-    }
-  }
-  float* wb = enc->wbuf;
-  _Float16* hb = enc->hbuf;
-  auto mat = [&](const Mat& m) -> const void* { return x3 ? (const void*)(hb + m.off) : (const void*)(wb + m.off); };
-  if (x3) {
-    std::vector<vge::EncDescX3Host> descs(n_enc);
-    for (int e = 0; e < n_enc; ++e)
-    {
-      descs[e] = vge::EncDescX3Host{hb + eoff[e].stem.off, hb + eoff[e].conv.off, hb + eoff[e].proj.off,
-                                    wb + eoff[e].gnw, wb + eoff[e].gnb, wb + eoff[e].stem.cs,  // [10][256] scales
-                                    x3s ? wb + eoff[e].fold : nullptr, eoff[e].in_col, eoff[e].d_in, eoff[e].P,
-                                    feat_dim, {}, {}};
-      for (int b = 0; b < 4; ++b) {
-        float gm = 0.f, bm = 0.f;
-        for (int c = 0; c < 256; ++c) {
-          gm = std::max(gm, std::fabs(pk[eoff[e].gnw + b * 256 + c]));
-          bm = std::max(bm, std::fabs(pk[eoff[e].gnb + b * 256 + c]));
-        }
-        descs[e].gn_gmax[b] = gm;
-        descs[e].gn_bmax[b] = bm;
-      }
-    }
-    for (int e = 0; e < n_enc; ++e)
-      if (eoff[e].P > 1) enc->stem_heavy |= 1u << e;
-    he = hipMalloc(&enc->d_encs, sizeof(vge::EncDescX3Host) * n_enc);
-    if (he == hipSuccess)
-      he = hipMemcpy(enc->d_encs, descs.data(), sizeof(vge::EncDescX3Host) * n_enc, hipMemcpyHostToDevice);
-  } else {
-    std::vector<vge::EncDescHost> descs(n_enc);
-    for (int e = 0; e < n_enc; ++e)
-      descs[e] = vge::EncDescHost{wb + eoff[e].stem.off, wb + eoff[e].conv.off, wb + eoff[e].proj.off, wb + eoff[e].gnw,
-                                  wb + eoff[e].gnb, eoff[e].in_col, eoff[e].d_in, eoff[e].P, feat_dim};
-    he = hipMalloc(&enc->d_encs, sizeof(vge::EncDescHost) * n_enc);
-    if (he == hipSuccess) he = hipMemcpy(enc->d_encs, descs.data(), sizeof(vge::EncDescHost) * n_enc, hipMemcpyHostToDevice);
-  }
-  if (he != hipSuccess) return hipfail(he);
-  enc->fuse.kv_w = wb + off_kvw;
-  enc->fuse.kv_b = wb + off_kvb;
-  enc->fuse.u = wb + off_u;
-  enc->fuse.n_mod = M;
-  for (int m = 0; m < M; ++m) {
-    const float x = ltemp[m];
-    const float sp = x > 20.0f ? x : log1pf(expf(x));  // F.softplus (beta 1, threshold 20)
-    enc->fuse.inv_tau[m] = 1.0f / (sp + 1e-3f);
-    enc->fuse.bias[m] = lbias[m];
-    enc->fuse.has_motion[m] = 1;
-  }
-  enc->Wov = mat(m_wov);
-  enc->Wov_cs = x3 ? wb + m_wov.cs : nullptr;
-  enc->cls = wb + off_cls;
-  enc->pe = wb + off_pe;
-  enc->layers.resize(L);
-  for (int l = 0; l < L; ++l) {
-    const LOff& o = loff[l];
-    auto csp = [&](const Mat& m) -> const float* { return x3 ? wb + m.cs : nullptr; };
-    enc->layers[l] = vge_encoder::Layer{mat(o.in_w), mat(o.out_w), mat(o.l1_w), mat(o.l2_w), wb + o.in_b, wb + o.out_b,
-                                        wb + o.l1_b, wb + o.l2_b, wb + o.n1_w, wb + o.n1_b, wb + o.n2_w, wb + o.n2_b,
-                                        csp(o.in_w), csp(o.out_w), csp(o.l1_w), csp(o.l2_w), o.e_x1, o.e_x2, o.e_h};
-  }
-  if (x3) {
-    enc->tx_fused = tx_fused;  // the f16 mode has the fused kernel only; it takes up to 8 layers
-    std::vector<vge::TxLayerX3Host>& tl = enc->tx_layers;
-    tl.resize(L);
-    for (int l = 0; l < L; ++l) {
-      const vge_encoder::Layer& y = enc->layers[l];
-      tl[l] = vge::TxLayerX3Host{(const _Float16*)y.in_w, y.in_cs, y.in_b, (const _Float16*)y.out_w, y.out_cs, y.out_b,
-                                 y.n1_w, y.n1_b, (const _Float16*)y.l1_w, y.l1_cs, y.l1_b, (const _Float16*)y.l2_w,
-                                 y.l2_cs, y.l2_b, y.n2_w, y.n2_b, y.e_x1, y.e_x2, y.e_h, 0};
-    }
-    he = vge::transformer_x3_kernel_setup();
-    if (he != hipSuccess) return hipfail(he);
-  }
-  he = hipEventCreateWithFlags(&enc->conv_done, hipEventDisableTiming);
-  if (he != hipSuccess) return hipfail(he);
-  he = hipHostMalloc(reinterpret_cast<void**>(&enc->status_h), sizeof(int), hipHostMallocMapped | hipHostMallocCoherent);
-  if (he == hipSuccess) {
-    *enc->status_h = 0;
-    he = hipHostGetDevicePointer(reinterpret_cast<void**>(&enc->status_d), enc->status_h, 0);
-  }
-  if (he != hipSuccess) return hipfail(he);
-  *out = enc;
-  return VGE_OK;
+  Weights w(weights, n_weights);
+  return generic ? create_generic(dims, w, out) : create_tiled(dims, w, compute, env, out);
 }
 
 int vge_encoder_reserve(vge_encoder* enc, int B) {
@@ -1218,6 +1211,7 @@ int vge_encoder_destroy(vge_encoder* enc) {
   for (hipEvent_t e : enc->prof_ev) (void)hipEventDestroy(e);
   if (enc->ws) (void)hipFree(enc->ws);
   if (enc->d_encs) (void)hipFree(enc->d_encs);
+  if (enc->d_encs_x3) (void)hipFree(enc->d_encs_x3);
   if (enc->wbuf) (void)hipFree(enc->wbuf);
   if (enc->d_units) (void)hipFree(enc->d_units);
   if (enc->conv_done) (void)hipEventDestroy(enc->conv_done);
@@ -1304,10 +1298,10 @@ int vge_encode(vge_encoder* enc, const float* feats, int B, int T, float* seq_em
   auto gemm = [&](int epi, const float* A, int lda, const void* W, const float* cs, float* o, int ldo, int Mr, int K,
                   int N, const float* bias, const float* res, const float* lw, const float* lb) -> hipError_t {
     if (x3) {
-      vge::GemmArgsX3Host g{A, lda, (const _Float16*)W, o, ldo, Mr, K, N, bias, res, 256, lw, lb, enc->pe, enc->cls, cs};
+      vge::GemmArgsX3 g{A, lda, (const _Float16*)W, o, ldo, Mr, K, N, bias, res, 256, lw, lb, enc->pe, enc->cls, cs};
       return vge::launch_gemm_x3(epi, g, s);
     }
-    vge::GemmArgsHost g{A, lda, (const float*)W, o, ldo, Mr, K, N, bias, res, 256, lw, lb, enc->pe, enc->cls};
+    vge::GemmArgs g{A, lda, (const float*)W, o, ldo, Mr, K, N, bias, res, 256, lw, lb, enc->pe, enc->cls};
     return vge::launch_gemm(epi, g, s);
   };
   HIPCHK(mark(0));
@@ -1329,13 +1323,14 @@ int vge_encode(vge_encoder* enc, const float* feats, int B, int T, float* seq_em
     }
     enc->tables[k].used = ++enc->units_clock;
     enc->units_last = k;
-    HIPCHK(vge::launch_conv_encoders_f16w(feats, B, enc->d_encs, enc->enc_out, enc->d_units + (size_t)k * enc->units_cap,
+    HIPCHK(vge::launch_conv_encoders_f16w(feats, B, enc->d_encs_x3, enc->enc_out, enc->d_units + (size_t)k * enc->units_cap,
                                           enc->tables[k].G, enc->tables[k].R, s));
   } else if (x3 && enc->x3s) {
-    HIPCHK(vge::launch_conv_encoders_x3s(feats, B, enc->d_encs, enc->n_enc, enc->stem_heavy, enc->enc_out,
+    HIPCHK(vge::launch_conv_encoders_x3s(feats, B, enc->d_encs_x3, enc->n_enc, enc->stem_heavy, enc->enc_out,
                                          enc->status_d, split, s));
   } else if (x3) {
-    HIPCHK(vge::launch_conv_encoders_x3(feats, B, enc->d_encs, enc->n_enc, enc->stem_heavy, enc->enc_out, split, enc->f16_mix & 1, s));
+    HIPCHK(vge::launch_conv_encoders_x3(feats, B, enc->d_encs_x3, enc->n_enc, enc->stem_heavy, enc->enc_out, split,
+                                        enc->f16_mix & 1, s));
   } else {
     HIPCHK(vge::launch_conv_encoders(feats, B, enc->d_encs, enc->n_enc, enc->enc_out, s));
   }
@@ -1358,8 +1353,12 @@ int vge_encode(vge_encoder* enc, const float* feats, int B, int T, float* seq_em
   }
   if (x3 && enc->tx_fused) {  // tokens + all layers + outputs in one launch, one window per workgroup
     HIPCHK(mark(3));
-    const vge::TxArgsX3Host ta{enc->pooled, B, enc->n_layers, (const _Float16*)enc->Wov, enc->Wov_cs, enc->cls, enc->pe,
-                               enc->tx_layers.data(), seq_embed, frame_embed, tc_window};
+    vge::TxArgsX3 ta = enc->tx;
+    ta.pooled = enc->pooled;
+    ta.n_windows = B;
+    ta.seq = seq_embed;
+    ta.frame = frame_embed;
+    ta.tc = tc_window;
     HIPCHK(vge::launch_transformer_x3(ta, (split || (enc->f16_mix & 2)) ? 2 : ((enc->f16_mix & 4) ? 1 : 0), s));
     HIPCHK(mark(4));
     HIPCHK(mark(5));
@@ -1377,7 +1376,7 @@ int vge_encode(vge_encoder* enc, const float* feats, int B, int T, float* seq_em
     HIPCHK(gemm(vge::EPI_BIAS_RES_LN, enc->att, 256, Ly.out_w, Ly.out_cs, enc->x1, 256, M, 256, 256, Ly.out_b, enc->x,
                 Ly.n1_w, Ly.n1_b));
     if (x3) {  // fused FFN block: the 1024-wide hidden stays on chip
-      const vge::FfnArgsX3Host fa{enc->x1, enc->x, M, (const _Float16*)Ly.l1_w, Ly.l1_cs, Ly.l1_b,
+      const vge::FfnArgsX3 fa{enc->x1, enc->x, M, (const _Float16*)Ly.l1_w, Ly.l1_cs, Ly.l1_b,
                                   (const _Float16*)Ly.l2_w, Ly.l2_cs, Ly.l2_b, Ly.n2_w, Ly.n2_b};
       HIPCHK(vge::launch_ffn_x3(fa, s));
     } else {

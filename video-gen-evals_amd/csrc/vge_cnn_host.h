@@ -22,10 +22,9 @@
 
 #include "../../include/vge.h"
 #include "vge_cnn.h"
+#include "vge_error.h"
 
 namespace vge {
-void set_last_error(const std::string& msg);  // vge_api.cpp (vge_last_error)
-
 namespace cnnh {
 
 inline int fail(int code, const std::string& msg) {

@@ -19,9 +19,11 @@
 // values of 4 consecutive K-steps.  Weights are packed on the host into 16 KB "chunks" (4 K-steps x 256
 // output columns) in the exact LDS image [g][n][q] = W[n][64g + 4c + q] that the B reads use.
 #include "vge_common.h"
-#include <cstring>
+#include "vge_core.h"
 
 namespace {
+
+using namespace vge;  // EncDesc, FuseParams, GemmArgs, EPI_* (vge_core.h)
 
 constexpr int CHUNK_F = 4096;          // floats per weight chunk (16 KB)
 constexpr int CHUNKS_PER_PANEL = 16;   // 64 K-steps / 4
@@ -80,19 +82,6 @@ __device__ __forceinline__ void zero_acc(floatx4 (&acc)[NT]) {
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) acc[nt] = floatx4{0.f, 0.f, 0.f, 0.f};
 }
-
-// ------------------------------------------------------------------ encoder descriptors
-struct EncDesc {
-  const float* stem;   // n_stem_panels * 16 chunks
-  const float* conv;   // 4 blocks x 2 convs x 5 taps x 16 chunks
-  const float* proj;   // 16 chunks
-  const float* gn_w;   // [4][256]
-  const float* gn_b;   // [4][256]
-  int in_col;          // column offset of this encoder's input in feats
-  int d_in;
-  int n_stem_panels;
-  int ld;              // feats row width (2596, or 2356 keypoint-less)
-};
 
 // ------------------------------------------------------------------ conv encoder chain
 // grid: n_enc * n_pairs blocks (XCD-aware order: concurrent blocks on one XCD share an encoder);
@@ -239,16 +228,6 @@ __global__ void __launch_bounds__(256, 1) conv_encoder_kernel(const float* __res
 }
 
 // ------------------------------------------------------------------ modality fusion (one wave per frame row)
-struct FuseParams {
-  const float* kv_w;     // [256]
-  const float* kv_b;     // [256]
-  const float* u;        // [256] = Wk^T (Wq LN(latent))   (folded constant query)
-  float inv_tau[8];      // 1 / (softplus(logit_temp) + 1e-3)
-  float bias[8];         // logit_bias
-  int n_mod;
-  int has_motion[8];
-};
-
 // NMOD modalities in infer_dims_from_stats order: vit, global, pose, beta[, kp2d] (5, or 4 keypoint-less); enc_out
 // planes 0..NMOD-1 are the state encoders, NMOD..2 NMOD-1 the motion encoders
 // wave sum broadcast to every lane by DPP row reductions + one readlane (VALU latency): the shuffle butterfly's
@@ -309,20 +288,6 @@ __global__ void __launch_bounds__(256) fuse_kernel(const float* __restrict__ enc
 // ------------------------------------------------------------------ panel GEMM with fused epilogues
 // out[M, N] = A[M, K] * W[N, K]^T.  Block = 4 waves = 2 row strips (16 rows) x 2 column halves (128 cols):
 // BM = 32 rows, BN = 256 cols; grid = (ceil(M/32), N/256).  A panels (32 x 256) staged by global_load_lds.
-enum Epi { EPI_TOKENS = 0, EPI_BIAS = 1, EPI_BIAS_RELU = 2, EPI_BIAS_RES_LN = 3 };
-
-struct GemmArgs {
-  const float* A;  int lda;     // rows padded to a multiple of 32 (pad rows are finite)
-  const float* W;               // packed chunks [N/256][K/256][16][4096]
-  float* out;      int ldo;
-  int M, K, N;
-  const float* bias;            // [N]
-  const float* res;  int ldr;   // residual (EPI_BIAS_RES_LN)
-  const float* ln_w; const float* ln_b;
-  const float* pe;              // EPI_TOKENS: pos_enc.pe [5000,256]
-  const float* cls;             // EPI_TOKENS: cls [256]
-};
-
 constexpr int GEMM_LDS_BYTES = (32 * VGE_LDX + 3 * CHUNK_F + 64) * 4;
 
 template <int EPI>
@@ -519,24 +484,6 @@ __global__ void __launch_bounds__(256) embed_tc_kernel(const float* __restrict__
 // ================================================================== host launchers
 namespace vge {
 
-struct EncDescHost {
-  const float* stem; const float* conv; const float* proj; const float* gn_w; const float* gn_b;
-  int in_col, d_in, n_stem_panels, ld;
-};
-static_assert(sizeof(EncDescHost) == sizeof(EncDesc), "EncDesc layout");
-
-struct FuseParamsHost {
-  const float* kv_w; const float* kv_b; const float* u;
-  float inv_tau[8]; float bias[8]; int n_mod; int has_motion[8];
-};
-static_assert(sizeof(FuseParamsHost) == sizeof(FuseParams), "FuseParams layout");
-
-struct GemmArgsHost {
-  const float* A; int lda; const float* W; float* out; int ldo; int M, K, N;
-  const float* bias; const float* res; int ldr; const float* ln_w; const float* ln_b; const float* pe; const float* cls;
-};
-static_assert(sizeof(GemmArgsHost) == sizeof(GemmArgs), "GemmArgs layout");
-
 hipError_t encoder_kernel_setup() {
   hipError_t e = hipFuncSetAttribute((const void*)conv_encoder_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      CONV_LDS_BYTES);
@@ -550,35 +497,31 @@ hipError_t encoder_kernel_setup() {
   return hipSuccess;
 }
 
-hipError_t launch_conv_encoders(const float* feats, int n_windows, const void* encs, int n_enc, float* enc_out,
+hipError_t launch_conv_encoders(const float* feats, int n_windows, const EncDesc* encs, int n_enc, float* enc_out,
                                 hipStream_t s) {
   const int n_pairs = (n_windows + 1) / 2;
   hipLaunchKernelGGL(conv_encoder_kernel, dim3(n_enc * n_pairs), dim3(256), CONV_LDS_BYTES, s, feats, n_windows,
-                     reinterpret_cast<const EncDesc*>(encs), n_enc, enc_out);
+                     encs, n_enc, enc_out);
   return hipGetLastError();
 }
 
-hipError_t launch_fuse(const float* enc_out, int n_rows, const FuseParamsHost& fp, float* pooled, hipStream_t s) {
-  FuseParams p;
-  memcpy(&p, &fp, sizeof(p));
+hipError_t launch_fuse(const float* enc_out, int n_rows, const FuseParams& fp, float* pooled, hipStream_t s) {
   if (fp.n_mod == 4)
-    hipLaunchKernelGGL(fuse_kernel<4>, dim3((n_rows + 3) / 4), dim3(256), 0, s, enc_out, n_rows, p, pooled);
+    hipLaunchKernelGGL(fuse_kernel<4>, dim3((n_rows + 3) / 4), dim3(256), 0, s, enc_out, n_rows, fp, pooled);
   else if (fp.n_mod == 5)
-    hipLaunchKernelGGL(fuse_kernel<5>, dim3((n_rows + 3) / 4), dim3(256), 0, s, enc_out, n_rows, p, pooled);
+    hipLaunchKernelGGL(fuse_kernel<5>, dim3((n_rows + 3) / 4), dim3(256), 0, s, enc_out, n_rows, fp, pooled);
   else
     return hipErrorInvalidValue;
   return hipGetLastError();
 }
 
-hipError_t launch_gemm(int epi, const GemmArgsHost& a, hipStream_t s) {
-  GemmArgs g;
-  memcpy(&g, &a, sizeof(g));
+hipError_t launch_gemm(int epi, const GemmArgs& a, hipStream_t s) {
   dim3 grid((a.M + 31) / 32, a.N / 256);
   switch (epi) {
-    case EPI_TOKENS: hipLaunchKernelGGL(gemm_kernel<EPI_TOKENS>, grid, dim3(256), GEMM_LDS_BYTES, s, g); break;
-    case EPI_BIAS: hipLaunchKernelGGL(gemm_kernel<EPI_BIAS>, grid, dim3(256), GEMM_LDS_BYTES, s, g); break;
-    case EPI_BIAS_RELU: hipLaunchKernelGGL(gemm_kernel<EPI_BIAS_RELU>, grid, dim3(256), GEMM_LDS_BYTES, s, g); break;
-    default: hipLaunchKernelGGL(gemm_kernel<EPI_BIAS_RES_LN>, grid, dim3(256), GEMM_LDS_BYTES, s, g); break;
+    case EPI_TOKENS: hipLaunchKernelGGL(gemm_kernel<EPI_TOKENS>, grid, dim3(256), GEMM_LDS_BYTES, s, a); break;
+    case EPI_BIAS: hipLaunchKernelGGL(gemm_kernel<EPI_BIAS>, grid, dim3(256), GEMM_LDS_BYTES, s, a); break;
+    case EPI_BIAS_RELU: hipLaunchKernelGGL(gemm_kernel<EPI_BIAS_RELU>, grid, dim3(256), GEMM_LDS_BYTES, s, a); break;
+    default: hipLaunchKernelGGL(gemm_kernel<EPI_BIAS_RES_LN>, grid, dim3(256), GEMM_LDS_BYTES, s, a); break;
   }
   return hipGetLastError();
 }

@@ -14,8 +14,11 @@
 //   gen_add_ln_kernel    LayerNorm(a + b) per token row (post-norm encoder layer)
 //   gen_embed_tc_kernel  normalize (model.py:190-193) + the per-window TC term (eval.py:209-226)
 #include "vge_common.h"
+#include "vge_core.h"
 
 namespace {
+
+using vge::GenFuse;  // vge_core.h
 
 constexpr int GT = 32;   // frames per window
 constexpr int GTOK = 33; // CLS + frames
@@ -100,13 +103,6 @@ __global__ void __launch_bounds__(256) gen_groupnorm_kernel(float* __restrict__ 
     p[i] = (p[i] - mean) * rstd * g[c] + b[c];
   }
 }
-
-struct GenFuse {
-  const float* kv_w; const float* kv_b; const float* u;  // [d] each (u = Wk^T Wq q_ln(latent))
-  float inv_tau[8], bias[8];
-  int n_mod, d;
-  int has_motion[8];
-};
 
 // one wave per frame row; lane holds columns lane + 64 j (j < 4)
 __global__ void __launch_bounds__(256) gen_fuse_kernel(const float* __restrict__ enc_out, int n_rows, GenFuse f,
@@ -323,13 +319,6 @@ __global__ void __launch_bounds__(256) gen_embed_tc_kernel(const float* __restri
 
 namespace vge {
 
-struct GenFuseHost {
-  const float* kv_w; const float* kv_b; const float* u;
-  float inv_tau[8], bias[8];
-  int n_mod, d;
-  int has_motion[8];
-};
-
 hipError_t launch_gen_conv(const float* x, int ldx, int xcol, int cin, const float* W, int cout, int taps, int dil, int epi,
                            const float* res, float* out, int n_windows, hipStream_t s) {
   if (taps > 5 || (taps / 2) * dil > 16) return hipErrorInvalidValue;
@@ -341,19 +330,8 @@ hipError_t launch_gen_groupnorm(float* x, int n_windows, int d, const float* g, 
   hipLaunchKernelGGL(gen_groupnorm_kernel, dim3(n_windows), dim3(256), 0, s, x, d, g, b);
   return hipGetLastError();
 }
-hipError_t launch_gen_fuse(const float* enc_out, int n_rows, const GenFuseHost& f, float* pooled_pre, hipStream_t s) {
-  GenFuse g;
-  g.kv_w = f.kv_w;
-  g.kv_b = f.kv_b;
-  g.u = f.u;
-  g.n_mod = f.n_mod;
-  g.d = f.d;
-  for (int m = 0; m < 8; ++m) {
-    g.inv_tau[m] = f.inv_tau[m];
-    g.bias[m] = f.bias[m];
-    g.has_motion[m] = f.has_motion[m];
-  }
-  hipLaunchKernelGGL(gen_fuse_kernel, dim3((n_rows + 3) / 4), dim3(256), 0, s, enc_out, n_rows, g, pooled_pre);
+hipError_t launch_gen_fuse(const float* enc_out, int n_rows, const GenFuse& f, float* pooled_pre, hipStream_t s) {
+  hipLaunchKernelGGL(gen_fuse_kernel, dim3((n_rows + 3) / 4), dim3(256), 0, s, enc_out, n_rows, f, pooled_pre);
   return hipGetLastError();
 }
 hipError_t launch_gen_gemm(const float* A, int lda, const float* W, int M, int N, int K, const float* bias, int epi,

@@ -48,7 +48,9 @@ __device__ long long g_vge_trace[64 * 8 * 32];
 
 namespace {
 
-// ------------------------------------------------------------------ conv encoder chain (EncDescX3: vge_x3.h)
+using namespace vge;  // EncDescX3, GemmArgsX3, FfnArgsX3, EPI_* (vge_core.h)
+
+// ------------------------------------------------------------------ conv encoder chain (EncDescX3: vge_core.h)
 // One workgroup = one encoder x W windows (32 W rows) on CW waves; wave w owns output columns
 // 32 N w .. 32 N w + 32 N - 1 (N = 8 / CW column tiles) of all rows, so every weight byte streamed into the
 // workgroup feeds 32 W rows.  Used as W = 4 / 2 with CW = 8 (one workgroup per CU, two waves per SIMD).
@@ -828,21 +830,6 @@ __global__ void __launch_bounds__(512, 1) conv_encoder_f16w_kernel(const float* 
 }
 
 // ------------------------------------------------------------------ panel GEMM (3xfp16) with fused epilogues
-enum Epi { EPI_TOKENS = 0, EPI_BIAS = 1, EPI_BIAS_RELU = 2, EPI_BIAS_RES_LN = 3 };
-
-struct GemmArgsX3 {
-  const float* A;  int lda;
-  const _Float16* W;            // chunks [N/256][K/16][16 KB]
-  float* out;      int ldo;
-  int M, K, N;
-  const float* bias;
-  const float* res;  int ldr;
-  const float* ln_w; const float* ln_b;
-  const float* pe;
-  const float* cls;
-  const float* cs;              // [N] weight column scales
-};
-
 // block = 8 waves, BM = 32 RT rows x BN = 256 columns, wave w owns columns 32w..32w+31 of all BM rows.
 // RT = 1: 32-row blocks, small enough (LDS 34 KB, <= 128 VGPRs) for several workgroups per CU, so one
 // workgroup's staging / epilogue latency hides behind another's MFMAs on these short (K <= 1024) GEMMs.
@@ -1005,15 +992,6 @@ __global__ void __launch_bounds__(512, 4) gemm_x3_kernel(GemmArgsX3 ga) {  // 4 
 // for a 32-row block, with the 1024-wide hidden activation never leaving the CU: the hidden dimension is
 // processed in 4 chunks of 256; each chunk's relu(X1 W1_chunk^T + b1) is split into LDS hi/lo planes and
 // immediately multiplied into the running FFN2 accumulator (K panel = that chunk).
-struct FfnArgsX3 {
-  const float* X1;  // [M (padded to 64)][256] input, also the residual
-  float* out;       // [M][256]
-  int M;
-  const _Float16* W1; const float* cs1; const float* b1;  // linear1 [1024][256]: 4 column blocks x 16 chunks
-  const _Float16* W2; const float* cs2; const float* b2;  // linear2 [256][1024]: 64 chunks (4 K panels)
-  const float* ln_w; const float* ln_b;
-};
-
 constexpr int FFN_LDS_BYTES = 4 * 32 * XSB + (32 * NWAVE + 2 * NWAVE) * 4;
 
 __global__ void __launch_bounds__(512, 4) ffn_x3_kernel(FfnArgsX3 fa) {
@@ -1214,8 +1192,6 @@ __global__ void __launch_bounds__(256) pack_x3_kernel(const float* __restrict__ 
 // ================================================================== host launchers
 namespace vge {
 
-static int conv_cu_count();
-
 hipError_t launch_pack_x3(const float* W, int N, int K_real, int ldk, int conv, int nch, int* sh, float* cs, int* bad,
                           _Float16* out, hipStream_t s) {
   if (N % 256 || K_real < 1 || nch * 16 < K_real) return hipErrorInvalidValue;
@@ -1224,21 +1200,6 @@ hipError_t launch_pack_x3(const float* W, int N, int K_real, int ldk, int conv, 
   hipLaunchKernelGGL(pack_x3_kernel, dim3((nt + 255) / 256), dim3(256), 0, s, W, N, K_real, ldk, conv, nch, sh, out);
   return hipGetLastError();
 }
-
-struct EncDescX3Host {
-  const _Float16* stem; const _Float16* conv; const _Float16* proj; const float* gn_w; const float* gn_b;
-  const float* cs; const float* fold;
-  int in_col, d_in, n_stem_panels, ld;
-  float gn_gmax[4], gn_bmax[4];
-};
-static_assert(sizeof(EncDescX3Host) == sizeof(EncDescX3), "EncDescX3 layout");
-
-struct GemmArgsX3Host {
-  const float* A; int lda; const _Float16* W; float* out; int ldo; int M, K, N;
-  const float* bias; const float* res; int ldr; const float* ln_w; const float* ln_b; const float* pe; const float* cls;
-  const float* cs;
-};
-static_assert(sizeof(GemmArgsX3Host) == sizeof(GemmArgsX3), "GemmArgsX3 layout");
 
 hipError_t encoder_x3_kernel_setup() {
   const void* ck[3] = {(const void*)conv_encoder_x3_kernel<true, true>, (const void*)conv_encoder_x3_kernel<false, true>,
@@ -1321,18 +1282,17 @@ ConvSched conv_quad_sched(int n_windows, int n_enc, unsigned heavy) {
   return cs;
 }
 
-hipError_t launch_conv_encoders_x3(const float* feats, int n_windows, const void* encs, int n_enc, unsigned heavy,
+hipError_t launch_conv_encoders_x3(const float* feats, int n_windows, const EncDescX3* encs, int n_enc, unsigned heavy,
                                    float* enc_out, bool split, bool stem_split, hipStream_t s) {
   if (n_windows < 1 || n_enc < 1) return hipSuccess;
   const ConvSched cs = conv_quad_sched(n_windows, n_enc, heavy);
   auto k = split ? conv_encoder_x3_kernel<true, true>
                  : (stem_split ? conv_encoder_x3_kernel<false, true> : conv_encoder_x3_kernel<false, false>);
-  hipLaunchKernelGGL(k, dim3(cs.G), dim3(512), (conv_lds_bytes<4, 8>()), s, feats,
-                     reinterpret_cast<const EncDescX3*>(encs), cs, enc_out);
+  hipLaunchKernelGGL(k, dim3(cs.G), dim3(512), (conv_lds_bytes<4, 8>()), s, feats, encs, cs, enc_out);
   return hipGetLastError();
 }
 
-static int conv_cu_count() {
+int conv_cu_count() {
   static int n_cu = 0;
   if (n_cu == 0) {
     int dev = 0;
@@ -1446,40 +1406,28 @@ hipError_t launch_conv_f16w_table(int n_windows, int n_enc, int G, int R, int U,
   return hipGetLastError();
 }
 
-hipError_t launch_conv_encoders_f16w(const float* feats, int n_windows, const void* encs, float* enc_out,
+hipError_t launch_conv_encoders_f16w(const float* feats, int n_windows, const EncDescX3* encs, float* enc_out,
                                      const int* d_units, int G, int R, hipStream_t s) {
   if (n_windows < 1) return hipSuccess;
   hipLaunchKernelGGL(conv_encoder_f16w_kernel, dim3(G), dim3(512), (conv_lds_bytes_max<F16W_WAVES, 1>()), s, feats,
-                     reinterpret_cast<const EncDescX3*>(encs), n_windows, G, R, d_units, enc_out);
+                     encs, n_windows, G, R, d_units, enc_out);
   return hipGetLastError();
 }
 
-hipError_t launch_gemm_x3(int epi, const GemmArgsX3Host& a, hipStream_t s) {
-  GemmArgsX3 g;
-  memcpy(&g, &a, sizeof(g));
+hipError_t launch_gemm_x3(int epi, const GemmArgsX3& a, hipStream_t s) {
   constexpr int BM = 32 * GEMM_RT, L = gemm_lds_bytes<GEMM_RT>();
   dim3 grid((a.M + BM - 1) / BM, a.N / 256);
   switch (epi) {
-    case EPI_TOKENS: hipLaunchKernelGGL((gemm_x3_kernel<EPI_TOKENS, GEMM_RT>), grid, dim3(512), L, s, g); break;
-    case EPI_BIAS: hipLaunchKernelGGL((gemm_x3_kernel<EPI_BIAS, GEMM_RT>), grid, dim3(512), L, s, g); break;
-    case EPI_BIAS_RELU: hipLaunchKernelGGL((gemm_x3_kernel<EPI_BIAS_RELU, GEMM_RT>), grid, dim3(512), L, s, g); break;
-    default: hipLaunchKernelGGL((gemm_x3_kernel<EPI_BIAS_RES_LN, GEMM_RT>), grid, dim3(512), L, s, g); break;
+    case EPI_TOKENS: hipLaunchKernelGGL((gemm_x3_kernel<EPI_TOKENS, GEMM_RT>), grid, dim3(512), L, s, a); break;
+    case EPI_BIAS: hipLaunchKernelGGL((gemm_x3_kernel<EPI_BIAS, GEMM_RT>), grid, dim3(512), L, s, a); break;
+    case EPI_BIAS_RELU: hipLaunchKernelGGL((gemm_x3_kernel<EPI_BIAS_RELU, GEMM_RT>), grid, dim3(512), L, s, a); break;
+    default: hipLaunchKernelGGL((gemm_x3_kernel<EPI_BIAS_RES_LN, GEMM_RT>), grid, dim3(512), L, s, a); break;
   }
   return hipGetLastError();
 }
 
-struct FfnArgsX3Host {
-  const float* X1; float* out; int M;
-  const _Float16* W1; const float* cs1; const float* b1;
-  const _Float16* W2; const float* cs2; const float* b2;
-  const float* ln_w; const float* ln_b;
-};
-static_assert(sizeof(FfnArgsX3Host) == sizeof(FfnArgsX3), "FfnArgsX3 layout");
-
-hipError_t launch_ffn_x3(const FfnArgsX3Host& a, hipStream_t s) {
-  FfnArgsX3 f;
-  memcpy(&f, &a, sizeof(f));
-  hipLaunchKernelGGL(ffn_x3_kernel, dim3((a.M + 31) / 32), dim3(512), FFN_LDS_BYTES, s, f);
+hipError_t launch_ffn_x3(const FfnArgsX3& a, hipStream_t s) {
+  hipLaunchKernelGGL(ffn_x3_kernel, dim3((a.M + 31) / 32), dim3(512), FFN_LDS_BYTES, s, a);
   return hipGetLastError();
 }
 

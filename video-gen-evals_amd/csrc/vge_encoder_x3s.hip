@@ -51,6 +51,8 @@ __device__ long long g_x3s_trace[64 * 8 * 128];
 
 namespace {
 
+using vge::EncDescX3;  // vge_core.h
+
 #ifndef X3S_TRACE_ROUND
 #define X3S_TRACE_ROUND 0  // VGE_TRACE builds stamp the units of this round of the persistent schedule
 #endif
@@ -752,17 +754,17 @@ hipError_t encoder_x3s_kernel_setup() {
 // before its group's last one give up, which must surface as VGE_ERR_DEVICE)
 static int g_x3s_spin_limit = 1 << 22;
 
-hipError_t launch_conv_encoders_x3s(const float* feats, int n_windows, const void* encs, int n_enc, unsigned heavy,
+hipError_t launch_conv_encoders_x3s(const float* feats, int n_windows, const EncDescX3* encs, int n_enc, unsigned heavy,
                                     float* enc_out, int* status, bool split, hipStream_t s) {
   if (n_windows < 1 || n_enc < 1) return hipSuccess;
   if (!status) return hipErrorInvalidValue;
   const ConvSched cs = conv_quad_sched(n_windows, n_enc, heavy);
   if (split)
-    hipLaunchKernelGGL(conv_encoder_x3s_kernel<true>, dim3(cs.G), dim3(512), X3S_LDS_BYTES, s, feats,
-                       reinterpret_cast<const EncDescX3*>(encs), cs, enc_out, status, g_x3s_spin_limit);
+    hipLaunchKernelGGL(conv_encoder_x3s_kernel<true>, dim3(cs.G), dim3(512), X3S_LDS_BYTES, s, feats, encs, cs, enc_out,
+                       status, g_x3s_spin_limit);
   else  // VGE_F16 (staggered single-fp16: hi planes only, one MFMA per product)
-    hipLaunchKernelGGL(conv_encoder_x3s_kernel<false>, dim3(cs.G), dim3(512), X3S_LDS_BYTES, s, feats,
-                       reinterpret_cast<const EncDescX3*>(encs), cs, enc_out, status, g_x3s_spin_limit);
+    hipLaunchKernelGGL(conv_encoder_x3s_kernel<false>, dim3(cs.G), dim3(512), X3S_LDS_BYTES, s, feats, encs, cs, enc_out,
+                       status, g_x3s_spin_limit);
   return hipGetLastError();
 }
 

@@ -14,6 +14,7 @@
 // Roofline: HBM-bound.  Algorithmic bytes per window tile: 32 rows x (1024+207+9+10+120) x 4 B
 // read (175,360 B) + 32 x 2596 x 4 B written (332,288 B).
 #include "vge_common.h"
+#include "vge_core.h"
 
 #pragma clang fp contract(off)
 

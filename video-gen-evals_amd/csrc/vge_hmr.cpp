@@ -9,24 +9,9 @@
 #include <vector>
 
 #include "../../include/vge_hmr.h"
+#include "vge_error.h"
 #include "vge_gemm.h"
-
-namespace vge {
-void set_last_error(const std::string& msg);  // vge_api.cpp (vge_last_error)
-hipError_t vit_kernels_setup();
-hipError_t launch_hmr_crop(const uint8_t*, int, int, const float*, const int*, int, uint8_t*, hipStream_t);
-hipError_t launch_ln_bf16(const float*, long, void*, long, const float*, const float*, int, int, float, hipStream_t);
-hipError_t launch_cast_bf16(const float*, long, void*, long, int, int, hipStream_t);
-hipError_t launch_bcast_rows(const float*, float*, int, int, hipStream_t);
-hipError_t launch_patchify(const uint8_t*, int, int, int, int, int, int, int, int, int, int, const float*, const float*,
-                           void*, hipStream_t);
-hipError_t launch_vit_attn(const void*, long, void*, long, int, int, int, int, hipStream_t);
-hipError_t launch_xattn1(const void*, long, const void*, long, void*, long, int, int, int, int, hipStream_t);
-hipError_t launch_softmax_rows(const float*, void*, int, int, hipStream_t);
-hipError_t launch_readout(const float*, int, const float*, int, const float*, const float*, float*, float*, float*, int,
-                          hipStream_t);
-hipError_t launch_copy_rows(const float*, long, float*, long, int, int, hipStream_t);
-}  // namespace vge
+#include "vge_hmr_k.h"
 
 namespace {
 

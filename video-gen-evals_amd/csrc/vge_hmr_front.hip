@@ -17,6 +17,7 @@
 // box is refused with hipErrorInvalidValue rather than blurred with a truncated kernel.
 // HBM-bound: reads ~4 x 3 B of frame per output pixel (L2-resident rows), writes 196,608 B per crop.
 #include "vge_common.h"
+#include "vge_hmr_k.h"
 
 #include <cmath>
 #include <vector>

@@ -20,12 +20,10 @@
 
 #include "../../include/vge_frames.h"
 #include "../../include/vge_ingest.h"
+#include "vge_error.h"
 #include "vge_jpeg_huff_tables.h"
 #include "vge_jpeg_math.h"
 
-namespace vge {
-void set_last_error(const std::string& msg);  // vge_api.cpp (vge_last_error)
-}
 using vge::set_last_error;
 
 namespace {

@@ -27,11 +27,9 @@
 #include <string>
 
 #include "../../include/vge_frames.h"
+#include "vge_error.h"
 #include "vge_jpeg_huff_tables.h"
 
-namespace vge {
-void set_last_error(const std::string& msg);  // vge_api.cpp (vge_last_error)
-}
 using vge::set_last_error;
 
 namespace {

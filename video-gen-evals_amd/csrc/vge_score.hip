@@ -17,6 +17,7 @@
 // Roofline: HBM-bound; per window the metrics read 33 x 256 x 4 + 1,024 B (0 B when fused into the
 // encoder's embed_tc_kernel, which is the default path) and write 8 B.
 #include "vge_common.h"
+#include "vge_core.h"
 
 namespace {
 

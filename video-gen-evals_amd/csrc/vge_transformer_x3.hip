@@ -15,7 +15,6 @@
 // vge_encoder_x3.hip; weight chunks as packed by pack_linear_x3 (vge_api.cpp).
 #include "vge_x3.h"
 #include <cstdlib>
-#include <cstring>
 
 #ifdef VGE_TRACE  // timing-only builds (tools/trace_transformer.py): s_memtime stamps, every wave of blocks 0..63
 __device__ long long g_vge_tx_trace[64 * 4 * 128];
@@ -32,26 +31,7 @@ __device__ long long g_vge_tx_trace[64 * 4 * 128];
 
 namespace {
 
-constexpr int TX_MAX_LAYERS = 8;
-
-struct TxLayerX3 {
-  const _Float16* in_w;  const float* in_cs; const float* in_b;     // in_proj [768][256]: 3 col blocks x 16
-  const _Float16* out_w; const float* out_cs; const float* out_b;   // out_proj [256][256]: 16 chunks
-  const float* n1_w; const float* n1_b;
-  const _Float16* l1_w; const float* l1_cs; const float* l1_b;      // linear1 [1024][256]: 4 col blocks x 16
-  const _Float16* l2_w; const float* l2_cs; const float* l2_b;      // linear2 [256][1024]: 4 K panels x 16
-  const float* n2_w; const float* n2_b;
-  int e_x1, e_x2, e_h, pad;  // static split exponents: LN1 / LN2 outputs, FFN hidden (host: range bounds)
-};
-
-struct TxArgsX3 {  // by value: the layer table is kernel-argument memory (scalar loads, no vmcnt waits)
-  const float* pooled;  // [B*32][256] fused per-frame vectors (fuse_kernel)
-  int n_windows, n_layers;
-  const _Float16* ov_w; const float* ov_cs;  // Wov = Wo Wv of the fusion (16 chunks)
-  const float* cls; const float* pe;         // [256], [33][256]
-  float* seq; float* frame; float* tc;       // [B][256], [B][33][256] | null, [B] | null
-  TxLayerX3 layers[TX_MAX_LAYERS];
-};
+using namespace vge;  // TxLayerX3, TxArgsX3, TX_MAX_LAYERS (vge_core.h)
 
 constexpr int TOK = 33;          // CLS + 32 frames
 constexpr int AROWS = TOK;       // rows of an A operand plane
@@ -901,25 +881,6 @@ __global__ void __launch_bounds__(256, OCC) transformer_x3_kernel(TxArgsX3 ta) {
 
 namespace vge {
 
-struct TxLayerX3Host {
-  const _Float16* in_w;  const float* in_cs; const float* in_b;
-  const _Float16* out_w; const float* out_cs; const float* out_b;
-  const float* n1_w; const float* n1_b;
-  const _Float16* l1_w; const float* l1_cs; const float* l1_b;
-  const _Float16* l2_w; const float* l2_cs; const float* l2_b;
-  const float* n2_w; const float* n2_b;
-  int e_x1, e_x2, e_h, pad;
-};
-static_assert(sizeof(TxLayerX3Host) == sizeof(TxLayerX3), "TxLayerX3 layout");
-
-struct TxArgsX3Host {
-  const float* pooled; int n_windows, n_layers;
-  const _Float16* ov_w; const float* ov_cs;
-  const float* cls; const float* pe;
-  const TxLayerX3Host* layers;  // host array [n_layers], n_layers <= 8
-  float* seq; float* frame; float* tc;
-};
-
 hipError_t transformer_x3_kernel_setup() {
   const struct {
     const void* k;
@@ -948,16 +909,6 @@ hipError_t transformer_x3_kernel_setup() {
 // and leave others idle (0.175 -> 0.18-0.19 ms).  VGE_TX_W=1|2 and VGE_TX_OCC=1|2 force either.
 static int g_tx_w_forced = -1;  // -1: not read yet, 0: automatic, 1 | 2 (VGE_TX_W, vge_debug_set_tx_windows)
 static int g_tx_occ = -1;       // single fp16, one window per workgroup: -1 not read yet, 0 automatic, 1 | 2 forced
-static int tx_n_cu() {
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1)
-      n_cu = 256;
-  }
-  return n_cu;
-}
 static int tx_windows_per_block(int n_windows, int mode) {
   if (g_tx_w_forced < 0) {
     const char* v = getenv("VGE_TX_W");
@@ -965,7 +916,7 @@ static int tx_windows_per_block(int n_windows, int mode) {
   }
   if (g_tx_w_forced) return g_tx_w_forced;
   if (mode == 0) return 1;
-  return n_windows >= (mode == 2 ? 8 : 4) * tx_n_cu() ? 2 : 1;
+  return n_windows >= (mode == 2 ? 8 : 4) * conv_cu_count() ? 2 : 1;
 }
 static int tx_blocks_per_cu(int n_windows) {  // single fp16, W = 1
   if (g_tx_occ < 0) {
@@ -973,47 +924,34 @@ static int tx_blocks_per_cu(int n_windows) {  // single fp16, W = 1
     g_tx_occ = (v && (v[0] == '1' || v[0] == '2')) ? v[0] - '0' : 0;
   }
   if (g_tx_occ) return g_tx_occ;
-  return n_windows > tx_n_cu() ? 2 : 1;
+  return n_windows > conv_cu_count() ? 2 : 1;
 }
 
 // mode: 0 single fp16, 1 activations split (fp16 weights), 2 3xfp16
-hipError_t launch_transformer_x3(const TxArgsX3Host& a, int mode, hipStream_t s) {
-  if (a.n_windows < 1) return hipSuccess;
-  if (a.n_layers < 0 || a.n_layers > TX_MAX_LAYERS) return hipErrorInvalidValue;
-  TxArgsX3 t;
-  memset(&t, 0, sizeof(t));
-  t.pooled = a.pooled;
-  t.n_windows = a.n_windows;
-  t.n_layers = a.n_layers;
-  t.ov_w = a.ov_w;
-  t.ov_cs = a.ov_cs;
-  t.cls = a.cls;
-  t.pe = a.pe;
-  t.seq = a.seq;
-  t.frame = a.frame;
-  t.tc = a.tc;
-  memcpy(t.layers, a.layers, sizeof(TxLayerX3) * a.n_layers);
-  if (tx_windows_per_block(a.n_windows, mode) == 2) {
+hipError_t launch_transformer_x3(const TxArgsX3& t, int mode, hipStream_t s) {
+  if (t.n_windows < 1) return hipSuccess;
+  if (t.n_layers < 0 || t.n_layers > TX_MAX_LAYERS) return hipErrorInvalidValue;
+  if (tx_windows_per_block(t.n_windows, mode) == 2) {
     if (mode == 2)
-      hipLaunchKernelGGL((transformer_x3_kernel<true, true, 2>), dim3((a.n_windows + 1) / 2), dim3(256),
+      hipLaunchKernelGGL((transformer_x3_kernel<true, true, 2>), dim3((t.n_windows + 1) / 2), dim3(256),
                          (tx_lds_bytes<2, true>()), s, t);
     else if (mode == 1)
-      hipLaunchKernelGGL((transformer_x3_kernel<true, false, 2>), dim3((a.n_windows + 1) / 2), dim3(256),
+      hipLaunchKernelGGL((transformer_x3_kernel<true, false, 2>), dim3((t.n_windows + 1) / 2), dim3(256),
                          (tx_lds_bytes<2, true>()), s, t);
     else
-      hipLaunchKernelGGL((transformer_x3_kernel<false, false, 2>), dim3((a.n_windows + 1) / 2), dim3(256),
+      hipLaunchKernelGGL((transformer_x3_kernel<false, false, 2>), dim3((t.n_windows + 1) / 2), dim3(256),
                          (tx_lds_bytes<2, false>()), s, t);
   } else {
     if (mode == 2)
-      hipLaunchKernelGGL((transformer_x3_kernel<true, true, 1>), dim3(a.n_windows), dim3(256), (tx_lds_bytes<1, true>()), s, t);
+      hipLaunchKernelGGL((transformer_x3_kernel<true, true, 1>), dim3(t.n_windows), dim3(256), (tx_lds_bytes<1, true>()), s, t);
     else if (mode == 1)
-      hipLaunchKernelGGL((transformer_x3_kernel<true, false, 1>), dim3(a.n_windows), dim3(256), (tx_lds_bytes<1, true>()), s,
+      hipLaunchKernelGGL((transformer_x3_kernel<true, false, 1>), dim3(t.n_windows), dim3(256), (tx_lds_bytes<1, true>()), s,
                          t);
-    else if (tx_blocks_per_cu(a.n_windows) == 2)
-      hipLaunchKernelGGL((transformer_x3_kernel<false, false, 1, 2>), dim3(a.n_windows), dim3(256),
+    else if (tx_blocks_per_cu(t.n_windows) == 2)
+      hipLaunchKernelGGL((transformer_x3_kernel<false, false, 1, 2>), dim3(t.n_windows), dim3(256),
                          (tx_lds_bytes<1, false>()), s, t);
     else
-      hipLaunchKernelGGL((transformer_x3_kernel<false, false, 1>), dim3(a.n_windows), dim3(256),
+      hipLaunchKernelGGL((transformer_x3_kernel<false, false, 1>), dim3(t.n_windows), dim3(256),
                          (tx_lds_bytes<1, false>()), s, t);
   }
   return hipGetLastError();

@@ -23,10 +23,7 @@
 #include <string>
 
 #include "../../include/vge.h"
-
-namespace vge {
-void set_last_error(const std::string& msg);  // vge_api.cpp (vge_last_error)
-}
+#include "vge_error.h"
 
 namespace {
 

@@ -23,6 +23,7 @@
 //   softmax_rows_kernel, readout_kernel (6D -> rotation matrix, mean-pose residuals), small helpers.
 #include "vge_common.h"
 #include "vge_gemm.h"
+#include "vge_hmr_k.h"
 #include <atomic>
 #include <cstdlib>
 

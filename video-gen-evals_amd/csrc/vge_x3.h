@@ -3,23 +3,7 @@
 // See vge_encoder_x3.hip for the arithmetic and layout description.
 #pragma once
 #include "vge_common.h"
-
-namespace vge {
-// Persistent schedule of the quad / pair conv kernels.  Work units: Q quads (4 windows) then the pairs (2 windows)
-// covering the rest of each encoder's windows; encoder e takes q_e quads (windows [0, 4 q_e)) and the pairs after
-// them.  Grid = G blocks (one per CU); unit u runs on block u % G in round u / G, so with Q a multiple of G every CU
-// does the same number of quads and at most one pair.  Within a round the block index is remapped so the 8 XCDs
-// (blocks dealt round robin) take contiguous runs of G / 8 units, i.e. the same encoders' weights in their L2.
-// q_e: whole XCD runs where that tiles Q (conv_quad_sched: then every XCD streams ONE encoder per round, and the
-// encoders with multi-panel stems -- `heavy`, a bit mask -- take the pairs), else nearly equal.  qpre / ppre: prefix
-// sums of the quads / pairs per encoder.
-constexpr int CONV_MAX_ENC = 16;
-struct ConvSched {
-  int n_windows, n_enc, G, Q, n_units;
-  int qpre[CONV_MAX_ENC + 1], ppre[CONV_MAX_ENC + 1];
-};
-ConvSched conv_quad_sched(int n_windows, int n_enc, unsigned heavy = 0);  // vge_encoder_x3.hip (host)
-}  // namespace vge
+#include "vge_core.h"  // EncDescX3, ConvSched and the other kernel-argument structs
 
 #ifndef VGE_ABL
 #define VGE_ABL 0  // timing-only ablation builds (tools/ablate.sh), a bit mask: 1 no MFMA, 2 no B loads after the
@@ -165,22 +149,6 @@ __device__ __forceinline__ void run_stream(Acc<R, N>& acc, const void* gw, int n
 #endif
   }
 }
-
-// One MovementConvEncoder's weights (model.py:21-58) as the x3 conv kernels read them.
-struct EncDescX3 {
-  const _Float16* stem;  // stem chunks; panel p (256 K) starts at chunk 16p, padded to STREAM_GROUP chunks
-  const _Float16* conv;  // 8 convs x 5 taps x 16 chunks
-  const _Float16* proj;  // 16 chunks
-  const float* gn_w;     // [4][256]
-  const float* gn_b;     // [4][256]
-  const float* cs;       // [10][256] weight column scales: stem, conv 0..7, proj
-  // staggered split kernel only (vge_encoder_x3s.hip), else null: the GroupNorm-folded corrections of blocks 1..3's
-  // conv1, [3 blocks][256 cols][16] = per-tap sums over input channels of W1 gamma (taps 0..4), then of W1 beta (at 8..12),
-  // then the proj's [256][2] (sums of P gamma, P beta)
-  const float* fold;
-  int in_col, d_in, n_stem_panels, ld;  // ld: feats row width (2596, or 2356 keypoint-less)
-  float gn_gmax[4], gn_bmax[4];  // max |gamma|, max |beta| of each GroupNorm (split-exponent bounds)
-};
 
 __host__ __device__ __forceinline__ int xcd_remap(int b, int nblk) {
   const int q8 = nblk >> 3, r8 = nblk & 7, x8 = b & 7;
