@@ -3,19 +3,12 @@
 // RTMPose-l whole-body forward.  Kernels: vge_cnn.hip (convolutions, prep), vge_pose_head.hip (head, decode).
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cmath>
-#include <cstring>
-#include <string>
-#include <unordered_map>
-#include <vector>
-
 #include "../../include/vge_dwpose.h"
-#include "vge_cnn.h"
 #include "vge_cnn_host.h"
 
-using namespace vge::cnnh;
+using namespace vge::host;
 #define HIPCHK VGE_HIPCHK
+#define RC VGE_RC
 
 namespace {
 
@@ -56,7 +49,7 @@ struct vge_dwpose {
   float mlp_g = 1.f, ln_g = 1.f;
   void* zero = nullptr;
   int hw = 0, hwp = 0;  // head feature map positions (in_h/32 * in_w/32) and their padded row width
-  // workspace
+  Workspace ws;
   int max_inst = 0;
   size_t act_elems = 0;  // per buffer (bf16 elements)
   void *in = nullptr, *X = nullptr, *D = nullptr, *SPP = nullptr, *CAT = nullptr, *Ma = nullptr, *Mb = nullptr,
@@ -71,18 +64,13 @@ struct vge_dwpose {
   std::vector<int> h_iof;
   void *pin_w = nullptr, *pin_p = nullptr, *pin_iof = nullptr;  // pinned staging of the instance tables
   hipEvent_t staged = nullptr;                                   // their last copies to the device
-  // profiling
-  std::vector<hipEvent_t> ev;
-  std::vector<int> ev_kind;
-  int prof_max = 0, prof_calls = 0, ev_per_call = 0;
-  double gemm_flops = 0, prof_flops = 0;  // prof_flops: summed over the recorded calls (instance counts differ)
+  Profiler prof;  // kinds: 0 conv / Linear, 1 depthwise / pooling / attention / prep, 2 head
+  double gemm_flops = 0;
   ~vge_dwpose() {
-    for (auto e : ev) (void)hipEventDestroy(e);
     if (staged) (void)hipEventSynchronize(staged), (void)hipEventDestroy(staged);
     for (void* p : {pin_w, pin_p, pin_iof})
       if (p) (void)hipHostFree(p);
   }
-  void* dmalloc(size_t bytes) { return dev.dmalloc(bytes); }
   ConvTuner tuner;  // per-layer conv variant, measured on first use
   ConvCtx cx() { return ConvCtx{zero, &gemm_flops, &tuner}; }
 };
@@ -296,8 +284,7 @@ int vge_dwpose_reserve(vge_dwpose* m, int max_inst) {
   }
   const size_t N = (size_t)max_inst, K = c.keypoints, rows = N * K;
   const int WXY = c.split * (c.in_w + c.in_h);
-  struct B { void** p; size_t bytes; };
-  const B bufs[] = {
+  const std::vector<Workspace::Buf> bufs = {
       {&m->in, N * c.in_h * c.in_w * 8 * 2},
       {&m->X, N * per * 2}, {&m->D, N * per * 2}, {&m->SPP, N * per * 2}, {&m->CAT, N * per * 2},
       {&m->Ma, N * per * 2}, {&m->Mb, N * per * 2}, {&m->T1, N * per * 2}, {&m->T2, N * per * 2},
@@ -315,6 +302,7 @@ int vge_dwpose_reserve(vge_dwpose* m, int max_inst) {
       {&m->pinst, N * sizeof(vge::PoseInst)},
       {(void**)&m->iof, N * 2 * sizeof(int)},
   };
+  m->max_inst = 0;
   if (!m->staged) HIPCHK(hipEventCreateWithFlags(&m->staged, hipEventDisableTiming));
   HIPCHK(hipEventSynchronize(m->staged));
   for (void* p : {m->pin_w, m->pin_p, m->pin_iof})
@@ -322,12 +310,7 @@ int vge_dwpose_reserve(vge_dwpose* m, int max_inst) {
   HIPCHK(hipHostMalloc(&m->pin_w, N * sizeof(vge::WarpInst)));
   HIPCHK(hipHostMalloc(&m->pin_p, N * sizeof(vge::PoseInst)));
   HIPCHK(hipHostMalloc(&m->pin_iof, N * 2 * sizeof(int)));
-  for (const B& b : bufs) {
-    void* p = m->dmalloc(b.bytes);
-    if (!p) return fail(VGE_ERR_NOMEM, "vge_dwpose_reserve: hipMalloc failed");
-    HIPCHK(hipMemset(p, 0, b.bytes));
-    *b.p = p;
-  }
+  RC(m->ws.reserve("vge_dwpose_reserve", bufs));
   m->act_elems = N * per;
   m->max_inst = max_inst;
   return VGE_OK;
@@ -340,30 +323,17 @@ int vge_dwpose_destroy(vge_dwpose* m) {
 
 int vge_dwpose_profile_begin(vge_dwpose* m, int max_calls) {
   if (!m || max_calls < 0) return fail(VGE_ERR_ARG, "vge_dwpose_profile_begin: bad argument");
-  for (auto e : m->ev) (void)hipEventDestroy(e);
-  m->ev_per_call = 2 * 512;
-  m->ev.assign((size_t)max_calls * m->ev_per_call, nullptr);
-  m->ev_kind.assign((size_t)max_calls * m->ev_per_call / 2, -1);
-  for (auto& e : m->ev) HIPCHK(hipEventCreate(&e));
-  m->prof_max = max_calls;
-  m->prof_calls = 0;
-  m->prof_flops = 0;
-  return VGE_OK;
+  // the STAGEs of vge_dwpose_keypoints: prep 1, stem 3, per stage down + fused 1x1 pair + channel attention + final
+  // conv and 3 per block, the SPP's 3 in the last stage, head 10
+  const int* nb = m->c.stage_blocks;
+  return m->prof.begin(max_calls, 1 + 3 + 4 * 4 + 3 * (nb[0] + nb[1] + nb[2] + nb[3]) + 3 + 10);
 }
 
 int vge_dwpose_profile_read(vge_dwpose* m, double* stage_ms, int* n_calls, double* gemm_flops_per_call) {
   if (!m || !stage_ms || !n_calls) return fail(VGE_ERR_ARG, "vge_dwpose_profile_read: bad argument");
-  for (int i = 0; i < 3; ++i) stage_ms[i] = 0;
-  for (size_t p = 0; p < (size_t)m->prof_calls * m->ev_per_call / 2; ++p) {
-    if (m->ev_kind[p] < 0) continue;
-    float t;
-    HIPCHK(hipEventSynchronize(m->ev[2 * p + 1]));
-    HIPCHK(hipEventElapsedTime(&t, m->ev[2 * p], m->ev[2 * p + 1]));
-    stage_ms[m->ev_kind[p]] += t;
-  }
-  *n_calls = m->prof_calls;
-  if (gemm_flops_per_call) *gemm_flops_per_call = m->prof_calls ? m->prof_flops / m->prof_calls : m->gemm_flops;
-  return VGE_OK;
+  const int rc = m->prof.read(stage_ms, 3, n_calls);
+  if (gemm_flops_per_call) *gemm_flops_per_call = m->prof.flops_per_call(m->gemm_flops);
+  return rc;
 }
 
 int vge_dwpose_keypoints(vge_dwpose* m, const uint8_t* frames, int F, int H, int W, const float* boxes,
@@ -420,37 +390,10 @@ int vge_dwpose_keypoints(vge_dwpose* m, const uint8_t* frames, int F, int H, int
   HIPCHK(hipMemcpyAsync(m->pinst, m->pin_p, N * sizeof(vge::PoseInst), hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(m->iof, m->pin_iof, (size_t)2 * F * sizeof(int), hipMemcpyHostToDevice, s));
   HIPCHK(hipEventRecord(m->staged, s));
-  const bool prof = m->prof_calls < m->prof_max;
-  size_t pair = prof ? (size_t)m->prof_calls * m->ev_per_call / 2 : 0;
-  auto beg = [&](int kind) -> int {
-    if (prof) {
-      m->ev_kind[pair] = kind;
-      HIPCHK(hipEventRecord(m->ev[2 * pair], s));
-    }
-    return VGE_OK;
-  };
-  auto end = [&]() -> int {
-    if (prof) HIPCHK(hipEventRecord(m->ev[2 * pair++ + 1], s));
-    return VGE_OK;
-  };
   m->gemm_flops = 0;
-  int rc;
-#define RC(x)                            \
-  do {                                   \
-    if ((rc = (x)) != VGE_OK) return rc; \
-  } while (0)
-#define CONV(...)            \
-  do {                       \
-    RC(beg(0));              \
-    RC(conv(m->cx(), __VA_ARGS__)); \
-    RC(end());               \
-  } while (0)
-#define OTHER(kind, expr) \
-  do {                    \
-    RC(beg(kind));        \
-    HIPCHK(expr);         \
-    RC(end());            \
-  } while (0)
+  m->prof.start_call();
+#define CONV(...) VGE_STAGE(m->prof, s, 0, conv(m->cx(), __VA_ARGS__))
+#define OTHER(kind, expr) VGE_STAGE(m->prof, s, kind, VGE_HIP(expr))
   OTHER(1, vge::launch_warp_prep(frames, H, W, m->winst, N, c.in_h, c.in_w, m->in, s));
   int h = c.in_h / 2, w = c.in_w / 2;
   const int s0 = c.stem_ch;
@@ -511,8 +454,7 @@ int vge_dwpose_keypoints(vge_dwpose* m, const uint8_t* frames, int F, int H, int
   OTHER(2, vge::launch_kp120(lv, m->pinst, m->iof, F, K, c.in_w, c.in_h, H, W, keypoints, s));
 #undef OTHER
 #undef CONV
-#undef RC
-  if (prof) ++m->prof_calls, m->prof_flops += m->gemm_flops;
+  m->prof.end_call(m->gemm_flops);
   return VGE_OK;
 }
 

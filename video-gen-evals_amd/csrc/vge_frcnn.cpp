@@ -5,15 +5,13 @@
 //   proposal selection / NMS / merge -> ROIAlignV2 -> fc1, fc2, predictor -> box inference + postprocess + gate count.
 #include <hip/hip_runtime.h>
 
-#include <memory>
-
 #include "../../include/vge_frcnn.h"
-#include "vge_cnn.h"
 #include "vge_cnn_host.h"
 #include "vge_frcnn_k.h"
 
-using namespace vge::cnnh;
+using namespace vge::host;
 #define HIPCHK VGE_HIPCHK
+#define RC VGE_RC
 
 #pragma clang fp contract(off)  // the FrozenBN fold in float32 as the oracle evaluates it
 
@@ -104,7 +102,7 @@ struct vge_frcnn {
   int ld_head = 0;
   void* zero = nullptr;
   // workspace for chunks of `chunk` frames of rH x rW
-  std::unique_ptr<DevAllocs> ws;
+  Workspace ws;
   int chunk = 0, rH = 0, rW = 0;
   int nh = 0, nw = 0, hp = 0, wp = 0, lh[5] = {0}, lw[5] = {0};
   int *xb = nullptr, *xk = nullptr, *yb = nullptr, *yk = nullptr, ksx = 0, ksy = 0;
@@ -392,10 +390,6 @@ int vge_frcnn_reserve(vge_frcnn* m, int chunk, int H, int W) {
       return fail(VGE_ERR_ARG, "vge_frcnn_reserve: chunk too large for " + std::to_string(H) + " x " + std::to_string(W) +
                                    " frames (at most " + std::to_string(((1ull << 31) - 1) / per) + ")");
   }
-  (void)hipDeviceSynchronize();  // the previous workspace (if any) is released only after its kernels completed
-  m->ws.reset();
-  m->ws = std::make_unique<DevAllocs>();
-  DevAllocs& d = *m->ws;
   m->chunk = 0;
   m->nh = sh[0];
   m->nw = sh[1];
@@ -405,18 +399,9 @@ int vge_frcnn_reserve(vge_frcnn* m, int chunk, int H, int W) {
     m->lh[l] = sh[4 + 2 * l];
     m->lw[l] = sh[5 + 2 * l];
   }
-  std::vector<int> b, k;
-  if (pil_coeffs(W, m->nw, b, k, m->ksx), !upload(d, b, &m->xb) || !upload(d, k, &m->xk))
-    return fail(VGE_ERR_NOMEM, "vge_frcnn_reserve: upload failed");
-  if (pil_coeffs(H, m->nh, b, k, m->ksy), !upload(d, b, &m->yb) || !upload(d, k, &m->yk))
-    return fail(VGE_ERR_NOMEM, "vge_frcnn_reserve: upload failed");
   const size_t N = chunk, s2 = (size_t)(m->hp / 2) * (m->wp / 2), s4 = (size_t)m->lh[0] * m->lw[0];
   const int w0 = m->c.groups * m->c.width_per_group, r2 = m->c.res2_ch, F = m->c.fpn_ch, P = m->c.rpn_post_topk;
-  struct Buf {
-    void** p;
-    size_t bytes;
-  };
-  std::vector<Buf> bufs = {
+  std::vector<Workspace::Buf> bufs = {
       {(void**)&m->tmp, N * H * m->nw * 3},
       {&m->in, N * m->hp * m->wp * 8 * 2},
       {&m->pool, N * s4 * m->c.stem_ch * 2},
@@ -443,12 +428,6 @@ int vge_frcnn_reserve(vge_frcnn* m, int chunk, int H, int W) {
     bufs.push_back({&m->P[l], N * px * F * 2});
     bufs.push_back({(void**)&m->RO[l], N * px * 16 * 4});
   }
-  for (const Buf& bf : bufs) {
-    void* p = d.dmalloc(bf.bytes);
-    if (!p) return fail(VGE_ERR_NOMEM, "vge_frcnn_reserve: hipMalloc failed");
-    HIPCHK(hipMemset(p, 0, bf.bytes));
-    *bf.p = p;
-  }
   // buffers whose lifetimes do not overlap share memory (-86 MB per 800-px frame, a quarter of the workspace): the
   // stem output (split-stem path only) lives before res2.0's conv1 writes T1; the FPN's upsampled top-down sum and
   // the RPN conv's output after the backbone, in the shortcut / grouped-conv buffers; the ROI features after the RPN,
@@ -456,23 +435,23 @@ int vge_frcnn_reserve(vge_frcnn* m, int chunk, int H, int W) {
   struct Alias {
     void** p;
     size_t bytes;
-    void* over;
+    void** over;
     size_t over_bytes;
   };
-  const Alias al[] = {{&m->stemo, N * s2 * m->c.stem_ch * 2, m->T1, N * s4 * 2 * w0 * 2},
-                      {&m->UP, N * s4 * F * 2, m->SC, N * s4 * r2 * 2},
-                      {&m->RT, N * s4 * F * 2, m->T2, N * s4 * w0 * 2},
-                      {&m->BOXF, N * P * 49 * F * 2, m->T1, N * s4 * 2 * w0 * 2}};
-  for (const Alias& a : al) {
-    if (a.bytes <= a.over_bytes) {
-      *a.p = a.over;
-      continue;
-    }
-    void* p = d.dmalloc(a.bytes);
-    if (!p) return fail(VGE_ERR_NOMEM, "vge_frcnn_reserve: hipMalloc failed");
-    HIPCHK(hipMemset(p, 0, a.bytes));
-    *a.p = p;
-  }
+  const Alias al[] = {{&m->stemo, N * s2 * m->c.stem_ch * 2, &m->T1, N * s4 * 2 * w0 * 2},
+                      {&m->UP, N * s4 * F * 2, &m->SC, N * s4 * r2 * 2},
+                      {&m->RT, N * s4 * F * 2, &m->T2, N * s4 * w0 * 2},
+                      {&m->BOXF, N * P * 49 * F * 2, &m->T1, N * s4 * 2 * w0 * 2}};
+  for (const Alias& a : al)
+    if (a.bytes > a.over_bytes) bufs.push_back({a.p, a.bytes});
+  RC(m->ws.reserve("vge_frcnn_reserve", bufs));
+  for (const Alias& a : al)
+    if (a.bytes <= a.over_bytes) *a.p = *a.over;
+  std::vector<int> b, k;
+  if (pil_coeffs(W, m->nw, b, k, m->ksx), !upload(m->ws.dev, b, &m->xb) || !upload(m->ws.dev, k, &m->xk))
+    return fail(VGE_ERR_NOMEM, "vge_frcnn_reserve: upload failed");
+  if (pil_coeffs(H, m->nh, b, k, m->ksy), !upload(m->ws.dev, b, &m->yb) || !upload(m->ws.dev, k, &m->yk))
+    return fail(VGE_ERR_NOMEM, "vge_frcnn_reserve: upload failed");
   m->chunk = chunk;
   m->rH = H;
   m->rW = W;
@@ -520,23 +499,8 @@ int vge_frcnn_detect(vge_frcnn* m, const uint8_t* frames, int F, int H, int W, f
   const int h4 = m->lh[0], w4 = m->lw[0];
   m->flops[0] = m->flops[1] = 0;
   m->prof.start_call();
-  int rc;
-#define RC(x)                            \
-  do {                                   \
-    if ((rc = (x)) != VGE_OK) return rc; \
-  } while (0)
-#define STAGE(k, expr)     \
-  do {                     \
-    RC(m->prof.beg(k, s)); \
-    RC(expr);              \
-    RC(m->prof.end(s));    \
-  } while (0)
-#define OTHER(expr)        \
-  do {                     \
-    RC(m->prof.beg(2, s)); \
-    HIPCHK(expr);          \
-    RC(m->prof.end(s));    \
-  } while (0)
+#define STAGE(k, expr) VGE_STAGE(m->prof, s, k, expr)
+#define OTHER(expr) STAGE(2, VGE_HIP(expr))
   vge::RpnLevels rl{};
   vge::RoiLevels ro{};
   for (int l = 0; l < 5; ++l) {
@@ -556,9 +520,8 @@ int vge_frcnn_detect(vge_frcnn* m, const uint8_t* frames, int F, int H, int W, f
                                           m->in, s));
     // ---- ResNeXt: stem, max pool, bottlenecks
     if (stem_fused(m->stem)) {  // the stem conv + ReLU + max pool in one kernel (no stem output in HBM)
-      RC(m->prof.beg(0, s));
-      HIPCHK(vge::launch_frcnn_stem_pool(m->in, m->stem.w, m->stem.Kp, m->stem.b, m->pool, n, m->hp, m->wp, s));
-      RC(m->prof.end(s));
+      STAGE(0, VGE_HIP(vge::launch_frcnn_stem_pool(m->in, m->stem.w, m->stem.Kp, m->stem.b, m->pool, n, m->hp, m->wp,
+                                                   s)));
       m->flops[0] += 2.0 * n * (m->hp / 2) * (m->wp / 2) * (double)m->stem.Cout * 49 * m->stem.Cinp;
     } else {
       STAGE(0, conv(m->cx(0), m->stem, m->in, 8, n, m->hp, m->wp, 2, m->stemo, c.stem_ch, s, 3));
@@ -694,7 +657,6 @@ int vge_frcnn_detect(vge_frcnn* m, const uint8_t* frames, int F, int H, int W, f
   }
 #undef OTHER
 #undef STAGE
-#undef RC
   m->prof.end_call(m->flops[0] + m->flops[1]);
   return VGE_OK;
 }

@@ -3,42 +3,19 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstring>
-#include <string>
-#include <unordered_map>
-#include <vector>
 
 #include "../../include/vge_hmr.h"
-#include "vge_error.h"
 #include "vge_gemm.h"
 #include "vge_hmr_k.h"
+#include "vge_model_host.h"
+
+using namespace vge::host;
+#define HIPCHK VGE_HIPCHK
+#define RC VGE_RC
 
 namespace {
 
-enum { GE_BF16 = 0, GE_GELU_BF16 = 1, GE_RES_F32 = 2, GE_PE_F32 = 3, GE_F32 = 4 };
 constexpr int NTOK = 192;  // 16 x 12 patches of the 256 x 192 backbone input (the attention kernel's tile)
-
-int fail(int code, const std::string& msg) {
-  vge::set_last_error(msg);
-  return code;
-}
-
-#define HIPCHK(expr)                                                                                    \
-  do {                                                                                                  \
-    hipError_t _e = (expr);                                                                             \
-    if (_e != hipSuccess) return fail(VGE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
-hipStream_t S(vge_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-int rup(int x, int a) { return (x + a - 1) / a * a; }
-
-uint16_t to_bf16(float f) {  // round to nearest even (torch .to(bfloat16))
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0;
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
 
 struct Lin {
   void* W = nullptr;     // bf16 [Npad][K]
@@ -65,62 +42,31 @@ struct DecLayer {
 
 struct vge_hmr {
   vge_hmr_config c{};
-  std::vector<void*> allocs;
+  DevAllocs dev;
   Lin pe;
   Vec pos, lnw, lnb, tok0, init_pose, init_betas;
   std::vector<VitBlock> blocks;
   std::vector<DecLayer> dec;
   Lin readout, cls, codebook, decoder;
-  // workspace
+  Workspace ws;
   int max_frames = 0;
   void *ape = nullptr, *h = nullptr, *qkv = nullptr, *ao = nullptr, *hid = nullptr;
   float* x = nullptr;
   float *xd = nullptr, *rd = nullptr, *logits = nullptr, *bp = nullptr;
   void *hd = nullptr, *qb = nullptr, *cab = nullptr, *hm = nullptr, *xdb = nullptr, *probs = nullptr, *qz = nullptr;
-  // profiling: event pairs around every launch of the backbone, by kind (0 GEMM, 1 attention, 2 LayerNorm /
-  // patchify), and one pair around the head (kind 3)
-  std::vector<hipEvent_t> ev;
-  std::vector<int> ev_kind;
-  int prof_max = 0, prof_calls = 0, ev_per_call = 0;
+  // event pairs around every launch of the backbone, by kind (0 GEMM, 1 attention, 2 LayerNorm / patchify), and one
+  // pair around the head (kind 3)
+  Profiler prof;
   double gemm_flops = 0;
-  ~vge_hmr() {
-    for (auto e : ev) (void)hipEventDestroy(e);
-    for (void* p : allocs) (void)hipFree(p);
-  }
-  void* dmalloc(size_t bytes) {
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
-    allocs.push_back(p);
-    return p;
-  }
 };
 
 namespace {
 
-struct WeightMap {
-  std::unordered_map<std::string, const vge_tensor_view*> m;
-  std::string missing, badshape;
-  const vge_tensor_view* get(const std::string& k, std::initializer_list<int64_t> shape) {
-    auto it = m.find(k);
-    if (it == m.end()) {
-      if (missing.empty()) missing = k;
-      return nullptr;
-    }
-    const vge_tensor_view* v = it->second;
-    bool ok = v->ndim == (int)shape.size() && v->data;
-    int i = 0;
-    for (int64_t s : shape) ok = ok && v->shape[i++] == s;
-    if (!ok && badshape.empty()) badshape = k;
-    return ok ? v : nullptr;
-  }
-};
-
 bool upload_f32(vge_hmr* m, const float* src, size_t n, size_t npad, Vec& out) {
   std::vector<float> h(npad, 0.f);
   if (src) memcpy(h.data(), src, n * 4);
-  out.p = static_cast<float*>(m->dmalloc(npad * 4));
   out.n = (int)n;
-  return out.p && hipMemcpy(out.p, h.data(), npad * 4, hipMemcpyHostToDevice) == hipSuccess;
+  return upload(m->dev, h, &out.p);
 }
 
 // W [N][K] f32 (row stride ldk, column offset k0) -> bf16 [Npad][K]; rows >= N zero
@@ -131,8 +77,9 @@ bool upload_lin(vge_hmr* m, const float* W, int N, int K, long ldk, const float*
   std::vector<uint16_t> h((size_t)L.Npad * K, 0);
   for (int n = 0; n < N; ++n)
     for (int k = 0; k < K; ++k) h[(size_t)n * K + k] = to_bf16(W[(size_t)n * ldk + k]);
-  L.W = m->dmalloc(h.size() * 2);
-  if (!L.W || hipMemcpy(L.W, h.data(), h.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return false;
+  uint16_t* dw = nullptr;
+  if (!upload(m->dev, h, &dw)) return false;
+  L.W = dw;
   Vec b;
   if (!upload_f32(m, bias, bias ? N : 0, L.Npad, b)) return false;
   L.b = b.p;
@@ -169,6 +116,41 @@ bool cfg_ok(const vge_hmr_config& c, std::string& why) {
   return true;
 }
 
+// SMPL token-decoder head over the backbone's context tokens m->h (rows = frames, padded to Fp)
+int head(vge_hmr* m, int F, float* pose, float* gori, float* betas, float* vit, hipStream_t s) {
+  const vge_hmr_config& c = m->c;
+  const int Mv = rup(F * NTOK, 256), Fp = rup(F, 256);
+  const int E = c.embed_dim, Dd = c.dec_dim, inner = c.dec_heads * 64;
+  HIPCHK(vge::launch_bcast_rows(m->tok0.p, m->xd, Fp, Dd, s));
+  for (int l = 0; l < c.dec_depth; ++l) {
+    const DecLayer& L = m->dec[l];
+    // self-attention over the single token: softmax over one key is 1, so it is to_out(v(LN(x)))
+    HIPCHK(vge::launch_ln_bf16(m->xd, Dd, m->hd, Dd, L.sa_nw.p, L.sa_nb.p, Fp, Dd, 1e-5f, s));
+    RC(gemm(vge::GEMM_BF16, m->hd, Dd, L.sa_v, m->qb, inner, Fp, s));
+    RC(gemm(vge::GEMM_RES_F32, m->qb, inner, L.sa_o, m->xd, Dd, Fp, s, m->xd, Dd));
+    // cross-attention to the 192 context tokens of the frame
+    HIPCHK(vge::launch_ln_bf16(m->xd, Dd, m->hd, Dd, L.ca_nw.p, L.ca_nb.p, Fp, Dd, 1e-5f, s));
+    RC(gemm(vge::GEMM_BF16, m->hd, Dd, L.ca_q, m->qb, inner, Fp, s));
+    RC(gemm(vge::GEMM_BF16, m->h, E, L.ca_kv, m->qkv, 2 * inner, Mv, s));
+    HIPCHK(vge::launch_xattn1(m->qb, inner, m->qkv, 2 * inner, m->cab, inner, F, inner, c.dec_heads, NTOK, s));
+    RC(gemm(vge::GEMM_RES_F32, m->cab, inner, L.ca_o, m->xd, Dd, Fp, s, m->xd, Dd));
+    // feed-forward
+    HIPCHK(vge::launch_ln_bf16(m->xd, Dd, m->hd, Dd, L.ff_nw.p, L.ff_nb.p, Fp, Dd, 1e-5f, s));
+    RC(gemm(vge::GEMM_GELU_BF16, m->hd, Dd, L.ff1, m->hm, c.dec_mlp, Fp, s));
+    RC(gemm(vge::GEMM_RES_F32, m->hm, c.dec_mlp, L.ff2, m->xd, Dd, Fp, s, m->xd, Dd));
+  }
+  HIPCHK(vge::launch_cast_bf16(m->xd, Dd, m->xdb, Dd, Fp, Dd, s));
+  RC(gemm(vge::GEMM_F32, m->xdb, Dd, m->readout, m->rd, 256, Fp, s));
+  const int NC = c.tok_num * c.tok_classes;
+  RC(gemm(vge::GEMM_F32, m->xdb, Dd, m->cls, m->logits, NC, Fp, s));
+  HIPCHK(vge::launch_softmax_rows(m->logits, m->probs, Fp * c.tok_num, c.tok_classes, s));
+  RC(gemm(vge::GEMM_BF16, m->probs, c.tok_classes, m->codebook, m->qz, c.tok_code_dim, Fp * c.tok_num, s));
+  RC(gemm(vge::GEMM_F32, m->qz, (long)c.tok_num * c.tok_code_dim, m->decoder, m->bp, 256, Fp, s));
+  HIPCHK(vge::launch_readout(m->rd, 256, m->bp, 256, m->init_pose.p, m->init_betas.p, pose, gori, betas, F, s));
+  HIPCHK(vge::launch_copy_rows(m->xd, Dd, vit, Dd, F, Dd, s));
+  return VGE_OK;
+}
+
 }  // namespace
 
 namespace {
@@ -184,9 +166,7 @@ int vge_hmr_create(const vge_hmr_config* cfg, const vge_tensor_view* weights, in
   if (!cfg_ok(*cfg, why)) return fail(VGE_ERR_ARG, "vge_hmr_create: unsupported config: " + why);
   HIPCHK(vge::vit_kernels_setup());
   const vge_hmr_config c = *cfg;
-  WeightMap wm;
-  for (int i = 0; i < n_weights; ++i)
-    if (weights[i].name) wm.m[weights[i].name] = &weights[i];
+  WeightMap wm(weights, n_weights);
   const int E = c.embed_dim, P = c.patch, T = NTOK, Dd = c.dec_dim, inner = c.dec_heads * 64;
   auto* m = new vge_hmr();
   m->c = c;
@@ -295,11 +275,8 @@ int vge_hmr_create(const vge_hmr_config* cfg, const vge_tensor_view* weights, in
   else
     ok = false;
   if (!ok) {
-    const std::string miss = wm.missing, bad = wm.badshape;
     delete m;
-    if (!miss.empty()) return fail(VGE_ERR_MISSING_WEIGHT, "vge_hmr_create: missing weight " + miss);
-    if (!bad.empty()) return fail(VGE_ERR_WEIGHT_SHAPE, "vge_hmr_create: wrong shape for " + bad);
-    return fail(VGE_ERR_HIP, "vge_hmr_create: device allocation / upload failed");
+    return wm.status("vge_hmr_create");
   }
   // algorithmic GEMM FLOPs of the backbone per frame (patch embed + per block qkv, proj, fc1, fc2)
   m->gemm_flops = 2.0 * T * ((double)E * 3 * P * P + c.depth * ((double)E * 3 * E + (double)E * E + 2.0 * E * c.mlp_dim));
@@ -314,8 +291,8 @@ int vge_hmr_reserve(vge_hmr* m, int max_frames) {
   const size_t Mv = rup(max_frames * NTOK, 256), Fp = rup(max_frames, 256);
   const size_t E = c.embed_dim, Dd = c.dec_dim, inner = c.dec_heads * 64;
   const size_t K0 = 3 * c.patch * c.patch;
-  struct B { void** p; size_t bytes; };
-  const B bufs[] = {
+  m->max_frames = 0;
+  RC(m->ws.reserve("vge_hmr_reserve", {
       {&m->ape, Mv * K0 * 2},
       {(void**)&m->x, Mv * E * 4},
       {&m->h, Mv * E * 2},
@@ -333,13 +310,7 @@ int vge_hmr_reserve(vge_hmr* m, int max_frames) {
       {&m->probs, Fp * c.tok_num * c.tok_classes * 2},
       {&m->qz, Fp * c.tok_num * c.tok_code_dim * 2},
       {(void**)&m->bp, Fp * 256 * 4},
-  };
-  for (const B& b : bufs) {
-    void* p = m->dmalloc(b.bytes);
-    if (!p) return fail(VGE_ERR_NOMEM, "vge_hmr_reserve: hipMalloc failed");
-    HIPCHK(hipMemset(p, 0, b.bytes));  // pad rows stay finite
-    *b.p = p;
-  }
+  }));
   m->max_frames = max_frames;
   return VGE_OK;
 }
@@ -351,29 +322,14 @@ int vge_hmr_destroy(vge_hmr* m) {
 
 int vge_hmr_profile_begin(vge_hmr* m, int max_calls) {
   if (!m || max_calls < 0) return fail(VGE_ERR_ARG, "vge_hmr_profile_begin: bad argument");
-  for (auto e : m->ev) (void)hipEventDestroy(e);
-  m->ev_per_call = 2 * (2 + 7 * m->c.depth + 2);
-  m->ev.assign((size_t)max_calls * m->ev_per_call, nullptr);
-  m->ev_kind.assign((size_t)max_calls * m->ev_per_call / 2, -1);
-  for (auto& e : m->ev) HIPCHK(hipEventCreate(&e));
-  m->prof_max = max_calls;
-  m->prof_calls = 0;
-  return VGE_OK;
+  return m->prof.begin(max_calls, 2 + 7 * m->c.depth + 2);  // the STAGEs of vge_hmr_extract
 }
 
 int vge_hmr_profile_read(vge_hmr* m, double* stage_ms, int* n_calls, double* gemm_flops_per_call) {
   if (!m || !stage_ms || !n_calls) return fail(VGE_ERR_ARG, "vge_hmr_profile_read: bad argument");
-  for (int i = 0; i < 4; ++i) stage_ms[i] = 0;
-  for (size_t p = 0; p < (size_t)m->prof_calls * m->ev_per_call / 2; ++p) {
-    if (m->ev_kind[p] < 0) continue;
-    float t;
-    HIPCHK(hipEventSynchronize(m->ev[2 * p + 1]));
-    HIPCHK(hipEventElapsedTime(&t, m->ev[2 * p], m->ev[2 * p + 1]));
-    stage_ms[m->ev_kind[p]] += t;
-  }
-  *n_calls = m->prof_calls;
+  const int rc = m->prof.read(stage_ms, 4, n_calls);
   if (gemm_flops_per_call) *gemm_flops_per_call = m->gemm_flops;
-  return VGE_OK;
+  return rc;
 }
 
 int vge_hmr_crop(const uint8_t* frames, int n_frames, int H, int W, const float* boxes, const int32_t* frame_of,
@@ -402,93 +358,28 @@ int vge_hmr_extract(vge_hmr* m, const uint8_t* frames, int F, float* pose, float
   if (F > m->max_frames) return fail(VGE_ERR_WORKSPACE, "vge_hmr_extract: call vge_hmr_reserve(>= n_frames) first");
   const vge_hmr_config& c = m->c;
   hipStream_t s = S(stream);
-  const int Mv = rup(F * NTOK, 256), Fp = rup(F, 256);
-  const int E = c.embed_dim, Dd = c.dec_dim, inner = c.dec_heads * 64, K0 = 3 * c.patch * c.patch;
-  const bool prof = m->prof_calls < m->prof_max;
-  size_t pair = prof ? (size_t)m->prof_calls * m->ev_per_call / 2 : 0;
-  auto beg = [&](int kind) -> int {
-    if (prof) {
-      m->ev_kind[pair] = kind;
-      HIPCHK(hipEventRecord(m->ev[2 * pair], s));
-    }
-    return VGE_OK;
-  };
-  auto end = [&]() -> int {
-    if (prof) HIPCHK(hipEventRecord(m->ev[2 * pair++ + 1], s));
-    return VGE_OK;
-  };
-  int rc;
-#define RC(x)                       \
-  do {                              \
-    if ((rc = (x)) != VGE_OK) return rc; \
-  } while (0)
+  const int Mv = rup(F * NTOK, 256);
+  const int E = c.embed_dim, K0 = 3 * c.patch * c.patch;
+  m->prof.start_call();
+#define STAGE(kind, expr) VGE_STAGE(m->prof, s, kind, expr)
   static const float mean[3] = {123.675f, 116.28f, 103.53f}, stdv[3] = {58.395f, 57.12f, 57.375f};
-  RC(beg(2));
-  HIPCHK(vge::launch_patchify(frames, F, c.in_h, c.in_w, (c.in_w - c.img_w) / 2, c.img_h, c.img_w, c.patch, c.pad, 16,
-                              12, mean, stdv, m->ape, s));
-  RC(end());
-  RC(beg(0));
-  RC(gemm(GE_PE_F32, m->ape, K0, m->pe, m->x, E, Mv, s, nullptr, 0, m->pos.p, NTOK));
-  RC(end());
+  STAGE(2, VGE_HIP(vge::launch_patchify(frames, F, c.in_h, c.in_w, (c.in_w - c.img_w) / 2, c.img_h, c.img_w, c.patch,
+                                        c.pad, 16, 12, mean, stdv, m->ape, s)));
+  STAGE(0, gemm(vge::GEMM_PE_F32, m->ape, K0, m->pe, m->x, E, Mv, s, nullptr, 0, m->pos.p, NTOK));
   for (int i = 0; i < c.depth; ++i) {
     const VitBlock& B = m->blocks[i];
-    RC(beg(2));
-    HIPCHK(vge::launch_ln_bf16(m->x, E, m->h, E, B.n1w.p, B.n1b.p, Mv, E, 1e-6f, s));
-    RC(end());
-    RC(beg(0));
-    RC(gemm(GE_BF16, m->h, E, B.qkv, m->qkv, 3 * E, Mv, s));
-    RC(end());
-    RC(beg(1));
-    HIPCHK(vge::launch_vit_attn(m->qkv, 3 * E, m->ao, E, F, E, c.heads, E / c.heads, s));
-    RC(end());
-    RC(beg(0));
-    RC(gemm(GE_RES_F32, m->ao, E, B.proj, m->x, E, Mv, s, m->x, E));
-    RC(end());
-    RC(beg(2));
-    HIPCHK(vge::launch_ln_bf16(m->x, E, m->h, E, B.n2w.p, B.n2b.p, Mv, E, 1e-6f, s));
-    RC(end());
-    RC(beg(0));
-    RC(gemm(GE_GELU_BF16, m->h, E, B.fc1, m->hid, c.mlp_dim, Mv, s));
-    RC(end());
-    RC(beg(0));
-    RC(gemm(GE_RES_F32, m->hid, c.mlp_dim, B.fc2, m->x, E, Mv, s, m->x, E));
-    RC(end());
+    STAGE(2, VGE_HIP(vge::launch_ln_bf16(m->x, E, m->h, E, B.n1w.p, B.n1b.p, Mv, E, 1e-6f, s)));
+    STAGE(0, gemm(vge::GEMM_BF16, m->h, E, B.qkv, m->qkv, 3 * E, Mv, s));
+    STAGE(1, VGE_HIP(vge::launch_vit_attn(m->qkv, 3 * E, m->ao, E, F, E, c.heads, E / c.heads, s)));
+    STAGE(0, gemm(vge::GEMM_RES_F32, m->ao, E, B.proj, m->x, E, Mv, s, m->x, E));
+    STAGE(2, VGE_HIP(vge::launch_ln_bf16(m->x, E, m->h, E, B.n2w.p, B.n2b.p, Mv, E, 1e-6f, s)));
+    STAGE(0, gemm(vge::GEMM_GELU_BF16, m->h, E, B.fc1, m->hid, c.mlp_dim, Mv, s));
+    STAGE(0, gemm(vge::GEMM_RES_F32, m->hid, c.mlp_dim, B.fc2, m->x, E, Mv, s, m->x, E));
   }
-  RC(beg(2));
-  HIPCHK(vge::launch_ln_bf16(m->x, E, m->h, E, m->lnw.p, m->lnb.p, Mv, E, 1e-6f, s));  // context tokens
-  RC(end());
-  RC(beg(3));
-  // ---- SMPL token-decoder head (rows = frames, padded to Fp)
-  HIPCHK(vge::launch_bcast_rows(m->tok0.p, m->xd, Fp, Dd, s));
-  for (int l = 0; l < c.dec_depth; ++l) {
-    const DecLayer& L = m->dec[l];
-    // self-attention over the single token: softmax over one key is 1, so it is to_out(v(LN(x)))
-    HIPCHK(vge::launch_ln_bf16(m->xd, Dd, m->hd, Dd, L.sa_nw.p, L.sa_nb.p, Fp, Dd, 1e-5f, s));
-    RC(gemm(GE_BF16, m->hd, Dd, L.sa_v, m->qb, inner, Fp, s));
-    RC(gemm(GE_RES_F32, m->qb, inner, L.sa_o, m->xd, Dd, Fp, s, m->xd, Dd));
-    // cross-attention to the 192 context tokens of the frame
-    HIPCHK(vge::launch_ln_bf16(m->xd, Dd, m->hd, Dd, L.ca_nw.p, L.ca_nb.p, Fp, Dd, 1e-5f, s));
-    RC(gemm(GE_BF16, m->hd, Dd, L.ca_q, m->qb, inner, Fp, s));
-    RC(gemm(GE_BF16, m->h, E, L.ca_kv, m->qkv, 2 * inner, Mv, s));
-    HIPCHK(vge::launch_xattn1(m->qb, inner, m->qkv, 2 * inner, m->cab, inner, F, inner, c.dec_heads, NTOK, s));
-    RC(gemm(GE_RES_F32, m->cab, inner, L.ca_o, m->xd, Dd, Fp, s, m->xd, Dd));
-    // feed-forward
-    HIPCHK(vge::launch_ln_bf16(m->xd, Dd, m->hd, Dd, L.ff_nw.p, L.ff_nb.p, Fp, Dd, 1e-5f, s));
-    RC(gemm(GE_GELU_BF16, m->hd, Dd, L.ff1, m->hm, c.dec_mlp, Fp, s));
-    RC(gemm(GE_RES_F32, m->hm, c.dec_mlp, L.ff2, m->xd, Dd, Fp, s, m->xd, Dd));
-  }
-  HIPCHK(vge::launch_cast_bf16(m->xd, Dd, m->xdb, Dd, Fp, Dd, s));
-  RC(gemm(GE_F32, m->xdb, Dd, m->readout, m->rd, 256, Fp, s));
-  const int NC = c.tok_num * c.tok_classes;
-  RC(gemm(GE_F32, m->xdb, Dd, m->cls, m->logits, NC, Fp, s));
-  HIPCHK(vge::launch_softmax_rows(m->logits, m->probs, Fp * c.tok_num, c.tok_classes, s));
-  RC(gemm(GE_BF16, m->probs, c.tok_classes, m->codebook, m->qz, c.tok_code_dim, Fp * c.tok_num, s));
-  RC(gemm(GE_F32, m->qz, (long)c.tok_num * c.tok_code_dim, m->decoder, m->bp, 256, Fp, s));
-  HIPCHK(vge::launch_readout(m->rd, 256, m->bp, 256, m->init_pose.p, m->init_betas.p, pose, gori, betas, F, s));
-  HIPCHK(vge::launch_copy_rows(m->xd, Dd, vit, Dd, F, Dd, s));
-  RC(end());
-#undef RC
-  if (prof) ++m->prof_calls;
+  STAGE(2, VGE_HIP(vge::launch_ln_bf16(m->x, E, m->h, E, m->lnw.p, m->lnb.p, Mv, E, 1e-6f, s)));  // context tokens
+  STAGE(3, head(m, F, pose, gori, betas, vit, s));
+#undef STAGE
+  m->prof.end_call(0);
   return VGE_OK;
 }
 
@@ -497,8 +388,8 @@ int vge_op_gemm_bf16(int epi, const void* A, long lda, const void* W, long ldw, 
                      const float* res, long ldr, const float* pos, int tokens, int M, int N, int K,
                      vge_stream_t stream) {
   if (epi < 0 || epi > 4 || !A || !W || !out || M <= 0 || N <= 0 || K <= 0 || M % 256 || N % 256 || K % 64 ||
-      lda % 8 || ldw % 8 || lda < K || ldw < K || ldo < N || (epi == GE_RES_F32 && (!res || ldr < N)) ||
-      (epi == GE_PE_F32 && (!pos || tokens <= 0)))
+      lda % 8 || ldw % 8 || lda < K || ldw < K || ldo < N || (epi == vge::GEMM_RES_F32 && (!res || ldr < N)) ||
+      (epi == vge::GEMM_PE_F32 && (!pos || tokens <= 0)))
     return fail(VGE_ERR_ARG, "vge_op_gemm_bf16: unsupported shape / arguments");
   HIPCHK(vge::vit_kernels_setup());
   vge::GemmBf16 g{A, lda, W, ldw, out, ldo, bias, res, ldr, pos, tokens, M, N, K};
@@ -509,7 +400,7 @@ int vge_op_gemm_bf16(int epi, const void* A, long lda, const void* W, long ldw, 
 int vge_op_gemm_lib(int epi, const void* A, long lda, const void* W, long ldw, void* out, long ldo, const float* bias,
                     const float* res, long ldr, int M, int N, int K, vge_stream_t stream) {
   if (epi < 0 || epi > 4 || !A || !W || !out || M <= 0 || N <= 0 || K <= 0 || lda < K || ldw < K || ldo < N ||
-      (epi == GE_RES_F32 && (!res || ldr < N)))
+      (epi == vge::GEMM_RES_F32 && (!res || ldr < N)))
     return fail(VGE_ERR_ARG, "vge_op_gemm_lib: unsupported shape / arguments");
   if (!vge::gemm_lib_ok(epi)) return fail(VGE_ERR_UNSUPPORTED, "vge_op_gemm_lib: epilogue not on the library path");
   vge::GemmBf16 g{A, lda, W, ldw, out, ldo, bias, res, ldr, nullptr, 1, M, N, K};

@@ -49,21 +49,18 @@ constexpr int GB_M = 256, GB_N = 256, GB_K = 32, GB_ST = 5, GB_GM = 8;
 constexpr int GB_TILE = GB_M * GB_K * 2;      // 16 KB per operand per stage
 constexpr int GB_LDS = GB_ST * 2 * GB_TILE;   // 160 KB
 
-enum GemmEpi {  // = vge::GemmEpiPublic (vge_gemm.h)
-  GE_BF16 = 0, GE_GELU_BF16 = 1, GE_RES_F32 = 2, GE_PE_F32 = 3, GE_F32 = 4,
-  GE_RELU_BF16 = 5, GE_RESB_BF16 = 6, GE_RESB_RELU_BF16 = 7  // the 1x1 conv epilogues (bias, bf16 residual, ReLU)
-};
+using namespace vge;  // the epilogue ids GEMM_* (vge_gemm.h)
 
 struct GemmBf16Args {
   const bf16* A;     // [M][lda]   rows of the activation
   const bf16* W;     // [N][ldw]   nn.Linear weight (row n = output column n)
   void* out;         // [M][ldo]   bf16 or f32
   const float* bias; // [N] or null
-  const float* res;  // GE_RES_F32: [M][ldr] residual (may alias out)
-  const float* pos;  // GE_PE_F32: pos_embed [tokens + 1][N]
+  const float* res;  // GEMM_RES_F32: [M][ldr] residual (may alias out)
+  const float* pos;  // GEMM_PE_F32: pos_embed [tokens + 1][N]
   long lda, ldw, ldo, ldr;
   int M, N, K, tokens;
-  const bf16* resb;  // GE_RESB_*: bf16 residual [M][ldr]
+  const bf16* resb;  // GEMM_RESB_*: bf16 residual [M][ldr]
 };
 
 // Stage a 256-row x 32-k operand tile (64-B rows) with NW waves: wave-instruction q (0..15) fills LDS bytes
@@ -252,23 +249,23 @@ __global__ void __launch_bounds__(64 * NW, 1) gemm_bf16_kernel(GemmBf16Args g) {
   const int gcol = n0 + wn * WC + c4;
   floatx4 bb = {0.f, 0.f, 0.f, 0.f};
   if (g.bias) bb = *reinterpret_cast<const floatx4*>(g.bias + gcol);
-  if constexpr (EPI == GE_PE_F32) bb += *reinterpret_cast<const floatx4*>(g.pos + gcol);  // pos_embed[:, :1]
+  if constexpr (EPI == GEMM_PE_F32) bb += *reinterpret_cast<const floatx4*>(g.pos + gcol);  // pos_embed[:, :1]
   // f32 epilogues read one row vector per output (residual or position embedding): every load of a half is issued
   // before that half's LDS round trip, and the next half's while this one is written, so the epilogue pays about one
   // memory latency instead of one per 4-iteration batch
   constexpr int NIT = 64 / RPI;                          // row-major iterations per half
-  constexpr bool RB = EPI == GE_RESB_BF16 || EPI == GE_RESB_RELU_BF16;
-  constexpr bool LD = EPI == GE_RES_F32 || EPI == GE_PE_F32 || RB;
+  constexpr bool RB = EPI == GEMM_RESB_BF16 || EPI == GEMM_RESB_RELU_BF16;
+  constexpr bool LD = EPI == GEMM_RES_F32 || EPI == GEMM_PE_F32 || RB;
   constexpr int NPF = LD ? (NIT > 16 ? 16 : NIT) : 1;    // loads kept in flight (NW = 4: 16 of 32 per half)
   auto grow_of = [&](int half, int it) { return m0 + wm * 128 + half * 64 + it * RPI + lr; };
   auto rowload = [&](int half, int it) -> floatx4 {
     const int grow = PM ? min(grow_of(half, it), g.M - 1) : grow_of(half, it);  // (PM: rows past M are not stored)
-    if constexpr (EPI == GE_RES_F32) return *reinterpret_cast<const floatx4*>(g.res + ((long)grow * g.ldr + gcol));
+    if constexpr (EPI == GEMM_RES_F32) return *reinterpret_cast<const floatx4*>(g.res + ((long)grow * g.ldr + gcol));
     if constexpr (RB) {
       const bf16x4 r = *reinterpret_cast<const bf16x4*>(g.resb + ((long)grow * g.ldr + gcol));
       return floatx4{(float)r[0], (float)r[1], (float)r[2], (float)r[3]};
     }
-    if constexpr (EPI == GE_PE_F32)  // tokens per frame = 192 (checked by the host)
+    if constexpr (EPI == GEMM_PE_F32)  // tokens per frame = 192 (checked by the host)
       return *reinterpret_cast<const floatx4*>(g.pos + ((1 + grow - (grow / 192) * 192) * g.N + gcol));
     return floatx4{0.f, 0.f, 0.f, 0.f};
   };
@@ -302,18 +299,18 @@ __global__ void __launch_bounds__(64 * NW, 1) gemm_bf16_kernel(GemmBf16Args g) {
       const int grow = grow_of(half, it);
       floatx4 v = *reinterpret_cast<const floatx4*>(my + rl * WC + c4) + bb;
       const long o = (long)grow * g.ldo + gcol;  // 64-bit: a 1x1 conv's output may pass 2^31 elements
-      if constexpr (RB || EPI == GE_RELU_BF16) {  // the 1x1 conv epilogues: bias (+ bf16 residual) (+ ReLU) -> bf16
+      if constexpr (RB || EPI == GEMM_RELU_BF16) {  // the 1x1 conv epilogues: bias (+ bf16 residual) (+ ReLU) -> bf16
         if constexpr (RB) {
           v += (it < NPF) ? rr[it % NPF] : rowload(half, it);
           if (it < NPF && half == 0) rr[it % NPF] = rowload(1, it);
         }
-        if constexpr (EPI == GE_RELU_BF16 || EPI == GE_RESB_RELU_BF16)
+        if constexpr (EPI == GEMM_RELU_BF16 || EPI == GEMM_RESB_RELU_BF16)
           v = floatx4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
         bf16x4 ob;
         ob[0] = (bf16)v.x; ob[1] = (bf16)v.y; ob[2] = (bf16)v.z; ob[3] = (bf16)v.w;
         if (!PM || grow < g.M) *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16*>(g.out) + o) = ob;
-      } else if constexpr (EPI == GE_BF16 || EPI == GE_GELU_BF16) {
-        if constexpr (EPI == GE_GELU_BF16) {  // exact-erf GELU: the one-exp2 form (|error| < 4.8e-7) flips enough
+      } else if constexpr (EPI == GEMM_BF16 || EPI == GEMM_GELU_BF16) {
+        if constexpr (EPI == GEMM_GELU_BF16) {  // exact-erf GELU: the one-exp2 form (|error| < 4.8e-7) flips enough
           floatx2 y[2] = {{v.x, v.y}, {v.z, v.w}};  // bf16 roundings to move TokenHMR's global_orient past the e2e
           gelu2_many(y);                              // chain's 1.5e-2 bound vs the bf16-point oracle (1.68e-2, r04 box)
           v = {y[0].x, y[0].y, y[1].x, y[1].y};
@@ -345,7 +342,7 @@ __global__ void __launch_bounds__(64 * NW, 1) gemm_bf16_kernel(GemmBf16Args g) {
 // NCL loads be outstanding and the epilogue retires them at 2 LPS; the epilogue's NST stores follow the next tile's
 // stage 3, so that tile's steps 0..2 let them be outstanding too.  Stores go through a per-tile buffer descriptor
 // (rows past M fall outside it and are dropped): one store instruction per (row tile, column tile) on every path,
-// which the counts rely on.  Residual-free bf16 epilogues only (GE_BF16, GE_GELU_BF16, GE_RELU_BF16), a bias, K / 32
+// which the counts rely on.  Residual-free bf16 epilogues only (GEMM_BF16, GEMM_GELU_BF16, GEMM_RELU_BF16), a bias, K / 32
 // >= 6 (so the bias and store windows of a tile never meet).
 constexpr int GP_LPS = 4;   // global_load_lds per thread per stage (2 A + 2 W)
 constexpr int GP_NST = 32;  // epilogue stores per thread: 8 row tiles x 4 column tiles of 16 x 16
@@ -378,7 +375,7 @@ __device__ __forceinline__ floatx4 gp_quad_t4(floatx4 v, bool o1, bool o2) {
 
 template <int EPI, bool PM>
 __global__ void __launch_bounds__(512, 1) gemmp_bf16_kernel(GemmBf16Args g) {
-  static_assert(EPI == GE_BF16 || EPI == GE_GELU_BF16 || EPI == GE_RELU_BF16, "residual-free bf16 epilogues");
+  static_assert(EPI == GEMM_BF16 || EPI == GEMM_GELU_BF16 || EPI == GEMM_RELU_BF16, "residual-free bf16 epilogues");
   constexpr int LPS = GP_LPS;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -503,8 +500,8 @@ __global__ void __launch_bounds__(512, 1) gemmp_bf16_kernel(GemmBf16Args g) {
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         floatx4 v = acq[t][u] + bb[u];
-        if constexpr (EPI == GE_RELU_BF16) v = floatx4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
-        if constexpr (EPI == GE_GELU_BF16) {
+        if constexpr (EPI == GEMM_RELU_BF16) v = floatx4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
+        if constexpr (EPI == GEMM_GELU_BF16) {
           floatx2 y[2] = {{v.x, v.y}, {v.z, v.w}};
           gelu2_many(y);
           v = floatx4{y[0].x, y[0].y, y[1].x, y[1].y};
@@ -665,8 +662,8 @@ __global__ void __launch_bounds__(256, 2) gemm2_bf16_kernel(GemmBf16Args g) {
   // ---- epilogue from the registers: lane -> row m0 + 64 wm + 32 t + (lane & 31), columns nb .. nb + 3 of group g;
   // UB column tiles per batch (every load of a batch in flight together; the position-embedding epilogue, with two
   // row vectors per output, takes one tile at a time to stay inside 256 registers)
-  constexpr bool RB = EPI == GE_RESB_BF16 || EPI == GE_RESB_RELU_BF16;
-  constexpr int UB = EPI == GE_PE_F32 ? 1 : 4;
+  constexpr bool RB = EPI == GEMM_RESB_BF16 || EPI == GEMM_RESB_RELU_BF16;
+  constexpr int UB = EPI == GEMM_PE_F32 ? 1 : 4;
   const int cb = n0 + wn * 128 + 4 * h;
   // (one branch on the bias pointer around the whole epilogue: a per-load test makes hipcc branch and drain vmcnt
   // around every load)
@@ -694,17 +691,17 @@ __global__ void __launch_bounds__(256, 2) gemm2_bf16_kernel(GemmBf16Args g) {
           const int c = cb + (u0 + u) * 32 + 8 * q;
           floatx4 bb = {0.f, 0.f, 0.f, 0.f};
           if constexpr (HB) bb = *reinterpret_cast<const floatx4*>(g.bias + c);
-          if constexpr (EPI == GE_PE_F32) bb += *reinterpret_cast<const floatx4*>(g.pos + c);
+          if constexpr (EPI == GEMM_PE_F32) bb += *reinterpret_cast<const floatx4*>(g.pos + c);
           v[u][q] += bb;
         }
-      if constexpr (EPI == GE_PE_F32) {  // tokens per frame = 192 (checked by the host)
+      if constexpr (EPI == GEMM_PE_F32) {  // tokens per frame = 192 (checked by the host)
         const float* pr = g.pos + (long)(1 + lrow - (lrow / 192) * 192) * g.N + cb;
 #pragma unroll
         for (int u = 0; u < UB; ++u)
 #pragma unroll
           for (int q = 0; q < 4; ++q) v[u][q] += *reinterpret_cast<const floatx4*>(pr + (u0 + u) * 32 + 8 * q);
       }
-      if constexpr (EPI == GE_RES_F32) {
+      if constexpr (EPI == GEMM_RES_F32) {
         const float* rr = g.res + (long)lrow * g.ldr + cb;
         floatx4 rv[UB][4];
 #pragma unroll
@@ -729,7 +726,7 @@ __global__ void __launch_bounds__(256, 2) gemm2_bf16_kernel(GemmBf16Args g) {
           for (int q = 0; q < 4; ++q)
             v[u][q] += floatx4{(float)rv[u][q][0], (float)rv[u][q][1], (float)rv[u][q][2], (float)rv[u][q][3]};
       }
-      if constexpr (EPI == GE_RELU_BF16 || EPI == GE_RESB_RELU_BF16) {
+      if constexpr (EPI == GEMM_RELU_BF16 || EPI == GEMM_RESB_RELU_BF16) {
 #pragma unroll
         for (int u = 0; u < UB; ++u)
 #pragma unroll
@@ -737,7 +734,7 @@ __global__ void __launch_bounds__(256, 2) gemm2_bf16_kernel(GemmBf16Args g) {
             v[u][q] = floatx4{fmaxf(v[u][q].x, 0.f), fmaxf(v[u][q].y, 0.f), fmaxf(v[u][q].z, 0.f),
                               fmaxf(v[u][q].w, 0.f)};
       }
-      if constexpr (EPI == GE_GELU_BF16) {
+      if constexpr (EPI == GEMM_GELU_BF16) {
 #pragma unroll
         for (int u = 0; u < UB; ++u) {
           floatx2 y[8];
@@ -752,7 +749,7 @@ __global__ void __launch_bounds__(256, 2) gemm2_bf16_kernel(GemmBf16Args g) {
         }
       }
       if (st_ok) {
-        if constexpr (EPI == GE_RES_F32 || EPI == GE_PE_F32 || EPI == GE_F32) {
+        if constexpr (EPI == GEMM_RES_F32 || EPI == GEMM_PE_F32 || EPI == GEMM_F32) {
           float* o = reinterpret_cast<float*>(g.out) + (long)row * g.ldo + cb;
 #pragma unroll
           for (int u = 0; u < UB; ++u)
@@ -1106,16 +1103,13 @@ __global__ void copy_rows_kernel(const float* __restrict__ x, long ldx, float* _
 // ================================================================================== host launchers
 namespace vge {
 
-static_assert((int)GE_RESB_RELU_BF16 == (int)GEMM_RESB_RELU_BF16 && (int)GE_RELU_BF16 == (int)GEMM_RELU_BF16,
-              "epilogue ids (vge_gemm.h)");
-
 template <int NW, int SH = 0>
 hipError_t gemm_setup_nw() {
-  const void* ks[8] = {(const void*)gemm_bf16_kernel<GE_BF16, NW, SH>, (const void*)gemm_bf16_kernel<GE_GELU_BF16, NW, SH>,
-                       (const void*)gemm_bf16_kernel<GE_RES_F32, NW, SH>, (const void*)gemm_bf16_kernel<GE_PE_F32, NW, SH>,
-                       (const void*)gemm_bf16_kernel<GE_F32, NW, SH>, (const void*)gemm_bf16_kernel<GE_RELU_BF16, NW, SH>,
-                       (const void*)gemm_bf16_kernel<GE_RESB_BF16, NW, SH>,
-                       (const void*)gemm_bf16_kernel<GE_RESB_RELU_BF16, NW, SH>};
+  const void* ks[8] = {(const void*)gemm_bf16_kernel<GEMM_BF16, NW, SH>, (const void*)gemm_bf16_kernel<GEMM_GELU_BF16, NW, SH>,
+                       (const void*)gemm_bf16_kernel<GEMM_RES_F32, NW, SH>, (const void*)gemm_bf16_kernel<GEMM_PE_F32, NW, SH>,
+                       (const void*)gemm_bf16_kernel<GEMM_F32, NW, SH>, (const void*)gemm_bf16_kernel<GEMM_RELU_BF16, NW, SH>,
+                       (const void*)gemm_bf16_kernel<GEMM_RESB_BF16, NW, SH>,
+                       (const void*)gemm_bf16_kernel<GEMM_RESB_RELU_BF16, NW, SH>};
   for (auto k : ks) {
     hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, GB_LDS);
     if (e != hipSuccess) return e;
@@ -1125,14 +1119,14 @@ hipError_t gemm_setup_nw() {
 
 template <int SH>
 hipError_t gemm_setup_pm() {  // the partial-M kernels (8 waves): 1x1 convs over n x H x W rows
-  const void* ks[8] = {(const void*)gemm_bf16_kernel<GE_BF16, 8, SH, true>,
-                       (const void*)gemm_bf16_kernel<GE_GELU_BF16, 8, SH, true>,
-                       (const void*)gemm_bf16_kernel<GE_RES_F32, 8, SH, true>,
-                       (const void*)gemm_bf16_kernel<GE_PE_F32, 8, SH, true>,
-                       (const void*)gemm_bf16_kernel<GE_F32, 8, SH, true>,
-                       (const void*)gemm_bf16_kernel<GE_RELU_BF16, 8, SH, true>,
-                       (const void*)gemm_bf16_kernel<GE_RESB_BF16, 8, SH, true>,
-                       (const void*)gemm_bf16_kernel<GE_RESB_RELU_BF16, 8, SH, true>};
+  const void* ks[8] = {(const void*)gemm_bf16_kernel<GEMM_BF16, 8, SH, true>,
+                       (const void*)gemm_bf16_kernel<GEMM_GELU_BF16, 8, SH, true>,
+                       (const void*)gemm_bf16_kernel<GEMM_RES_F32, 8, SH, true>,
+                       (const void*)gemm_bf16_kernel<GEMM_PE_F32, 8, SH, true>,
+                       (const void*)gemm_bf16_kernel<GEMM_F32, 8, SH, true>,
+                       (const void*)gemm_bf16_kernel<GEMM_RELU_BF16, 8, SH, true>,
+                       (const void*)gemm_bf16_kernel<GEMM_RESB_BF16, 8, SH, true>,
+                       (const void*)gemm_bf16_kernel<GEMM_RESB_RELU_BF16, 8, SH, true>};
   for (auto k : ks) {
     hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, GB_LDS);
     if (e != hipSuccess) return e;
@@ -1142,8 +1136,8 @@ hipError_t gemm_setup_pm() {  // the partial-M kernels (8 waves): 1x1 convs over
 
 template <bool PM>
 hipError_t gemmp_setup() {
-  const void* ks[3] = {(const void*)gemmp_bf16_kernel<GE_BF16, PM>, (const void*)gemmp_bf16_kernel<GE_GELU_BF16, PM>,
-                       (const void*)gemmp_bf16_kernel<GE_RELU_BF16, PM>};
+  const void* ks[3] = {(const void*)gemmp_bf16_kernel<GEMM_BF16, PM>, (const void*)gemmp_bf16_kernel<GEMM_GELU_BF16, PM>,
+                       (const void*)gemmp_bf16_kernel<GEMM_RELU_BF16, PM>};
   for (auto k : ks) {
     hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, GB_LDS);
     if (e != hipSuccess) return e;
@@ -1153,11 +1147,11 @@ hipError_t gemmp_setup() {
 
 template <bool PM>
 hipError_t gemm2_setup() {
-  const void* ks[8] = {(const void*)gemm2_bf16_kernel<GE_BF16, PM>, (const void*)gemm2_bf16_kernel<GE_GELU_BF16, PM>,
-                       (const void*)gemm2_bf16_kernel<GE_RES_F32, PM>, (const void*)gemm2_bf16_kernel<GE_PE_F32, PM>,
-                       (const void*)gemm2_bf16_kernel<GE_F32, PM>, (const void*)gemm2_bf16_kernel<GE_RELU_BF16, PM>,
-                       (const void*)gemm2_bf16_kernel<GE_RESB_BF16, PM>,
-                       (const void*)gemm2_bf16_kernel<GE_RESB_RELU_BF16, PM>};
+  const void* ks[8] = {(const void*)gemm2_bf16_kernel<GEMM_BF16, PM>, (const void*)gemm2_bf16_kernel<GEMM_GELU_BF16, PM>,
+                       (const void*)gemm2_bf16_kernel<GEMM_RES_F32, PM>, (const void*)gemm2_bf16_kernel<GEMM_PE_F32, PM>,
+                       (const void*)gemm2_bf16_kernel<GEMM_F32, PM>, (const void*)gemm2_bf16_kernel<GEMM_RELU_BF16, PM>,
+                       (const void*)gemm2_bf16_kernel<GEMM_RESB_BF16, PM>,
+                       (const void*)gemm2_bf16_kernel<GEMM_RESB_RELU_BF16, PM>};
   for (auto k : ks) {
     hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS);
     if (e != hipSuccess) return e;
@@ -1169,16 +1163,16 @@ template <bool PM>
 void launch_gemm2(int epi, const GemmBf16Args& g, hipStream_t s) {
   const dim3 grid(((g.M + G2_M - 1) / G2_M) * (g.N / G2_N)), blk(256);
   switch (epi) {
-    case GE_BF16: hipLaunchKernelGGL((gemm2_bf16_kernel<GE_BF16, PM>), grid, blk, G2_LDS, s, g); break;
-    case GE_GELU_BF16: hipLaunchKernelGGL((gemm2_bf16_kernel<GE_GELU_BF16, PM>), grid, blk, G2_LDS, s, g); break;
-    case GE_RES_F32: hipLaunchKernelGGL((gemm2_bf16_kernel<GE_RES_F32, PM>), grid, blk, G2_LDS, s, g); break;
-    case GE_PE_F32: hipLaunchKernelGGL((gemm2_bf16_kernel<GE_PE_F32, PM>), grid, blk, G2_LDS, s, g); break;
-    case GE_RELU_BF16: hipLaunchKernelGGL((gemm2_bf16_kernel<GE_RELU_BF16, PM>), grid, blk, G2_LDS, s, g); break;
-    case GE_RESB_BF16: hipLaunchKernelGGL((gemm2_bf16_kernel<GE_RESB_BF16, PM>), grid, blk, G2_LDS, s, g); break;
-    case GE_RESB_RELU_BF16:
-      hipLaunchKernelGGL((gemm2_bf16_kernel<GE_RESB_RELU_BF16, PM>), grid, blk, G2_LDS, s, g);
+    case GEMM_BF16: hipLaunchKernelGGL((gemm2_bf16_kernel<GEMM_BF16, PM>), grid, blk, G2_LDS, s, g); break;
+    case GEMM_GELU_BF16: hipLaunchKernelGGL((gemm2_bf16_kernel<GEMM_GELU_BF16, PM>), grid, blk, G2_LDS, s, g); break;
+    case GEMM_RES_F32: hipLaunchKernelGGL((gemm2_bf16_kernel<GEMM_RES_F32, PM>), grid, blk, G2_LDS, s, g); break;
+    case GEMM_PE_F32: hipLaunchKernelGGL((gemm2_bf16_kernel<GEMM_PE_F32, PM>), grid, blk, G2_LDS, s, g); break;
+    case GEMM_RELU_BF16: hipLaunchKernelGGL((gemm2_bf16_kernel<GEMM_RELU_BF16, PM>), grid, blk, G2_LDS, s, g); break;
+    case GEMM_RESB_BF16: hipLaunchKernelGGL((gemm2_bf16_kernel<GEMM_RESB_BF16, PM>), grid, blk, G2_LDS, s, g); break;
+    case GEMM_RESB_RELU_BF16:
+      hipLaunchKernelGGL((gemm2_bf16_kernel<GEMM_RESB_RELU_BF16, PM>), grid, blk, G2_LDS, s, g);
       break;
-    default: hipLaunchKernelGGL((gemm2_bf16_kernel<GE_F32, PM>), grid, blk, G2_LDS, s, g); break;
+    default: hipLaunchKernelGGL((gemm2_bf16_kernel<GEMM_F32, PM>), grid, blk, G2_LDS, s, g); break;
   }
 }
 
@@ -1226,16 +1220,16 @@ template <int NW, int SH = 0, bool PM = false>
 void launch_gemm_nw(int epi, dim3 grid, const GemmBf16Args& g, hipStream_t s) {
   const dim3 blk(64 * NW);
   switch (epi) {
-    case GE_BF16: hipLaunchKernelGGL((gemm_bf16_kernel<GE_BF16, NW, SH, PM>), grid, blk, GB_LDS, s, g); break;
-    case GE_GELU_BF16: hipLaunchKernelGGL((gemm_bf16_kernel<GE_GELU_BF16, NW, SH, PM>), grid, blk, GB_LDS, s, g); break;
-    case GE_RES_F32: hipLaunchKernelGGL((gemm_bf16_kernel<GE_RES_F32, NW, SH, PM>), grid, blk, GB_LDS, s, g); break;
-    case GE_PE_F32: hipLaunchKernelGGL((gemm_bf16_kernel<GE_PE_F32, NW, SH, PM>), grid, blk, GB_LDS, s, g); break;
-    case GE_RELU_BF16: hipLaunchKernelGGL((gemm_bf16_kernel<GE_RELU_BF16, NW, SH, PM>), grid, blk, GB_LDS, s, g); break;
-    case GE_RESB_BF16: hipLaunchKernelGGL((gemm_bf16_kernel<GE_RESB_BF16, NW, SH, PM>), grid, blk, GB_LDS, s, g); break;
-    case GE_RESB_RELU_BF16:
-      hipLaunchKernelGGL((gemm_bf16_kernel<GE_RESB_RELU_BF16, NW, SH, PM>), grid, blk, GB_LDS, s, g);
+    case GEMM_BF16: hipLaunchKernelGGL((gemm_bf16_kernel<GEMM_BF16, NW, SH, PM>), grid, blk, GB_LDS, s, g); break;
+    case GEMM_GELU_BF16: hipLaunchKernelGGL((gemm_bf16_kernel<GEMM_GELU_BF16, NW, SH, PM>), grid, blk, GB_LDS, s, g); break;
+    case GEMM_RES_F32: hipLaunchKernelGGL((gemm_bf16_kernel<GEMM_RES_F32, NW, SH, PM>), grid, blk, GB_LDS, s, g); break;
+    case GEMM_PE_F32: hipLaunchKernelGGL((gemm_bf16_kernel<GEMM_PE_F32, NW, SH, PM>), grid, blk, GB_LDS, s, g); break;
+    case GEMM_RELU_BF16: hipLaunchKernelGGL((gemm_bf16_kernel<GEMM_RELU_BF16, NW, SH, PM>), grid, blk, GB_LDS, s, g); break;
+    case GEMM_RESB_BF16: hipLaunchKernelGGL((gemm_bf16_kernel<GEMM_RESB_BF16, NW, SH, PM>), grid, blk, GB_LDS, s, g); break;
+    case GEMM_RESB_RELU_BF16:
+      hipLaunchKernelGGL((gemm_bf16_kernel<GEMM_RESB_RELU_BF16, NW, SH, PM>), grid, blk, GB_LDS, s, g);
       break;
-    default: hipLaunchKernelGGL((gemm_bf16_kernel<GE_F32, NW, SH, PM>), grid, blk, GB_LDS, s, g); break;
+    default: hipLaunchKernelGGL((gemm_bf16_kernel<GEMM_F32, NW, SH, PM>), grid, blk, GB_LDS, s, g); break;
   }
 }
 
@@ -1259,7 +1253,7 @@ static int device_cus() {
 // the persistent kernel's conditions: a residual-free bf16 epilogue with a bias, K / 32 >= 6, more tiles than CUs (one
 // workgroup per CU, a multiple of 8 of them), a tile's stores inside a 32-bit buffer range
 bool gemm_persist_ok(int epi, const GemmBf16& a) {
-  if ((epi != GE_BF16 && epi != GE_GELU_BF16 && epi != GE_RELU_BF16) || !a.bias || a.K / GB_K < 6 || a.N % GB_N ||
+  if ((epi != GEMM_BF16 && epi != GEMM_GELU_BF16 && epi != GEMM_RELU_BF16) || !a.bias || a.K / GB_K < 6 || a.N % GB_N ||
       a.K % 64 || a.M < 1)
     return false;
   const long ntiles = (long)((a.M + GB_M - 1) / GB_M) * (a.N / GB_N);
@@ -1275,11 +1269,11 @@ static hipError_t launch_gemmp(int epi, const GemmBf16Args& g, hipStream_t s) {
   const int grid = device_cus() & ~7;  // one workgroup per CU, a multiple of 8 (the XCD-grouped tile walk)
   const bool pm = g.M % GB_M != 0;
   switch (epi) {
-    case GE_BF16: pm ? launch_gemmp_t<GE_BF16, true>(g, grid, s) : launch_gemmp_t<GE_BF16, false>(g, grid, s); break;
-    case GE_GELU_BF16:
-      pm ? launch_gemmp_t<GE_GELU_BF16, true>(g, grid, s) : launch_gemmp_t<GE_GELU_BF16, false>(g, grid, s);
+    case GEMM_BF16: pm ? launch_gemmp_t<GEMM_BF16, true>(g, grid, s) : launch_gemmp_t<GEMM_BF16, false>(g, grid, s); break;
+    case GEMM_GELU_BF16:
+      pm ? launch_gemmp_t<GEMM_GELU_BF16, true>(g, grid, s) : launch_gemmp_t<GEMM_GELU_BF16, false>(g, grid, s);
       break;
-    default: pm ? launch_gemmp_t<GE_RELU_BF16, true>(g, grid, s) : launch_gemmp_t<GE_RELU_BF16, false>(g, grid, s);
+    default: pm ? launch_gemmp_t<GEMM_RELU_BF16, true>(g, grid, s) : launch_gemmp_t<GEMM_RELU_BF16, false>(g, grid, s);
   }
   return hipGetLastError();
 }
@@ -1316,8 +1310,8 @@ hipError_t launch_gemm_bf16(int epi, const GemmBf16& a, hipStream_t s) {
   g.lda = a.lda; g.ldw = a.ldw; g.ldo = a.ldo; g.ldr = a.ldr;
   g.M = a.M; g.N = a.N; g.K = a.K; g.tokens = a.tokens;
   g.resb = reinterpret_cast<const bf16*>(a.resb);
-  const bool rb = epi == GE_RESB_BF16 || epi == GE_RESB_RELU_BF16;
-  if (a.M < 1 || a.N % GB_N || a.K % 64 || (rb && !a.resb) || (epi == GE_PE_F32 && a.tokens != AT_T))
+  const bool rb = epi == GEMM_RESB_BF16 || epi == GEMM_RESB_RELU_BF16;
+  if (a.M < 1 || a.N % GB_N || a.K % 64 || (rb && !a.resb) || (epi == GEMM_PE_F32 && a.tokens != AT_T))
     return hipErrorInvalidValue;
   if (const hipError_t e = vit_kernels_setup(); e != hipSuccess) return e;
   if (g_gemm_waves == 0) {
@@ -1332,7 +1326,7 @@ hipError_t launch_gemm_bf16(int epi, const GemmBf16& a, hipStream_t s) {
     return hipGetLastError();
   }
   const dim3 grid(((a.M + GB_M - 1) / GB_M) * (a.N / GB_N));
-  const bool sh = g_gemm_waves == 16 || (g_gemm_waves == 1 && epi != GE_RES_F32 && epi != GE_PE_F32 && epi != GE_F32);
+  const bool sh = g_gemm_waves == 16 || (g_gemm_waves == 1 && epi != GEMM_RES_F32 && epi != GEMM_PE_F32 && epi != GEMM_F32);
   if (a.M % GB_M) {
     if (sh)
       launch_gemm_nw<8, 1, true>(epi, grid, g, s);

@@ -5,11 +5,11 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/vge_dwpose.h"
-#include "vge_cnn.h"
 #include "vge_cnn_host.h"
 
-using namespace vge::cnnh;
+using namespace vge::host;
 #define HIPCHK VGE_HIPCHK
+#define RC VGE_RC
 
 namespace {
 
@@ -36,6 +36,7 @@ struct vge_yolox {
   YCsp c2, c3, c4, c5, p4, p3, n3, n4;
   YHead head[3];
   void* zero = nullptr;
+  Workspace ws;
   int chunk = 0;
   void *in = nullptr, *A = nullptr, *B = nullptr, *X2b = nullptr, *CAT = nullptr, *Ma = nullptr, *Mb = nullptr,
        *T = nullptr, *Cat8 = nullptr, *Cat16 = nullptr, *Pcat16 = nullptr, *Pcat32 = nullptr, *SPP = nullptr,
@@ -160,13 +161,11 @@ bool cfg_ok(const vge_yolox_config& c, std::string& why) {
 
 // CSPLayer: out = conv3(cat(m(conv1(x)), conv2(x))); conv1 | conv2 write [x_1 | x_2] into the concat buffer and the
 // last Bottleneck overwrites x_1 in place (its identity read and its store touch the same element)
-int ycsp(vge_yolox* m, const YCsp& L, const void* x, long ldx, int n, int h, int w, void* out, long ldo, hipStream_t s,
-         int& rc_kind) {
-  (void)rc_kind;
+int ycsp(vge_yolox* m, const YCsp& L, const void* x, long ldx, int n, int h, int w, void* out, long ldo,
+         hipStream_t s) {
   const int hid = L.hid, nb = (int)L.m1.size();
   uint16_t* cat = static_cast<uint16_t*>(m->CAT);
-  int rc;
-  if ((rc = conv(m->cx(), L.c12, x, ldx, n, h, w, 1, cat, 2 * hid, s)) != VGE_OK) return rc;
+  RC(conv(m->cx(), L.c12, x, ldx, n, h, w, 1, cat, 2 * hid, s));
   const void* Ma = cat;
   long lda = 2 * hid;
   void* scratch[2] = {m->Ma, m->Mb};
@@ -174,10 +173,9 @@ int ycsp(vge_yolox* m, const YCsp& L, const void* x, long ldx, int n, int h, int
     const bool last = b == nb - 1;
     void* o = last ? (void*)cat : scratch[b & 1];
     const long ldb = last ? 2 * hid : hid;
-    if ((rc = conv(m->cx(), L.m1[b], Ma, lda, n, h, w, 1, m->T, hid, s)) != VGE_OK) return rc;
-    if ((rc = conv(m->cx(), L.m2[b], m->T, hid, n, h, w, 1, o, ldb, s, 1, 0, L.shortcut ? 1 : 0,
-                   L.shortcut ? Ma : nullptr, lda)) != VGE_OK)
-      return rc;
+    RC(conv(m->cx(), L.m1[b], Ma, lda, n, h, w, 1, m->T, hid, s));
+    RC(conv(m->cx(), L.m2[b], m->T, hid, n, h, w, 1, o, ldb, s, 1, 0, L.shortcut ? 1 : 0, L.shortcut ? Ma : nullptr,
+            lda));
     Ma = o;
     lda = ldb;
   }
@@ -218,8 +216,8 @@ int vge_yolox_reserve(vge_yolox* m, int chunk) {
   const size_t S = c.in_size, w0 = c.width, hc = c.head_ch, N = chunk;
   const size_t s2 = (S / 2) * (S / 2), s4 = (S / 4) * (S / 4), s8 = (S / 8) * (S / 8), s16 = (S / 16) * (S / 16),
                s32 = (S / 32) * (S / 32);
-  struct B { void** p; size_t bytes; };
-  const B bufs[] = {
+  m->chunk = 0;
+  RC(m->ws.reserve("vge_yolox_reserve", {
       {&m->in, N * s2 * 16 * 2},       {&m->A, N * s2 * w0 * 2},         {&m->B, N * s4 * 2 * w0 * 2},
       {&m->X2b, N * s4 * 2 * w0 * 2},  {&m->CAT, N * s4 * 2 * w0 * 2},   {&m->Ma, N * s4 * w0 * 2},
       {&m->Mb, N * s4 * w0 * 2},       {&m->T, N * s4 * w0 * 2},         {&m->Cat8, N * s8 * 8 * w0 * 2},
@@ -229,13 +227,7 @@ int vge_yolox_reserve(vge_yolox* m, int chunk) {
       {&m->PAN[2], N * s32 * 16 * w0 * 2}, {&m->HS, N * s8 * hc * 2},     {&m->HB, N * s8 * 2 * hc * 2},
       {&m->CF, N * s8 * hc * 2},       {&m->RF, N * s8 * hc * 2},
       {(void**)&m->OUT[0], N * s8 * 8 * 4}, {(void**)&m->OUT[1], N * s16 * 8 * 4}, {(void**)&m->OUT[2], N * s32 * 8 * 4},
-  };
-  for (const B& b : bufs) {
-    void* p = m->dev.dmalloc(b.bytes);
-    if (!p) return fail(VGE_ERR_NOMEM, "vge_yolox_reserve: hipMalloc failed");
-    HIPCHK(hipMemset(p, 0, b.bytes));
-    *b.p = p;
-  }
+  }));
   m->chunk = chunk;
   return VGE_OK;
 }
@@ -279,30 +271,9 @@ int vge_yolox_detect_scored(vge_yolox* m, const uint8_t* frames, int F, int H, i
   (void)A;
   m->gemm_flops = 0;
   m->prof.start_call();
-  int rc;
-#define RC(x)                            \
-  do {                                   \
-    if ((rc = (x)) != VGE_OK) return rc; \
-  } while (0)
-#define CONV(...)                   \
-  do {                              \
-    RC(m->prof.beg(0, s));          \
-    RC(conv(m->cx(), __VA_ARGS__)); \
-    RC(m->prof.end(s));             \
-  } while (0)
-#define CSP(...)                    \
-  do {                              \
-    int k_ = 0;                     \
-    RC(m->prof.beg(0, s));          \
-    RC(ycsp(m, __VA_ARGS__, s, k_)); \
-    RC(m->prof.end(s));             \
-  } while (0)
-#define OTHER(expr)        \
-  do {                     \
-    RC(m->prof.beg(1, s)); \
-    HIPCHK(expr);          \
-    RC(m->prof.end(s));    \
-  } while (0)
+#define CONV(...) VGE_STAGE(m->prof, s, 0, conv(m->cx(), __VA_ARGS__))
+#define CSP(...) VGE_STAGE(m->prof, s, 0, ycsp(m, __VA_ARGS__, s))
+#define OTHER(expr) VGE_STAGE(m->prof, s, 1, VGE_HIP(expr))
   const int c3 = 4 * w0, c4 = 8 * w0, c5 = 16 * w0;
   for (int f0 = 0; f0 < F; f0 += m->chunk) {
     const int n = std::min(m->chunk, F - f0);
@@ -354,7 +325,6 @@ int vge_yolox_detect_scored(vge_yolox* m, const uint8_t* frames, int F, int H, i
 #undef OTHER
 #undef CSP
 #undef CONV
-#undef RC
   m->prof.end_call(m->gemm_flops);
   return VGE_OK;
 }

@@ -153,73 +153,46 @@ def _cfg_c(cfg: RtmposeConfig) -> RtmposeConfigC:
                           cfg.final_k, cfg.split)
 
 
+_vp, _i32, _i64 = C.c_void_p, C.c_int, C.c_long
+_SIG = {
+    "vge_dwpose_create": [C.POINTER(RtmposeConfigC), C.POINTER(L.TensorView), _i32, C.POINTER(_vp)],
+    "vge_dwpose_reserve": [_vp, _i32],
+    "vge_dwpose_destroy": [_vp],
+    "vge_dwpose_keypoints": [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
+    "vge_dwpose_profile_begin": [_vp, _i32],
+    "vge_dwpose_profile_read": [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double)],
+    "vge_op_conv_bf16": [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                         _i32, _i32, _i32, _i32, _vp],
+    "vge_yolox_create": [C.POINTER(YoloxConfigC), C.POINTER(L.TensorView), _i32, C.POINTER(_vp)],
+    "vge_yolox_reserve": [_vp, _i32],
+    "vge_yolox_destroy": [_vp],
+    "vge_yolox_detect": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
+    "vge_yolox_detect_scored": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
+    "vge_yolox_profile_begin": [_vp, _i32],
+    "vge_yolox_profile_read": [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double)],
+}
+
+
 def _sig(lib):
-    if getattr(lib, "_dwpose_sig", False):
-        return lib
-    vp, i32, i64 = C.c_void_p, C.c_int, C.c_long
-    sig = {
-        "vge_dwpose_create": [C.POINTER(RtmposeConfigC), C.POINTER(L.TensorView), i32, C.POINTER(vp)],
-        "vge_dwpose_reserve": [vp, i32],
-        "vge_dwpose_destroy": [vp],
-        "vge_dwpose_keypoints": [vp, vp, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp],
-        "vge_dwpose_profile_begin": [vp, i32],
-        "vge_dwpose_profile_read": [vp, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double)],
-        "vge_op_conv_bf16": [vp, i64, vp, vp, vp, i64, vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32,
-                             i32, i32, vp],
-        "vge_yolox_create": [C.POINTER(YoloxConfigC), C.POINTER(L.TensorView), i32, C.POINTER(vp)],
-        "vge_yolox_reserve": [vp, i32],
-        "vge_yolox_destroy": [vp],
-        "vge_yolox_detect": [vp, vp, i32, i32, i32, vp, vp, vp, vp],
-        "vge_yolox_detect_scored": [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp],
-        "vge_yolox_profile_begin": [vp, i32],
-        "vge_yolox_profile_read": [vp, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double)],
-    }
-    for name, args in sig.items():
-        f = getattr(lib, name)
-        f.argtypes = args
-        f.restype = C.c_int
-    lib._dwpose_sig = True
-    return lib
+    return L.bind(lib, "dwpose", _SIG)
 
 
-def _views(state_dict: Dict[str, np.ndarray]):
-    keep, views = [], []
-    for k, v in state_dict.items():
-        a = np.ascontiguousarray(np.asarray(v, dtype=np.float32))
-        keep.append(a)
-        tv = L.TensorView()
-        tv.name = k.encode()
-        tv.data = a.ctypes.data
-        tv.ndim = a.ndim
-        for i, s in enumerate(a.shape[:4]):
-            tv.shape[i] = s
-        views.append(tv)
-    return keep, (L.TensorView * len(views))(*views), len(views)
+_views = L.tensor_views
 
 
-class DwposeExtractor:
+class DwposeExtractor(L.NativeModel):
     """One RTMPose whole-body model resident in HBM (BN-folded bf16 NHWC weights) + its activation workspace."""
+    PREFIX = "dwpose"
 
     def __init__(self, state_dict: Dict[str, np.ndarray], cfg: RtmposeConfig = RTMPOSE_L, device="cuda",
                  max_instances: int = 64):
-        self.lib = _sig(L.load())
-        self.cfg = cfg
-        self.device = torch.device(device)
-        keep, arr, n = _views(state_dict)
-        h = C.c_void_p()
-        cc = _cfg_c(cfg)
-        with torch.cuda.device(self.device):
-            L.check(self.lib.vge_dwpose_create(C.byref(cc), arr, n, C.byref(h)), "vge_dwpose_create")
-        del keep
-        self.h = h
-        self.max_instances = 0
+        self._create(_sig(L.load()), cfg, _cfg_c(cfg), state_dict, device)
         self.reserve(max_instances)
 
+    max_instances = property(lambda self: self._reserved[0])
+
     def reserve(self, max_instances: int) -> None:
-        if max_instances > self.max_instances:
-            with torch.cuda.device(self.device):
-                L.check(self.lib.vge_dwpose_reserve(self.h, int(max_instances)), "vge_dwpose_reserve")
-            self.max_instances = max_instances
+        self._reserve(max_instances)
 
     @staticmethod
     def instances(n_persons: np.ndarray) -> int:
@@ -255,43 +228,17 @@ class DwposeExtractor:
                 "vge_dwpose_keypoints")
         return out
 
-    def profile_begin(self, max_calls: int) -> None:
-        L.check(self.lib.vge_dwpose_profile_begin(self.h, int(max_calls)), "vge_dwpose_profile_begin")
-
     def profile_read(self):
-        ms = (C.c_double * 3)()
-        n = C.c_int()
-        fl = C.c_double()
-        L.check(self.lib.vge_dwpose_profile_read(self.h, ms, C.byref(n), C.byref(fl)), "vge_dwpose_profile_read")
-        return {"gemm": ms[0], "dw_pool_attn_prep": ms[1], "head_misc": ms[2]}, n.value, fl.value
-
-    def close(self) -> None:
-        if self.h:
-            self.lib.vge_dwpose_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._profile_read(("gemm", "dw_pool_attn_prep", "head_misc"))
 
 
-class YoloxDetector:
+class YoloxDetector(L.NativeModel):
     """DWPose's YOLOX person detector resident in HBM (onnxdet.inference_detector restated; person class only)."""
+    PREFIX = "yolox"
 
     def __init__(self, state_dict: Dict[str, np.ndarray], cfg: YoloxConfig = YOLOX_L, device="cuda", chunk: int = 32):
-        self.lib = _sig(L.load())
-        self.cfg = cfg
-        self.device = torch.device(device)
-        keep, arr, n = _views(state_dict)
-        h = C.c_void_p()
-        cc = _ycfg_c(cfg)
-        with torch.cuda.device(self.device):
-            L.check(self.lib.vge_yolox_create(C.byref(cc), arr, n, C.byref(h)), "vge_yolox_create")
-            del keep
-            self.h = h
-            L.check(self.lib.vge_yolox_reserve(self.h, int(chunk)), "vge_yolox_reserve")
+        self._create(_sig(L.load()), cfg, _ycfg_c(cfg), state_dict, device)
+        self._reserve(chunk)
 
     @property
     def anchors(self) -> int:
@@ -314,26 +261,8 @@ class YoloxDetector:
                 "vge_yolox_detect")
         return (boxes, npers, scores) if with_scores else (boxes, npers)
 
-    def profile_begin(self, max_calls: int) -> None:
-        L.check(self.lib.vge_yolox_profile_begin(self.h, int(max_calls)), "vge_yolox_profile_begin")
-
     def profile_read(self):
-        ms = (C.c_double * 2)()
-        n = C.c_int()
-        fl = C.c_double()
-        L.check(self.lib.vge_yolox_profile_read(self.h, ms, C.byref(n), C.byref(fl)), "vge_yolox_profile_read")
-        return {"gemm": ms[0], "other": ms[1]}, n.value, fl.value
-
-    def close(self) -> None:
-        if self.h:
-            self.lib.vge_yolox_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._profile_read(("gemm", "other"))
 
 
 class Wholebody:

@@ -69,24 +69,20 @@ def _cfg_c(cfg: FrcnnConfig) -> FrcnnConfigC:
                         cfg.num_classes, cfg.score_thresh, cfg.nms_thresh, cfg.det_per_img, cfg.gate_thresh)
 
 
+_vp, _i32 = C.c_void_p, C.c_int
+_SIG = {
+    "vge_frcnn_create": [C.POINTER(FrcnnConfigC), C.POINTER(L.TensorView), _i32, C.POINTER(_vp)],
+    "vge_frcnn_reserve": [_vp, _i32, _i32, _i32],
+    "vge_frcnn_destroy": [_vp],
+    "vge_frcnn_shapes": [_vp, _i32, _i32, C.POINTER(C.c_int)],
+    "vge_frcnn_detect": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, C.POINTER(FrcnnTapsC), _vp],
+    "vge_frcnn_profile_begin": [_vp, _i32],
+    "vge_frcnn_profile_read": [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double)],
+}
+
+
 def _sig(lib):
-    if getattr(lib, "_frcnn_sig", False):
-        return lib
-    vp, i32 = C.c_void_p, C.c_int
-    sig = {
-        "vge_frcnn_create": [C.POINTER(FrcnnConfigC), C.POINTER(L.TensorView), i32, C.POINTER(vp)],
-        "vge_frcnn_reserve": [vp, i32, i32, i32],
-        "vge_frcnn_destroy": [vp],
-        "vge_frcnn_shapes": [vp, i32, i32, C.POINTER(C.c_int)],
-        "vge_frcnn_detect": [vp, vp, i32, i32, i32, vp, vp, vp, vp, C.POINTER(FrcnnTapsC), vp],
-        "vge_frcnn_profile_begin": [vp, i32],
-        "vge_frcnn_profile_read": [vp, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double)],
-    }
-    for k, a in sig.items():
-        getattr(lib, k).argtypes = a
-        getattr(lib, k).restype = C.c_int
-    lib._frcnn_sig = True
-    return lib
+    return L.bind(lib, "frcnn", _SIG)
 
 
 def _flops(cfg: FrcnnConfig, hp: int, wp: int) -> Tuple[float, float]:
@@ -129,31 +125,26 @@ def _flops(cfg: FrcnnConfig, hp: int, wp: int) -> Tuple[float, float]:
     return backbone, head
 
 
-class FrcnnDetector:
+class FrcnnDetector(L.NativeModel):
     """detectron2 DefaultPredictor(faster_rcnn_X_101_32x8d_FPN_3x) resident in HBM: FrozenBN-folded bf16 NHWC
     weights + a chunk workspace.  chunk: frames per workspace pass (larger chunks fill the GPU better: 256 frames of
     256 x 256 take 260 / 252 / 244 ms at chunks of 32 / 32 / 64 on one box); capped where a layer's row count or an
     elementwise kernel's thread count would pass 2^31 (`max_chunk`: 838 frames at detectron2's 800-pixel size; every
     activation is addressed through 64-bit offsets)."""
 
+    PREFIX = "frcnn"
+
     def __init__(self, state_dict: Dict[str, np.ndarray], cfg: FrcnnConfig = FRCNN_X101, device="cuda",
                  chunk: int = 64, frame_hw: Tuple[int, int] = (256, 256)):
-        from .dwpose import _views
-        self.lib = _sig(L.load())
-        self.cfg = cfg
-        self.device = torch.device(device)
-        keep, arr, n = _views(state_dict)
-        h = C.c_void_p()
-        cc = _cfg_c(cfg)
-        with torch.cuda.device(self.device):
-            L.check(self.lib.vge_frcnn_create(C.byref(cc), arr, n, C.byref(h)), "vge_frcnn_create")
-            del keep
-            self.h = h
-            self.chunk_req = int(chunk)
-            self.chunk = min(self.chunk_req, self.max_chunk(*frame_hw))
-            L.check(self.lib.vge_frcnn_reserve(self.h, self.chunk, int(frame_hw[0]), int(frame_hw[1])),
-                    "vge_frcnn_reserve")
-            self.frame_hw = (int(frame_hw[0]), int(frame_hw[1]))
+        self._create(_sig(L.load()), cfg, _cfg_c(cfg), state_dict, device)
+        self.chunk_req = int(chunk)
+        self._fit(int(frame_hw[0]), int(frame_hw[1]))
+
+    def _fit(self, H: int, W: int) -> None:
+        """The workspace for H x W frames, at a chunk that fits them."""
+        self.chunk = min(self.chunk_req, self.max_chunk(H, W))
+        self._reserve(self.chunk, H, W)
+        self.frame_hw = (H, W)
 
     def max_chunk(self, H: int, W: int) -> int:
         """The largest chunk vge_frcnn_reserve accepts for H x W frames (rows per layer and threads per elementwise
@@ -210,11 +201,8 @@ class FrcnnDetector:
         if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
             raise L.VgeError("frames must be contiguous uint8 [F,H,W,3]")
         F_, H_, W_ = (int(v) for v in frames.shape[:3])
-        if (H_, W_) != self.frame_hw:  # a new frame size: the workspace is rebuilt at a chunk that fits it
-            self.chunk = min(self.chunk_req, self.max_chunk(H_, W_))
-            with torch.cuda.device(self.device):
-                L.check(self.lib.vge_frcnn_reserve(self.h, self.chunk, H_, W_), "vge_frcnn_reserve")
-            self.frame_hw = (H_, W_)
+        if (H_, W_) != self.frame_hw:  # a new frame size: the workspace is rebuilt
+            self._fit(H_, W_)
         dev = frames.device
         out = {"dets": torch.zeros((F_, self.cfg.det_per_img, 6), dtype=torch.float32, device=dev),
                "n_dets": torch.empty((F_,), dtype=torch.int32, device=dev),
@@ -227,23 +215,5 @@ class FrcnnDetector:
                 "vge_frcnn_detect")
         return out
 
-    def profile_begin(self, max_calls: int) -> None:
-        L.check(self.lib.vge_frcnn_profile_begin(self.h, int(max_calls)), "vge_frcnn_profile_begin")
-
     def profile_read(self):
-        ms = (C.c_double * 3)()
-        n = C.c_int()
-        fl = (C.c_double * 2)()
-        L.check(self.lib.vge_frcnn_profile_read(self.h, ms, C.byref(n), fl), "vge_frcnn_profile_read")
-        return {"backbone_gemm": ms[0], "head_gemm": ms[1], "other": ms[2]}, n.value, (fl[0], fl[1])
-
-    def close(self) -> None:
-        if getattr(self, "h", None):
-            self.lib.vge_frcnn_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._profile_read(("backbone_gemm", "head_gemm", "other"), n_flops=2)

@@ -53,64 +53,39 @@ def _cfg_c(cfg: HmrConfig) -> HmrConfigC:
     return HmrConfigC(**asdict(cfg))
 
 
+_vp, _i32 = C.c_void_p, C.c_int
+_SIG = {
+    "vge_hmr_create": [C.POINTER(HmrConfigC), C.POINTER(L.TensorView), _i32, C.POINTER(_vp)],
+    "vge_hmr_reserve": [_vp, _i32],
+    "vge_hmr_destroy": [_vp],
+    "vge_hmr_extract": [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
+    "vge_hmr_profile_begin": [_vp, _i32],
+    "vge_hmr_profile_read": [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double)],
+    "vge_op_gemm_bf16": [_i32, _vp, C.c_long, _vp, C.c_long, _vp, C.c_long, _vp, _vp, C.c_long, _vp, _i32, _i32, _i32,
+                         _i32, _vp],
+    "vge_op_gemm_lib": [_i32, _vp, C.c_long, _vp, C.c_long, _vp, C.c_long, _vp, _vp, C.c_long, _i32, _i32, _i32, _vp],
+    "vge_op_vit_attention": [_vp, _vp, _i32, _i32, _i32, _vp],
+    "vge_hmr_crop": [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp],
+    "vge_op_layernorm_bf16": [_vp, _vp, _vp, _vp, _i32, _i32, C.c_float, _vp],
+}
+
+
 def _sig(lib):
-    if getattr(lib, "_hmr_sig", False):
-        return lib
-    vp, i32 = C.c_void_p, C.c_int
-    sig = {
-        "vge_hmr_create": [C.POINTER(HmrConfigC), C.POINTER(L.TensorView), i32, C.POINTER(vp)],
-        "vge_hmr_reserve": [vp, i32],
-        "vge_hmr_destroy": [vp],
-        "vge_hmr_extract": [vp, vp, i32, vp, vp, vp, vp, vp],
-        "vge_hmr_profile_begin": [vp, i32],
-        "vge_hmr_profile_read": [vp, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double)],
-        "vge_op_gemm_bf16": [i32, vp, C.c_long, vp, C.c_long, vp, C.c_long, vp, vp, C.c_long, vp, i32, i32, i32, i32,
-                             vp],
-        "vge_op_gemm_lib": [i32, vp, C.c_long, vp, C.c_long, vp, C.c_long, vp, vp, C.c_long, i32, i32, i32, vp],
-        "vge_op_vit_attention": [vp, vp, i32, i32, i32, vp],
-        "vge_hmr_crop": [vp, i32, i32, i32, vp, vp, i32, vp, vp],
-        "vge_op_layernorm_bf16": [vp, vp, vp, vp, i32, i32, C.c_float, vp],
-    }
-    for name, args in sig.items():
-        f = getattr(lib, name)
-        f.argtypes = args
-        f.restype = C.c_int
-    lib._hmr_sig = True
-    return lib
+    return L.bind(lib, "hmr", _SIG)
 
 
-class HmrExtractor:
+class HmrExtractor(L.NativeModel):
     """One TokenHMR model resident in HBM (bf16 weights) + its activation workspace."""
+    PREFIX = "hmr"
 
     def __init__(self, state_dict: Dict[str, np.ndarray], cfg: HmrConfig = TOKENHMR, device="cuda", max_frames: int = 256):
-        self.lib = _sig(L.load())
-        self.cfg = cfg
-        self.device = torch.device(device)
-        keep, views = [], []
-        for k, v in state_dict.items():
-            a = np.ascontiguousarray(np.asarray(v, dtype=np.float32))
-            keep.append(a)
-            tv = L.TensorView()
-            tv.name = k.encode()
-            tv.data = a.ctypes.data
-            tv.ndim = a.ndim
-            for i, s in enumerate(a.shape[:4]):
-                tv.shape[i] = s
-            views.append(tv)
-        arr = (L.TensorView * len(views))(*views)
-        h = C.c_void_p()
-        cc = _cfg_c(cfg)
-        with torch.cuda.device(self.device):
-            L.check(self.lib.vge_hmr_create(C.byref(cc), arr, len(views), C.byref(h)), "vge_hmr_create")
-        self.h = h
-        self.max_frames = 0
+        self._create(_sig(L.load()), cfg, _cfg_c(cfg), state_dict, device)
         self.reserve(max_frames)
 
+    max_frames = property(lambda self: self._reserved[0])
+
     def reserve(self, max_frames: int) -> None:
-        if max_frames > self.max_frames:
-            with torch.cuda.device(self.device):
-                L.check(self.lib.vge_hmr_reserve(self.h, int(max_frames)), "vge_hmr_reserve")
-            self.max_frames = max_frames
+        self._reserve(max_frames)
 
     def extract(self, frames: torch.Tensor, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
         """frames: uint8 [F, 256, 256, 3] RGB on the device -> {pose [F,207], global_orient [F,9], betas [F,10],
@@ -137,26 +112,8 @@ class HmrExtractor:
                     "global_orient": h["global_orient"][i].reshape(1, 3, 3), "vit": h["vit"][i]}
                 for i in range(frames.shape[0])}
 
-    def profile_begin(self, max_calls: int) -> None:
-        L.check(self.lib.vge_hmr_profile_begin(self.h, int(max_calls)), "vge_hmr_profile_begin")
-
     def profile_read(self):
-        ms = (C.c_double * 4)()
-        n = C.c_int()
-        fl = C.c_double()
-        L.check(self.lib.vge_hmr_profile_read(self.h, ms, C.byref(n), C.byref(fl)), "vge_hmr_profile_read")
-        return {"gemm": ms[0], "attention": ms[1], "layernorm_patchify": ms[2], "head": ms[3]}, n.value, fl.value
-
-    def close(self) -> None:
-        if self.h:
-            self.lib.vge_hmr_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._profile_read(("gemm", "attention", "layernorm_patchify", "head"))
 
 
 # ---- op-level entry points (parity tests) ---------------------------------------------------------

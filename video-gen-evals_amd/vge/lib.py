@@ -6,6 +6,9 @@ import ctypes as C
 import os
 from pathlib import Path
 
+import numpy as np
+import torch
+
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("VGE_LIB", _HERE / "libvge.so"))
 
@@ -173,3 +176,81 @@ def check(status: int, what: str) -> None:
         msg = load().vge_last_error().decode(errors="replace")
         cls = {VGE_ERR_UNSUPPORTED: UnsupportedModelError, VGE_ERR_DEVICE: DeviceFaultError}.get(status, VgeError)
         raise cls(f"{what} failed: {STATUS.get(status, status)}: {msg}")
+
+
+def bind(lib: C.CDLL, tag: str, sig: dict) -> C.CDLL:
+    """Give the functions of `sig` (name -> argtypes) their argtypes and an int restype, once per library and tag."""
+    flag = f"_{tag}_sig"
+    if not getattr(lib, flag, False):
+        for name, args in sig.items():
+            f = getattr(lib, name)
+            f.argtypes = args
+            f.restype = C.c_int
+        setattr(lib, flag, True)
+    return lib
+
+
+def tensor_views(state_dict):
+    """state_dict -> (the float32 arrays the views point into, a TensorView array, its length): the weights argument
+    of every vge_*_create.  The arrays must stay alive until the create call returns."""
+    keep, views = [], []
+    for k, v in state_dict.items():
+        a = np.ascontiguousarray(np.asarray(v, dtype=np.float32))
+        keep.append(a)
+        tv = TensorView()
+        tv.name = k.encode()
+        tv.data = a.ctypes.data
+        tv.ndim = a.ndim
+        for i, s in enumerate(a.shape[:4]):
+            tv.shape[i] = s
+        views.append(tv)
+    return keep, (TensorView * len(views))(*views), len(views)
+
+
+class NativeModel:
+    """Handle of a native extractor model, vge_<PREFIX>_{create, reserve, destroy, profile_begin, profile_read}: the
+    weights resident in HBM plus a workspace that only grows.  A subclass sets PREFIX, calls _create from its __init__
+    and adds its forward calls; .lib, .cfg, .device and .h (the C handle) are public."""
+    PREFIX = ""
+
+    def _call(self, fn: str, *args) -> None:
+        name = f"vge_{self.PREFIX}_{fn}"
+        check(getattr(self.lib, name)(*args), name)
+
+    def _create(self, lib: C.CDLL, cfg, cfg_c: C.Structure, state_dict, device) -> None:
+        self.lib, self.cfg, self.device = lib, cfg, torch.device(device)
+        self.h, self._reserved = None, (0,)
+        keep, arr, n = tensor_views(state_dict)
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            self._call("create", C.byref(cfg_c), arr, n, C.byref(h))
+        self.h = h
+
+    def _reserve(self, n: int, *shape: int) -> None:
+        """vge_<PREFIX>_reserve(h, n, *shape) when n exceeds what is reserved or `shape` (a frame size) changed."""
+        if n > self._reserved[0] or shape != self._reserved[1:]:
+            with torch.cuda.device(self.device):
+                self._call("reserve", self.h, int(n), *shape)
+            self._reserved = (n, *shape)
+
+    def profile_begin(self, max_calls: int) -> None:
+        self._call("profile_begin", self.h, int(max_calls))
+
+    def _profile_read(self, stage_names, n_flops: int = 1):
+        """({stage: summed ms over the recorded calls}, recorded calls, FLOPs per call: a float, or a tuple of n_flops)"""
+        ms = (C.c_double * len(stage_names))()
+        n = C.c_int()
+        fl = (C.c_double * n_flops)()
+        self._call("profile_read", self.h, ms, C.byref(n), fl)
+        return dict(zip(stage_names, ms)), n.value, fl[0] if n_flops == 1 else tuple(fl)
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            self._call("destroy", self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
