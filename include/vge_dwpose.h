@@ -120,6 +120,57 @@ int vge_op_conv_bf16(const void* x, long ldx, const void* w, const float* bias, 
                      long ldr, const float* rscale, int n_img, int H, int W, int Cin, int KH, int KW, int stride,
                      int pad, int Cout, int act, int out_f32, int res_mode, vge_stream_t stream);
 
+/* Op-level entry points of the kernels around the dense layers (parity tests).  Each checks its arguments
+ * (VGE_ERR_ARG, vge_last_error names the entry and the rule, before any GPU work) and then runs the launcher the
+ * model calls.  bf16 maps are NHWC with a pixel stride (ld*, a multiple of 8) that may exceed the channels used; C is
+ * a multiple of 8.
+ *
+ * Depthwise K x K, stride 1, + SiLU: w f32 [K*K][C], b f32 [C].  K = 3, 5 (sliding-window kernel) or 55 (5 x 5 on
+ * the one-thread-per-output kernel). */
+int vge_op_dwconv_bf16(const void* x, long ldx, const float* w, const float* b, void* y, long ldy, int n_img, int H,
+                       int W, int C, int K, vge_stream_t stream);
+/* buf [n_img][H][W][ld]: channels 0..C-1 in, max_pool(k0 / k1 / k2, stride 1) out at channel offsets C, 2C, 3C (odd,
+ * ascending sizes).  variant: 0 = as the models choose, 1 = generic kernel, 2 = LDS kernel (5 / 9 / 13 on maps of
+ * <= 400 positions; refused elsewhere). */
+int vge_op_spp_pool_bf16(void* buf, long ld, int n_img, int H, int W, int C, int k0, int k1, int k2, int variant,
+                         vge_stream_t stream);
+/* ChannelAttention in place: att [n_img][C] f32 = hardsigmoid(b + Wt^T mean(x)), x *= att.  Wt f32 [C][C] =
+ * fc.weight transposed, mean = scratch of n_img * 2048 floats (C <= 2048); att is left readable. */
+int vge_op_chan_attn_bf16(void* x, long ld, int n_img, int HW, int C, const float* Wt, const float* b, float* mean,
+                          float* att, vge_stream_t stream);
+/* nearest 2x: x [n_img][H][W][ldx] -> y [n_img][2H][2W][ldy] */
+int vge_op_upsample2x_bf16(const void* x, long ldx, void* y, long ldy, int n_img, int H, int W, int C,
+                           vge_stream_t stream);
+/* The pose model's input preparation.  frames device uint8 [n_frames][H][W][3]; boxes HOST float [n_inst][4] xyxy,
+ * frame_of HOST int [n_inst] (the source frame of each instance); inst = device scratch of 16 B per instance; out
+ * bf16 [n_inst][in_h][in_w][8] (BGR normalised, channels 3..7 zero).  The box -> affine arithmetic is the function
+ * vge_dwpose_keypoints uses.  The instance table is copied synchronously. */
+int vge_op_warp_prep(const uint8_t* frames, int n_frames, int H, int W, const float* boxes, const int* frame_of,
+                     int n_inst, int in_h, int in_w, void* inst, void* out, vge_stream_t stream);
+/* The detector's input preparation: letterbox into S x S + Focus -> bf16 [n_frames][S/2][S/2][16] (12 used), with
+ * the ratio / extent arithmetic of vge_yolox_detect. */
+int vge_op_letterbox_focus(const uint8_t* frames, int n_frames, int H, int W, int S, void* out, vge_stream_t stream);
+/* RTMCCHead ScaleNorm over the hw positions of each keypoint channel: y f32 [inst][hw][ldy] (channel k of instance
+ * n_rows / K) -> out bf16 [n_rows][Kp], columns hw..Kp-1 zero; hw <= Kp <= 256. */
+int vge_op_head_scalenorm_t(const float* y, long ldy, int hw, int K, int Kp, float g, long n_rows, void* out,
+                            vge_stream_t stream);
+/* ScaleNorm of f32 rows [rows][D] -> bf16, D <= 512 */
+int vge_op_scalenorm_rows(const float* x, int D, float g, long rows, void* y, vge_stream_t stream);
+/* GAU token mixing: uv f32 [n_inst * K][2E + S] (u | v | base, SiLU applied), gamma / beta f32 [2][S] -> out bf16
+ * [n_inst * K][E].  variant: 0 = as the model chooses, 1 = VALU kernel (K <= 136), 2 = MFMA kernel (K <= 160, S
+ * even); a variant whose LDS need exceeds 160 KB at (K, S) is refused. */
+int vge_op_gau_attn(const float* uv, int n_inst, int K, int E, int S, const float* gamma, const float* beta, void* out,
+                    int variant, vge_stream_t stream);
+/* logits f32 [rows][ld] = WX x-bins then WY y-bins -> lv f32 [rows][3] = x / split, y / split, min(max_x, max_y)
+ * (first index among equal maxima; -1 / split where the value is <= 0) */
+int vge_op_simcc_decode(const float* logits, long ld, int WX, int WY, float split, long rows, float* lv,
+                        vge_stream_t stream);
+/* YOLOX decode + two-person NMS of three head levels: out<k> f32 [n_frames][grid<k>^2][8] (reg xywh, obj logit, cls-0
+ * logit), boxes [n_frames][2][4], n_persons [n_frames]; scores [n_frames][2] and cand [n_frames][A][5] optional. */
+int vge_op_yolox_decode_nms(const float* out0, const float* out1, const float* out2, int grid0, int grid1, int grid2,
+                            int stride0, int stride1, int stride2, int n_frames, float ratio, float* boxes,
+                            int* n_persons, float* scores, float* cand, vge_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

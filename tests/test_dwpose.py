@@ -79,6 +79,11 @@ def test_dwpose_config_rejected_without_gpu_work():
     out = C.c_void_p()
     assert lib.vge_dwpose_create(C.byref(bad), None, 0, C.byref(out)) == 1
     assert b"multiples of 32" in lib.vge_last_error()
+    # gau_s: 160 is the last value either token-mixing kernel holds in LDS at 136 tokens (tests/test_pose_ops.py runs
+    # it); the next multiple of 8 is refused with the limit named
+    bad = D._cfg_c(D.RtmposeConfig(gau_s=168))
+    assert lib.vge_dwpose_create(C.byref(bad), None, 0, C.byref(out)) == 1
+    assert b"gau_s must be <= 160" in lib.vge_last_error() and b"160 KB" in lib.vge_last_error()
 
 
 def test_missing_weight_reported():

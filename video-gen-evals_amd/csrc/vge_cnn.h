@@ -36,7 +36,11 @@ int conv_lib_epi(const ConvLaunch& c);
 bool conv_gemm_persist_ok(const ConvLaunch& c);  // variant 10 applies (the persistent GEMM, vge_vit.hip gemmp)
 hipError_t launch_dwconv(const void* x, long ldx, const float* w, const float* b, void* y, long ldy, int n_img, int H,
                          int W, int C, int K, hipStream_t s);
-hipError_t launch_spp_pool(void* buf, long ld, int n_img, int H, int W, int C, int k0, int k1, int k2, hipStream_t s);
+// variant: 0 = the LDS kernel where spp_lds_ok, else the generic one; 1 = generic; 2 = LDS (an error where it does
+// not apply, never a fallback)
+bool spp_lds_ok(int H, int W, int k0, int k1, int k2);
+hipError_t launch_spp_pool(void* buf, long ld, int n_img, int H, int W, int C, int k0, int k1, int k2, int variant,
+                           hipStream_t s);
 hipError_t launch_chan_attn(void* x, long ld, int n_img, int HW, int C, const float* Wt, const float* b, float* mean,
                             float* att, hipStream_t s);
 hipError_t launch_warp_prep(const uint8_t* frames, int H, int W, const void* inst, int n_inst, int oh, int ow, void* out,
@@ -53,9 +57,16 @@ hipError_t launch_yolox_decode_nms(DetLevel l0, DetLevel l1, DetLevel l2, int F,
 hipError_t launch_head_sn_t(const float* y, long ldy, int hw, int K, int Kp, float g, long n_rows, void* out,
                             hipStream_t s);
 hipError_t launch_scalenorm_rows(const float* x, int D, float g, long rows, void* y, hipStream_t s);
-size_t gau_lds_bytes(int S);
+// GAU token mixing: variant 1 = the VALU kernel (K <= 136), 2 = the MFMA kernel (K <= 160, S even), 0 = the MFMA
+// kernel where it applies (VGE_GAU_VALU=1: the VALU one first), else the other.  Both hold one instance in at most
+// GAU_LDS_LIMIT bytes of LDS; gau_variant_ok(.., 0) = either form takes the shape.  A forced variant that does not
+// take it is an error, never a fallback.
+constexpr size_t GAU_LDS_LIMIT = 160 * 1024;
+size_t gau_lds_bytes(int S);               // VALU form, sized for 136 tokens
+size_t gau_mfma_lds_bytes(int K, int S);
+bool gau_variant_ok(int K, int E, int S, int variant);
 hipError_t launch_gau_attn(const float* uv, int n_inst, int K, int E, int S, const float* gamma, const float* beta,
-                           void* out, hipStream_t s);
+                           void* out, int variant, hipStream_t s);
 hipError_t launch_simcc_decode(const float* logits, long ld, int WX, int WY, float split, long rows, float* lv,
                                hipStream_t s);
 hipError_t launch_kp120(const float* lv, const void* inst, const int* inst_of_frame, int F, int K, int in_w, int in_h,

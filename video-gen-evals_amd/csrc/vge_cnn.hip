@@ -1489,10 +1489,17 @@ hipError_t launch_dwconv(const void* x, long ldx, const float* w, const float* b
   return hipGetLastError();
 }
 
-hipError_t launch_spp_pool(void* buf, long ld, int n_img, int H, int W, int C, int k0, int k1, int k2, hipStream_t s) {
+bool spp_lds_ok(int H, int W, int k0, int k1, int k2) {
+  return k0 == 5 && k1 == 9 && k2 == 13 && (long)H * W <= SPP_LDS_MAX_HW;
+}
+
+hipError_t launch_spp_pool(void* buf, long ld, int n_img, int H, int W, int C, int k0, int k1, int k2, int variant,
+                           hipStream_t s) {
+  const bool lds = spp_lds_ok(H, W, k0, k1, k2);
+  if (variant < 0 || variant > 2 || (variant == 2 && !lds)) return hipErrorInvalidValue;  // no silent fallback
   const long n = (long)n_img * H * W * (C / 8);
   if (n == 0) return hipSuccess;
-  if (k0 == 5 && k1 == 9 && k2 == 13 && H * W <= SPP_LDS_MAX_HW) {
+  if (lds && variant != 1) {
     static LdsAttrOnce attr;
     const int bytes = 3 * SPP_LDS_MAX_HW * 8 * 16;
     if (const hipError_t e = attr(reinterpret_cast<const void*>(&spp_lds_kernel), bytes); e != hipSuccess) return e;

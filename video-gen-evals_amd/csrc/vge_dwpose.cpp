@@ -150,9 +150,14 @@ bool cfg_ok(const vge_rtmpose_config& c, std::string& why) {
   }
   if (c.keypoints < 133 || c.keypoints > 136)
     return why = "keypoints must be 133..136 (COCO-WholeBody indices feed the 120-d row)", false;
-  if (!pow2(c.gau_hidden) || c.gau_hidden > 512 || !pow2(c.gau_e) || c.gau_e < 128 || c.gau_s <= 0 ||
-      c.gau_s > 256 || c.gau_s % 8)
-    return why = "gau_hidden / gau_e powers of two (hidden <= 512, e >= 128), gau_s % 8 == 0 and <= 256", false;
+  if (!pow2(c.gau_hidden) || c.gau_hidden > 512 || !pow2(c.gau_e) || c.gau_e < 128 || c.gau_s <= 0 || c.gau_s % 8)
+    return why = "gau_hidden / gau_e powers of two (hidden <= 512, e >= 128), gau_s a positive multiple of 8", false;
+  // the token-mixing kernels hold one instance's tokens in LDS; judged at 136 tokens, the most `keypoints` admits,
+  // so the limit does not move with the keypoint count
+  if (!vge::gau_variant_ok(136, c.gau_e, c.gau_s, 0))
+    return why = "gau_s must be <= 160: beyond it the GAU token mixing of 136 tokens needs more than the 160 KB of "
+                 "LDS a workgroup can have (MFMA form " + std::to_string(vge::gau_mfma_lds_bytes(136, c.gau_s)) +
+                 " B, VALU form " + std::to_string(vge::gau_lds_bytes(c.gau_s)) + " B)", false;
   if (c.final_k <= 0 || c.final_k % 2 == 0 || c.final_k > 9) return why = "final_k must be odd and <= 9", false;
   if (c.split <= 0) return why = "split must be positive", false;
   const int hw = (c.in_h / 32) * (c.in_w / 32);
@@ -160,9 +165,26 @@ bool cfg_ok(const vge_rtmpose_config& c, std::string& why) {
   return true;
 }
 
-}  // namespace
+// onnxpose.bbox_xyxy2cs (padding 1.25) + _fix_aspect_ratio in float: the warp's affine map and the box center /
+// scale the keypoints are mapped back with (no contraction, so oracle.dwpose.affine_params reproduces every value)
+void box_instance(int frame, float x0, float y0, float x1, float y1, int in_w, int in_h, vge::WarpInst& wi,
+                  vge::PoseInst& pi) {
+#pragma clang fp contract(off)
+  const float cx = (x0 + x1) * 0.5f, cy = (y0 + y1) * 0.5f;
+  const float w = (x1 - x0) * 1.25f, h = (y1 - y0) * 1.25f;
+  const float ar = (float)in_w / (float)in_h;
+  float sw, sh;
+  if (w > h * ar) {
+    sw = w;
+    sh = w / ar;
+  } else {
+    sw = h * ar;
+    sh = h;
+  }
+  wi = {frame, cx, cy, sw / (float)in_w};
+  pi = {cx, cy, sw, sh};
+}
 
-namespace {
 std::string I(int i) { return std::to_string(i); }
 }  // namespace
 
@@ -348,20 +370,11 @@ int vge_dwpose_keypoints(vge_dwpose* m, const uint8_t* frames, int F, int H, int
   m->h_p.clear();
   m->h_iof.assign((size_t)2 * F, -1);
   auto add = [&](int f, float x0, float y0, float x1, float y1) {
-#pragma clang fp contract(off)
-    const float cx = (x0 + x1) * 0.5f, cy = (y0 + y1) * 0.5f;
-    const float w = (x1 - x0) * 1.25f, h = (y1 - y0) * 1.25f;
-    const float ar = (float)c.in_w / (float)c.in_h;
-    float sw, sh;
-    if (w > h * ar) {
-      sw = w;
-      sh = w / ar;
-    } else {
-      sw = h * ar;
-      sh = h;
-    }
-    m->h_w.push_back({f, cx, cy, sw / (float)c.in_w});
-    m->h_p.push_back({cx, cy, sw, sh});
+    vge::WarpInst wi;
+    vge::PoseInst pi;
+    box_instance(f, x0, y0, x1, y1, c.in_w, c.in_h, wi, pi);
+    m->h_w.push_back(wi);
+    m->h_p.push_back(pi);
   };
   for (int f = 0; f < F; ++f) {
     const int n = n_persons[f];
@@ -410,7 +423,7 @@ int vge_dwpose_keypoints(vge_dwpose* m, const uint8_t* frames, int F, int H, int
     const void* src = m->D;
     if (St.spp) {
       CONV(St.spp1, m->D, C, N, h, w, 1, m->SPP, 2 * C, s);
-      OTHER(1, vge::launch_spp_pool(m->SPP, 2 * C, N, h, w, C / 2, 5, 9, 13, s));
+      OTHER(1, vge::launch_spp_pool(m->SPP, 2 * C, N, h, w, C / 2, 5, 9, 13, 0, s));
       CONV(St.spp2, m->SPP, 2 * C, N, h, w, 1, m->X, C, s);
       src = m->X;
     }
@@ -445,7 +458,7 @@ int vge_dwpose_keypoints(vge_dwpose* m, const uint8_t* frames, int F, int H, int
   CONV(m->mlp, m->ha, m->hwp, (int)rows, 1, 1, 1, m->hx, Hd, s, 0, 1);
   OTHER(2, vge::launch_scalenorm_rows(m->hx, Hd, m->ln_g, rows, m->hxn, s));
   CONV(m->uv, m->hxn, Hd, (int)rows, 1, 1, 1, m->uvb, 2 * E + Sg, s, 1, 1);
-  OTHER(2, vge::launch_gau_attn(m->uvb, N, K, E, Sg, m->gamma, m->beta, m->go, s));
+  OTHER(2, vge::launch_gau_attn(m->uvb, N, K, E, Sg, m->gamma, m->beta, m->go, 0, s));
   CONV(m->o, m->go, E, (int)rows, 1, 1, 1, m->hy, Hd, s, 0, 0, 2, m->hx, Hd, m->rscale);
   float* logits = simcc ? simcc : m->logits;
   CONV(m->cls, m->hy, Hd, (int)rows, 1, 1, 1, logits, WX + WY, s, 0, 1);
@@ -482,5 +495,114 @@ int vge_op_conv_bf16(const void* x, long ldx, const void* w, const float* bias, 
   HIPCHK(vge::launch_conv_bf16(c, S(stream)));
   return VGE_OK;
 }
+
+// ------------------------------------------------------------------ op-level entry points of the non-GEMM kernels
+// (tests): arguments are checked, then the launcher the model calls runs and nothing else.
+#define OP_REFUSE(cond, msg) \
+  if (cond) return fail(VGE_ERR_ARG, std::string(OP) + ": " + (msg))
+
+int vge_op_dwconv_bf16(const void* x, long ldx, const float* w, const float* b, void* y, long ldy, int n_img, int H,
+                       int W, int C, int K, vge_stream_t stream) {
+  static const char* OP = "vge_op_dwconv_bf16";
+  OP_REFUSE(K != 3 && K != 5 && K != 55, "K must be 3, 5 or 55 (5 x 5, one thread per output)");
+  OP_REFUSE(C <= 0 || C % 8, "C must be a positive multiple of 8");
+  OP_REFUSE(ldx < C || ldy < C || ldx % 8 || ldy % 8, "ldx / ldy must be multiples of 8 and >= C");
+  OP_REFUSE(n_img <= 0 || H <= 0 || W <= 0, "n_img, H, W must be positive");
+  OP_REFUSE(!x || !w || !b || !y, "null pointer");
+  HIPCHK(vge::launch_dwconv(x, ldx, w, b, y, ldy, n_img, H, W, C, K, S(stream)));
+  return VGE_OK;
+}
+
+int vge_op_spp_pool_bf16(void* buf, long ld, int n_img, int H, int W, int C, int k0, int k1, int k2, int variant,
+                         vge_stream_t stream) {
+  static const char* OP = "vge_op_spp_pool_bf16";
+  OP_REFUSE(C <= 0 || C % 8, "C must be a positive multiple of 8");
+  OP_REFUSE(ld < 4L * C || ld % 8, "ld must be a multiple of 8 and >= 4 C (the input and its three pools)");
+  OP_REFUSE(n_img <= 0 || H <= 0 || W <= 0, "n_img, H, W must be positive");
+  OP_REFUSE(k0 <= 0 || k0 % 2 == 0 || k1 % 2 == 0 || k2 % 2 == 0 || k0 > k1 || k1 > k2,
+            "pool sizes must be odd and ascending");
+  OP_REFUSE(variant < 0 || variant > 2, "variant must be 0 (auto), 1 (generic) or 2 (LDS)");
+  OP_REFUSE(variant == 2 && !vge::spp_lds_ok(H, W, k0, k1, k2),
+            "variant 2 (LDS) takes pools 5 / 9 / 13 on maps of <= 400 positions only");
+  OP_REFUSE(!buf, "null pointer");
+  HIPCHK(vge::launch_spp_pool(buf, ld, n_img, H, W, C, k0, k1, k2, variant, S(stream)));
+  return VGE_OK;
+}
+
+int vge_op_chan_attn_bf16(void* x, long ld, int n_img, int HW, int C, const float* Wt, const float* b, float* mean,
+                          float* att, vge_stream_t stream) {
+  static const char* OP = "vge_op_chan_attn_bf16";
+  OP_REFUSE(C <= 0 || C % 8 || C > 2048, "C must be a multiple of 8 in [8, 2048]");
+  OP_REFUSE(ld < C || ld % 8, "ld must be a multiple of 8 and >= C");
+  OP_REFUSE(n_img <= 0 || HW <= 0, "n_img, HW must be positive");
+  OP_REFUSE(!x || !Wt || !b || !mean || !att, "null pointer");
+  HIPCHK(vge::launch_chan_attn(x, ld, n_img, HW, C, Wt, b, mean, att, S(stream)));
+  return VGE_OK;
+}
+
+int vge_op_warp_prep(const uint8_t* frames, int n_frames, int H, int W, const float* boxes, const int* frame_of,
+                     int n_inst, int in_h, int in_w, void* inst, void* out, vge_stream_t stream) {
+  static const char* OP = "vge_op_warp_prep";
+  OP_REFUSE(n_frames <= 0 || H <= 0 || W <= 0 || n_inst <= 0 || in_h <= 0 || in_w <= 0,
+            "n_frames, H, W, n_inst, in_h, in_w must be positive");
+  OP_REFUSE(!frames || !boxes || !frame_of || !inst || !out, "null pointer");
+  std::vector<vge::WarpInst> tab((size_t)n_inst);
+  for (int i = 0; i < n_inst; ++i) {
+    OP_REFUSE(frame_of[i] < 0 || frame_of[i] >= n_frames, "frame index out of range");
+    vge::PoseInst unused;
+    const float* bx = boxes + (size_t)i * 4;
+    box_instance(frame_of[i], bx[0], bx[1], bx[2], bx[3], in_w, in_h, tab[i], unused);
+  }
+  HIPCHK(hipMemcpy(inst, tab.data(), tab.size() * sizeof(vge::WarpInst), hipMemcpyHostToDevice));
+  HIPCHK(vge::launch_warp_prep(frames, H, W, inst, n_inst, in_h, in_w, out, S(stream)));
+  return VGE_OK;
+}
+
+int vge_op_head_scalenorm_t(const float* y, long ldy, int hw, int K, int Kp, float g, long n_rows, void* out,
+                            vge_stream_t stream) {
+  static const char* OP = "vge_op_head_scalenorm_t";
+  OP_REFUSE(hw <= 0 || hw > 256 || Kp > 256 || Kp < hw, "hw and Kp must be <= 256 (4 values per lane) with hw <= Kp");
+  OP_REFUSE(K <= 0 || ldy < K, "ldy must be >= K");
+  OP_REFUSE(n_rows <= 0 || n_rows % K, "n_rows must be a positive multiple of K");
+  OP_REFUSE(!y || !out, "null pointer");
+  HIPCHK(vge::launch_head_sn_t(y, ldy, hw, K, Kp, g, n_rows, out, S(stream)));
+  return VGE_OK;
+}
+
+int vge_op_scalenorm_rows(const float* x, int D, float g, long rows, void* y, vge_stream_t stream) {
+  static const char* OP = "vge_op_scalenorm_rows";
+  OP_REFUSE(D <= 0 || D > 512, "D must be in [1, 512] (8 values per lane)");
+  OP_REFUSE(rows <= 0, "rows must be positive");
+  OP_REFUSE(!x || !y, "null pointer");
+  HIPCHK(vge::launch_scalenorm_rows(x, D, g, rows, y, S(stream)));
+  return VGE_OK;
+}
+
+int vge_op_gau_attn(const float* uv, int n_inst, int K, int E, int Sg, const float* gamma, const float* beta, void* out,
+                    int variant, vge_stream_t stream) {
+  static const char* OP = "vge_op_gau_attn";
+  OP_REFUSE(variant < 0 || variant > 2, "variant must be 0 (auto), 1 (VALU) or 2 (MFMA)");
+  OP_REFUSE(n_inst <= 0 || K <= 0 || Sg <= 0 || E <= 0 || E % 128, "n_inst, K, S positive, E a positive multiple of 128");
+  OP_REFUSE(variant == 1 && K > 136, "variant 1 (VALU) takes K <= 136 tokens");
+  OP_REFUSE(!vge::gau_variant_ok(K, E, Sg, variant),
+            "LDS need above the 160 KB limit or shape not taken (MFMA form: K <= 160, S even, " +
+                std::to_string(vge::gau_mfma_lds_bytes(K, Sg)) + " B; VALU form: K <= 136, " +
+                std::to_string(vge::gau_lds_bytes(Sg)) + " B)");
+  OP_REFUSE(!uv || !gamma || !beta || !out, "null pointer");
+  HIPCHK(vge::launch_gau_attn(uv, n_inst, K, E, Sg, gamma, beta, out, variant, S(stream)));
+  return VGE_OK;
+}
+
+int vge_op_simcc_decode(const float* logits, long ld, int WX, int WY, float split, long rows, float* lv,
+                        vge_stream_t stream) {
+  static const char* OP = "vge_op_simcc_decode";
+  OP_REFUSE(WX <= 0 || WY <= 0 || ld < (long)WX + WY, "ld must be >= WX + WY, both positive");
+  OP_REFUSE(!(split > 0.f) || rows <= 0, "split and rows must be positive");
+  OP_REFUSE(!logits || !lv, "null pointer");
+  HIPCHK(vge::launch_simcc_decode(logits, ld, WX, WY, split, rows, lv, S(stream)));
+  return VGE_OK;
+}
+
+#undef OP_REFUSE
 
 }  // extern "C"

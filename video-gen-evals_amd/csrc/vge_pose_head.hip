@@ -72,7 +72,8 @@ __global__ void __launch_bounds__(256) scalenorm_rows_kernel(const float* __rest
 }
 
 // One workgroup (4 waves) per instance.  uv [inst * K + t][2E + S] f32 (SiLU already applied): u = cols
-// [0, E), v = [E, 2E), base = [2E, 2E + S).  LDS: k-matrix [K][S + 1], kernel [K][KP], one q row per wave.
+// [0, E), v = [E, 2E), base = [2E, 2E + S).  LDS: k-matrix [K][S + 1] (later the v chunk [K][128]: the region is sized
+// for the wider of the two, so a chunk never reaches the kernel matrix behind it), kernel [K][KP], one q row per wave.
 template <int KMAX>
 __global__ void __launch_bounds__(256) gau_attn_kernel(const float* __restrict__ uv, int K, int E, int S,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -81,7 +82,7 @@ __global__ void __launch_bounds__(256) gau_attn_kernel(const float* __restrict__
   constexpr int KP = KMAX + 1;
   const int SP = S + 1;
   float* kk = sm;                       // [K][SP]
-  float* A = kk + KMAX * SP;            // [K][KP]
+  float* A = kk + KMAX * max(SP, 128);  // [K][KP]
   float* qrow = A + KMAX * KP;          // [4][S]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long base_row = (long)blockIdx.x * K;
@@ -423,33 +424,46 @@ hipError_t launch_scalenorm_rows(const float* x, int D, float g, long rows, void
 
 constexpr int GAU_KMAX = 136;
 
-size_t gau_lds_bytes(int S) { return sizeof(float) * ((size_t)GAU_KMAX * (S + 1) + GAU_KMAX * (GAU_KMAX + 1) + 4 * S); }
+// k-matrix rows of S + 1 floats, later the 128-column v chunk: the region holds whichever is larger
+size_t gau_lds_bytes(int S) {
+  return sizeof(float) * ((size_t)GAU_KMAX * std::max(S + 1, 128) + GAU_KMAX * (GAU_KMAX + 1) + 4 * S);
+}
 
 size_t gau_mfma_lds_bytes(int K, int S) {
   const int KP2 = (K + 1) & ~1;
   return sizeof(float) * ((size_t)std::max(K * (S + 1), KP2 * 160) + (size_t)K * (K | 1));
 }
 
+bool gau_variant_ok(int K, int E, int S, int variant) {
+  if (K <= 0 || S <= 0 || E <= 0 || E % 128) return false;
+  const bool valu = K <= GAU_KMAX && gau_lds_bytes(S) <= GAU_LDS_LIMIT;
+  const bool mfma = K <= GAU_M_TILES * 32 && S % 2 == 0 && gau_mfma_lds_bytes(K, S) <= GAU_LDS_LIMIT;
+  return variant == 1 ? valu : variant == 2 ? mfma : variant == 0 ? (valu || mfma) : false;
+}
+
 hipError_t launch_gau_attn(const float* uv, int n_inst, int K, int E, int S, const float* gamma, const float* beta,
-                           void* out, hipStream_t s) {
+                           void* out, int variant, hipStream_t s) {
+  if (!gau_variant_ok(K, E, S, variant)) return hipErrorInvalidValue;
   if (n_inst == 0) return hipSuccess;
-  static int use_valu = -1;  // VGE_GAU_VALU=1: the VALU kernel (A/B timing)
+  static int use_valu = -1;  // VGE_GAU_VALU=1: the VALU kernel where it applies (A/B timing)
   if (use_valu < 0) {
     const char* e = getenv("VGE_GAU_VALU");
     use_valu = (e && atoi(e) == 1) ? 1 : 0;
   }
-  const size_t mb = gau_mfma_lds_bytes(K, S);
-  if (!use_valu && K <= GAU_M_TILES * 32 && S % 2 == 0 && E % 128 == 0 && mb <= 160 * 1024) {
+  if (variant == 0) variant = gau_variant_ok(K, E, S, use_valu ? 1 : 2) ? (use_valu ? 1 : 2) : (use_valu ? 2 : 1);
+  if (variant == 2) {
     static LdsAttrOnce mattr;
-    if (const hipError_t e = mattr(reinterpret_cast<const void*>(&gau_mfma_kernel), 160 * 1024); e != hipSuccess) return e;
-    hipLaunchKernelGGL(gau_mfma_kernel, dim3(n_inst), dim3(256), mb, s, uv, K, E, S, gamma, beta,
+    if (const hipError_t e = mattr(reinterpret_cast<const void*>(&gau_mfma_kernel), (int)GAU_LDS_LIMIT); e != hipSuccess)
+      return e;
+    hipLaunchKernelGGL(gau_mfma_kernel, dim3(n_inst), dim3(256), gau_mfma_lds_bytes(K, S), s, uv, K, E, S, gamma, beta,
                        (float)std::sqrt((double)S), static_cast<bf16*>(out));
     return hipGetLastError();
   }
-  const size_t bytes = gau_lds_bytes(S);
   static LdsAttrOnce attr;
-  if (const hipError_t e = attr(reinterpret_cast<const void*>(&gau_attn_kernel<GAU_KMAX>), 160 * 1024); e != hipSuccess) return e;
-  hipLaunchKernelGGL(gau_attn_kernel<GAU_KMAX>, dim3(n_inst), dim3(256), bytes, s, uv, K, E, S, gamma, beta,
+  if (const hipError_t e = attr(reinterpret_cast<const void*>(&gau_attn_kernel<GAU_KMAX>), (int)GAU_LDS_LIMIT);
+      e != hipSuccess)
+    return e;
+  hipLaunchKernelGGL(gau_attn_kernel<GAU_KMAX>, dim3(n_inst), dim3(256), gau_lds_bytes(S), s, uv, K, E, S, gamma, beta,
                      (float)std::sqrt((double)S), static_cast<bf16*>(out));
   return hipGetLastError();
 }

@@ -159,6 +159,18 @@ bool cfg_ok(const vge_yolox_config& c, std::string& why) {
   return true;
 }
 
+// onnxdet.preprocess' letterbox of an H x W frame into S x S: r = min(S / H, S / W), the resized extent (rh, rw) and
+// the source steps per canvas pixel the resize kernel walks with; false = the frame is too small (an empty extent)
+bool letterbox_geometry(int H, int W, int S, double& r, int& rh, int& rw, float& inv_rx, float& inv_ry) {
+  r = std::min((double)S / H, (double)S / W);
+  rh = (int)(H * r);
+  rw = (int)(W * r);
+  if (rh <= 0 || rw <= 0) return false;
+  inv_rx = (float)((double)W / rw);
+  inv_ry = (float)((double)H / rh);
+  return true;
+}
+
 // CSPLayer: out = conv3(cat(m(conv1(x)), conv2(x))); conv1 | conv2 write [x_1 | x_2] into the concat buffer and the
 // last Bottleneck overwrites x_1 in place (its identity read and its store touch the same element)
 int ycsp(vge_yolox* m, const YCsp& L, const void* x, long ldx, int n, int h, int w, void* out, long ldo,
@@ -262,10 +274,11 @@ int vge_yolox_detect_scored(vge_yolox* m, const uint8_t* frames, int F, int H, i
   if (m->chunk <= 0) return fail(VGE_ERR_WORKSPACE, "vge_yolox_detect: call vge_yolox_reserve first");
   const vge_yolox_config& c = m->c;
   const int Sz = c.in_size, w0 = c.width, hc = c.head_ch;
-  const double r = std::min((double)Sz / H, (double)Sz / W);
-  const int rh = (int)(H * r), rw = (int)(W * r);
-  if (rh <= 0 || rw <= 0) return fail(VGE_ERR_ARG, "vge_yolox_detect: frame too small for the letterbox");
-  const float inv_rx = (float)((double)W / rw), inv_ry = (float)((double)H / rh);
+  double r;
+  int rh, rw;
+  float inv_rx, inv_ry;
+  if (!letterbox_geometry(H, W, Sz, r, rh, rw, inv_rx, inv_ry))
+    return fail(VGE_ERR_ARG, "vge_yolox_detect: frame too small for the letterbox");
   const int A = (Sz / 8) * (Sz / 8) + (Sz / 16) * (Sz / 16) + (Sz / 32) * (Sz / 32);
   hipStream_t s = S(stream);
   (void)A;
@@ -292,7 +305,7 @@ int vge_yolox_detect_scored(vge_yolox* m, const uint8_t* frames, int F, int H, i
     CSP(m->c4, m->B, c4, n, h16, h16, cat16 + c4, 2 * c4);              // x1 -> second half of Cat16
     CONV(m->d5, cat16 + c4, 2 * c4, n, h16, h16, 2, m->B, c5, s);
     CONV(m->spp1, m->B, c5, n, h32, h32, 1, m->SPP, 2 * c5, s);
-    OTHER(vge::launch_spp_pool(m->SPP, 2 * c5, n, h32, h32, c5 / 2, 5, 9, 13, s));
+    OTHER(vge::launch_spp_pool(m->SPP, 2 * c5, n, h32, h32, c5 / 2, 5, 9, 13, 0, s));
     CONV(m->spp2, m->SPP, 2 * c5, n, h32, h32, 1, m->B2, c5, s);
     CSP(m->c5, m->B2, c5, n, h32, h32, m->X0, c5);
     CONV(m->lat0, m->X0, c5, n, h32, h32, 1, pcat32 + c4, 2 * c4, s);   // fpn_out0 -> second half of Pcat32
@@ -328,5 +341,50 @@ int vge_yolox_detect_scored(vge_yolox* m, const uint8_t* frames, int F, int H, i
   m->prof.end_call(m->gemm_flops);
   return VGE_OK;
 }
+
+// ------------------------------------------------------------------ op-level entry points (tests): arguments are
+// checked, then the launcher the model calls runs and nothing else.
+#define OP_REFUSE(cond, msg) \
+  if (cond) return fail(VGE_ERR_ARG, std::string(OP) + ": " + (msg))
+
+int vge_op_letterbox_focus(const uint8_t* frames, int n_frames, int H, int W, int Sz, void* out, vge_stream_t stream) {
+  static const char* OP = "vge_op_letterbox_focus";
+  OP_REFUSE(n_frames <= 0 || H <= 0 || W <= 0, "n_frames, H, W must be positive");
+  OP_REFUSE(Sz <= 0 || Sz % 2, "S must be positive and even (Focus halves it)");
+  double r;
+  int rh, rw;
+  float inv_rx, inv_ry;
+  OP_REFUSE(!letterbox_geometry(H, W, Sz, r, rh, rw, inv_rx, inv_ry), "frame too small for the letterbox");
+  OP_REFUSE(!frames || !out, "null pointer");
+  HIPCHK(vge::launch_letterbox_focus(frames, n_frames, H, W, Sz, rh, rw, inv_rx, inv_ry, out, S(stream)));
+  return VGE_OK;
+}
+
+int vge_op_upsample2x_bf16(const void* x, long ldx, void* y, long ldy, int n_img, int H, int W, int C,
+                           vge_stream_t stream) {
+  static const char* OP = "vge_op_upsample2x_bf16";
+  OP_REFUSE(C <= 0 || C % 8, "C must be a positive multiple of 8");
+  OP_REFUSE(ldx < C || ldy < C || ldx % 8 || ldy % 8, "ldx / ldy must be multiples of 8 and >= C");
+  OP_REFUSE(n_img <= 0 || H <= 0 || W <= 0, "n_img, H, W must be positive");
+  OP_REFUSE(!x || !y, "null pointer");
+  HIPCHK(vge::launch_upsample2x(x, ldx, y, ldy, n_img, H, W, C, S(stream)));
+  return VGE_OK;
+}
+
+int vge_op_yolox_decode_nms(const float* out0, const float* out1, const float* out2, int grid0, int grid1, int grid2,
+                            int stride0, int stride1, int stride2, int n_frames, float ratio, float* boxes,
+                            int* n_persons, float* scores, float* cand, vge_stream_t stream) {
+  static const char* OP = "vge_op_yolox_decode_nms";
+  OP_REFUSE(grid0 <= 0 || grid1 <= 0 || grid2 <= 0 || grid0 > 1024 || grid1 > 1024 || grid2 > 1024,
+            "grids must be in [1, 1024]");
+  OP_REFUSE(stride0 <= 0 || stride1 <= 0 || stride2 <= 0, "strides must be positive");
+  OP_REFUSE(n_frames <= 0 || !(ratio > 0.f), "n_frames and ratio must be positive");
+  OP_REFUSE(!out0 || !out1 || !out2 || !boxes || !n_persons, "null pointer");
+  const vge::DetLevel L0{out0, grid0, stride0}, L1{out1, grid1, stride1}, L2{out2, grid2, stride2};
+  HIPCHK(vge::launch_yolox_decode_nms(L0, L1, L2, n_frames, ratio, boxes, n_persons, scores, cand, S(stream)));
+  return VGE_OK;
+}
+
+#undef OP_REFUSE
 
 }  // extern "C"

@@ -163,6 +163,18 @@ _SIG = {
     "vge_dwpose_profile_read": [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double)],
     "vge_op_conv_bf16": [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                          _i32, _i32, _i32, _i32, _vp],
+    "vge_op_dwconv_bf16": [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp],
+    "vge_op_spp_pool_bf16": [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
+    "vge_op_chan_attn_bf16": [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
+    "vge_op_upsample2x_bf16": [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp],
+    "vge_op_warp_prep": [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
+    "vge_op_letterbox_focus": [_vp, _i32, _i32, _i32, _i32, _vp, _vp],
+    "vge_op_head_scalenorm_t": [_vp, _i64, _i32, _i32, _i32, C.c_float, _i64, _vp, _vp],
+    "vge_op_scalenorm_rows": [_vp, _i32, C.c_float, _i64, _vp, _vp],
+    "vge_op_gau_attn": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp],
+    "vge_op_simcc_decode": [_vp, _i64, _i32, _i32, C.c_float, _i64, _vp, _vp],
+    "vge_op_yolox_decode_nms": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp, _vp, _vp,
+                                _vp],
     "vge_yolox_create": [C.POINTER(YoloxConfigC), C.POINTER(L.TensorView), _i32, C.POINTER(_vp)],
     "vge_yolox_reserve": [_vp, _i32],
     "vge_yolox_destroy": [_vp],
@@ -322,3 +334,72 @@ def conv_bf16(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, stride: int 
                                  Cout if res is not None else 0, _ptr(rs) if rs is not None else None, n, H, W, Cin, KH, KW,
                                  stride, pad, Cout, actc, int(out_f32), mode, _stream(x.device)), "vge_op_conv_bf16")
     return out
+
+
+# ---- op-level entry points of the kernels around the dense layers (parity tests) -------------------
+# Thin wrappers of include/vge_dwpose.h's vge_op_*: tensors are passed by their first element, so a caller may hand in
+# a view into a larger buffer (guard rows around it, a pixel stride `ld` wider than the channels used).
+def _dp(t: Optional[torch.Tensor]) -> Optional[int]:
+    if t is None:
+        return None
+    if not t.is_cuda:
+        raise L.VgeError("vge ops need device (cuda/HIP) tensors")
+    return t.data_ptr()
+
+
+def _op(name: str, *args) -> None:
+    L.check(getattr(_sig(L.load()), name)(*args), name)
+
+
+def dwconv_bf16(x, ldx: int, w, b, y, ldy: int, n: int, H: int, W: int, Cc: int, K: int) -> None:
+    _op("vge_op_dwconv_bf16", _dp(x), ldx, _dp(w), _dp(b), _dp(y), ldy, n, H, W, Cc, K, _stream(x.device))
+
+
+def spp_pool_bf16(buf, ld: int, n: int, H: int, W: int, Cc: int, ks=(5, 9, 13), variant: int = 0) -> None:
+    _op("vge_op_spp_pool_bf16", _dp(buf), ld, n, H, W, Cc, ks[0], ks[1], ks[2], variant, _stream(buf.device))
+
+
+def chan_attn_bf16(x, ld: int, n: int, HW: int, Cc: int, Wt, b, mean, att) -> None:
+    _op("vge_op_chan_attn_bf16", _dp(x), ld, n, HW, Cc, _dp(Wt), _dp(b), _dp(mean), _dp(att), _stream(x.device))
+
+
+def upsample2x_bf16(x, ldx: int, y, ldy: int, n: int, H: int, W: int, Cc: int) -> None:
+    _op("vge_op_upsample2x_bf16", _dp(x), ldx, _dp(y), ldy, n, H, W, Cc, _stream(x.device))
+
+
+def warp_prep(frames: torch.Tensor, boxes: np.ndarray, frame_of: np.ndarray, in_h: int, in_w: int, out) -> None:
+    """frames uint8 [F, H, W, 3] on the device; boxes host [n, 4] xyxy, frame_of host [n]; out bf16 [n, in_h, in_w, 8]."""
+    F_, H_, W_ = (int(v) for v in frames.shape[:3])
+    bx = np.ascontiguousarray(boxes, dtype=np.float32)
+    fo = np.ascontiguousarray(frame_of, dtype=np.int32)
+    inst = torch.empty((len(fo), 4), dtype=torch.float32, device=frames.device)
+    _op("vge_op_warp_prep", _ptr(frames), F_, H_, W_, bx.ctypes.data, fo.ctypes.data, len(fo), in_h, in_w, _ptr(inst),
+        _dp(out), _stream(frames.device))
+
+
+def letterbox_focus(frames: torch.Tensor, S: int, out) -> None:
+    """frames uint8 [F, H, W, 3] on the device -> out bf16 [F, S/2, S/2, 16]."""
+    F_, H_, W_ = (int(v) for v in frames.shape[:3])
+    _op("vge_op_letterbox_focus", _ptr(frames), F_, H_, W_, S, _dp(out), _stream(frames.device))
+
+
+def head_scalenorm_t(y, ldy: int, hw: int, K: int, Kp: int, g: float, n_rows: int, out) -> None:
+    _op("vge_op_head_scalenorm_t", _dp(y), ldy, hw, K, Kp, g, n_rows, _dp(out), _stream(y.device))
+
+
+def scalenorm_rows(x, D: int, g: float, rows: int, y) -> None:
+    _op("vge_op_scalenorm_rows", _dp(x), D, g, rows, _dp(y), _stream(x.device))
+
+
+def gau_attn(uv, n: int, K: int, E: int, S: int, gamma, beta, out, variant: int = 0) -> None:
+    _op("vge_op_gau_attn", _dp(uv), n, K, E, S, _dp(gamma), _dp(beta), _dp(out), variant, _stream(uv.device))
+
+
+def simcc_decode(logits, ld: int, WX: int, WY: int, split: float, rows: int, lv) -> None:
+    _op("vge_op_simcc_decode", _dp(logits), ld, WX, WY, split, rows, _dp(lv), _stream(logits.device))
+
+
+def yolox_decode_nms(outs, grids, strides, F_: int, ratio: float, boxes, n_persons, scores=None, cand=None) -> None:
+    """outs: three f32 [F, g*g, 8] level tensors (reg xywh, obj logit, cls-0 logit, 2 unused)."""
+    _op("vge_op_yolox_decode_nms", _dp(outs[0]), _dp(outs[1]), _dp(outs[2]), *grids, *strides, F_, ratio, _dp(boxes),
+        _dp(n_persons), _dp(scores), _dp(cand), _stream(boxes.device))

@@ -30,6 +30,9 @@ EXPORTS = ["vge_featurize", "vge_featurize_layout", "vge_layout_feat_dim", "vge_
            "vge_hmr_profile_read", "vge_op_gemm_bf16", "vge_op_gemm_lib", "vge_op_vit_attention", "vge_op_layernorm_bf16",
            "vge_dwpose_create", "vge_dwpose_reserve", "vge_dwpose_destroy", "vge_dwpose_keypoints",
            "vge_dwpose_profile_begin", "vge_dwpose_profile_read", "vge_op_conv_bf16",
+           "vge_op_dwconv_bf16", "vge_op_spp_pool_bf16", "vge_op_chan_attn_bf16", "vge_op_upsample2x_bf16",
+           "vge_op_warp_prep", "vge_op_letterbox_focus", "vge_op_head_scalenorm_t", "vge_op_scalenorm_rows",
+           "vge_op_gau_attn", "vge_op_simcc_decode", "vge_op_yolox_decode_nms",
            "vge_yolox_create", "vge_yolox_reserve", "vge_yolox_destroy", "vge_yolox_detect", "vge_yolox_detect_scored",
            "vge_hmr_crop",
            "vge_yolox_profile_begin", "vge_yolox_profile_read",
