@@ -192,6 +192,83 @@ def test_gemm_persistent_matches_one_tile_kernel(H, M, N, K, epi):
     assert torch.equal(outs[0], outs[1]), (outs[0].float() - outs[1].float()).abs().max().item()
 
 
+def _set_gemm_waves(mode):
+    import ctypes as C
+    from vge import lib as Lb
+    lib = Lb.load()
+    lib.vge_debug_set_gemm_waves.argtypes = [C.c_int]
+    lib.vge_debug_set_gemm_waves(mode)
+
+
+@gpu
+@pytest.mark.parametrize("epi", ["bf16", "gelu_bf16", "res_f32", "pe_f32", "f32"])
+@pytest.mark.parametrize("M,N,K", [(256, 256, 64), (512, 512, 192)])
+def test_gemm_wave_modes_match_default(H, M, N, K, epi):
+    """The GEMM's wave modes (2 = gemm2_bf16_kernel's 128 x 256 tiles with swapped MFMA operands, 4 = four waves of
+    128 x 128, 8 / 16 = the 8-wave kernel forced to 32x32x16 / 16x16x32) against the default choice by epilogue (1):
+    every form accumulates the same products in the same K order (32-deep stages of two 16-k steps) and applies the
+    same epilogue operations in the same order -> bit-identical.  (256, 256, 64) is one tile with two K stages, the
+    shortest ring the kernels accept; (512, 512, 192) is four tiles in two column panels with six stages, so the 3-slot
+    and the 5-slot rings both wrap.  (Before the LDS ordering point in its epilogue, mode 4 differed from the default by
+    5.9-7.2 on res_f32 and pe_f32 at both shapes, in rows 4 k + 3 of its LDS transpose: DESIGN 3.7.)"""
+    if epi == "pe_f32":
+        M = 768
+    A = _bf((M, K), 1.0, 21).to(DEV)
+    W = _bf((N, K), K ** -0.5, 22).to(DEV)
+    kw = dict(bias=(torch.randn(N, generator=torch.Generator().manual_seed(23)) * 0.1).to(DEV))
+    if epi == "res_f32":
+        kw["res"] = torch.randn(M, N, generator=torch.Generator().manual_seed(24)).to(DEV)
+    if epi == "pe_f32":
+        kw["pos"] = torch.randn(193, N, generator=torch.Generator().manual_seed(25)).to(DEV)
+    outs = {}
+    try:
+        for mode in (1, 2, 4, 8, 16):
+            _set_gemm_waves(mode)
+            outs[mode] = H.gemm_bf16(A, W, epi, **kw)
+            torch.cuda.synchronize()
+    finally:
+        _set_gemm_waves(1)
+    assert torch.isfinite(outs[1].float()).all()
+    for mode in (2, 4, 8, 16):
+        assert torch.equal(outs[1], outs[mode]), (mode, (outs[1].float() - outs[mode].float()).abs().max().item())
+
+
+@gpu
+@pytest.mark.parametrize("n,Hh,Ww,Cin,Cout,act,res", [
+    (4, 25, 25, 1024, 1024, "relu", None),   # M = 2500: ragged last 256-row and 128-row tile
+    (3, 13, 17, 512, 512, "relu", "pre"),    # M = 663, bf16 residual before the ReLU
+])
+def test_gemm_wave_modes_partial_m_match_default_conv(n, Hh, Ww, Cin, Cout, act, res):
+    """The partial-M instantiations of the same modes, reached through a 1x1 conv with variant 9 forced (ragged shapes of
+    test_dwpose.py::test_conv_1x1_gemm_variant_matches_default): bit-identical to the default conv kernel."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import ctypes as C
+    from vge import dwpose as D
+    from vge import lib as Lb
+    lib = Lb.load()
+    lib.vge_debug_set_conv_variant.argtypes = [C.c_int]
+    x = _bf((n, Hh, Ww, Cin), seed=31).to(DEV)
+    w = _bf((Cout, Cin, 1, 1), (2.0 / Cin) ** 0.5, seed=32).to(DEV)
+    b = (torch.randn(Cout, generator=torch.Generator().manual_seed(33)) * 0.1).to(DEV)
+    r = _bf((n, Hh, Ww, Cout), seed=34).to(DEV) if res else None
+    conv = lambda: D.conv_bf16(x, w, b, stride=1, pad=0, act=act, res=r, res_pre=res == "pre")  # noqa: E731
+    want = conv()
+    outs = {}
+    try:
+        lib.vge_debug_set_conv_variant(9)
+        for mode in (1, 2, 4, 8, 16):
+            _set_gemm_waves(mode)
+            outs[mode] = conv()
+            torch.cuda.synchronize()
+    finally:
+        lib.vge_debug_set_conv_variant(0)
+        _set_gemm_waves(1)
+    assert torch.isfinite(want.float()).all()
+    for mode, got in outs.items():
+        assert torch.equal(want, got), (mode, (want.float() - got.float()).abs().max().item())
+
+
 @gpu
 @pytest.mark.parametrize("epi", ["bf16", "res_f32", "f32"])
 @pytest.mark.parametrize("M,N,K", [(49152, 3840, 1280), (12288, 1280, 5120), (1000, 256, 64), (333, 768, 1024)])

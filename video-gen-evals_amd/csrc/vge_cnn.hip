@@ -8,7 +8,8 @@
 //       in the zero padding (and K / M padding) read a zero page instead of being masked, so the LDS ring is
 //       filled exactly like a dense GEMM's.  128 x TN output tile per 256-thread workgroup, 32-deep K stages in
 //       a 3-slot ring, LDS image XOR-swizzled on the source address (conflict-free ds_read_b128 fragments),
-//       XCD-contiguous tile ranges.  Epilogue through LDS, row-major: + bias (folded BatchNorm), SiLU /
+//       XCD-contiguous tile ranges (the pieces shared with the GEMM kernels: vge_bf16_tile.h).  Epilogue through LDS,
+//       row-major: + bias (folded BatchNorm), SiLU /
 //       sigmoid, + residual (bf16 identity of CSPNeXtBlock, or f32 x per-column scale for RTMCCBlock's
 //       res_scale), bf16 or f32 store.  Every nn.Linear of the head runs here too (1x1 "image").
 //   dwconv_kernel        depthwise KxK conv + folded BN + SiLU (one thread = 8 channels of one pixel).
@@ -18,7 +19,7 @@
 //   warp_prep_kernel     onnxpose.preprocess: per-instance affine crop (bilinear, border 0, uint8 round) of the
 //                        RGB frame, BGR mean/std normalisation -> NHWC bf16 with 8 channels (3 used).
 //   letterbox_focus_kernel  onnxdet.preprocess (resize by r, pad 114) + YOLOX Focus space-to-depth -> 16 ch.
-#include "vge_common.h"
+#include "vge_bf16_tile.h"
 #include "vge_lds_attr.h"
 #include "vge_cnn.h"
 #include "vge_gemm.h"
@@ -28,12 +29,6 @@
 #include <type_traits>
 
 namespace {
-
-typedef __bf16 bf16;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef unsigned uintx2_t __attribute__((ext_vector_type(2)));
-typedef unsigned uintx4_t __attribute__((ext_vector_type(4)));
 
 constexpr int CV_M = 128, CV_K = 32, CV_ST = 3;
 
@@ -55,11 +50,6 @@ struct ConvArgs {
                        // n0 .. n0 + Cin - 1 (Cin = the tile width; weights [Cout][taps * Cin], zero off the groups)
 };
 
-__device__ __forceinline__ int xcd_remap(int b, int nblk) {  // bijective: each XCD takes a contiguous range
-  const int q8 = nblk >> 3, r8 = nblk & 7, x8 = b & 7;
-  return (x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8) + (b >> 3);
-}
-
 // Implicit-GEMM gather state of one A row (the tile rows a lane fetches): the address of the row's (kh, kw) = (0, 0)
 // tap plus this lane's 16-B chunk (lc8 = 8 lc channels), and (ih0 << 16) | (iw0 & 0xFFFF) (a row past M gets ih0 =
 // -16384, which fails every tap's bounds check).
@@ -77,10 +67,6 @@ __device__ __forceinline__ RowState row_state(const ConvArgs& a, int m, int lc8)
   const long off = m < a.M ? ((long)img * a.H + ih0) * a.W + iw0 : 0;
   return {a.x + off * a.ldx + lc8, (ih0 << 16) | (iw0 & 0xFFFF)};
 }
-// The 32-k stage starting at k0 of NR rows into LDS (row j's 1 KB wave-instruction at dst(j)).  Cin >= 32: the stage
-// lies inside one tap, so the tap, its (kh, kw) and the channel base are uniform (scalar) and a row's source is its
-// base + one scalar offset; Cin 8 / 16: a lane's chunk may fall in the next tap (per-lane tap).  Taps outside the
-// image, past the kernel's taps, and rows past M read the zero page.
 // The sources of the 32-k stage starting at k0 for NR rows: src[j] = row j's source or the zero page (taps outside
 // the image, past the kernel's taps, rows past M).  Cin >= 32: the stage lies inside one tap, so the tap, its (kh, kw)
 // and the channel base are uniform (scalar) and a row's source is its base + one scalar offset; Cin 8 / 16: a lane's
@@ -278,7 +264,7 @@ __global__ void __launch_bounds__(256) conv_bf16_kernel(ConvArgs a) {
 }
 
 // ------------------------------------------------------------------------------------ conv v2 (wide tiles)
-// The same implicit GEMM on 256 x BN tiles with 8 waves and gemm_bf16_kernel's schedule (vge_vit.hip): 32-deep
+// The same implicit GEMM on 256 x BN tiles with 8 waves and the 8-wave GEMM's schedule (vge_bf16_tile.h): 32-deep
 // stages in a 5-slot ring with three stages in flight (counted vmcnt, one barrier per stage), the next stage's
 // fragments read into a second register set while the current one's MFMAs run, loads and LDS reads interleaved
 // between the MFMAs (sched_group_barrier).  BN 256: waves 2 (M) x 4 (N) of 128 x 64; BN 128: 4 x 2 of 64 x 64.
@@ -403,17 +389,8 @@ __global__ void __launch_bounds__(512, 1) conv2_bf16_kernel(ConvArgs a) {
     mma(cur, 0);
     mma(cur, 1);
     prep(min(kt + 5, nk - 1));
-#pragma unroll
-    for (int j = 0; j < LPS; ++j) {
-      __builtin_amdgcn_sched_group_barrier(0x008, NM / LPS > 0 ? NM / LPS : 1, 0);  // MFMA
-      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                            // VMEM (global_load_lds)
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      __builtin_amdgcn_sched_group_barrier(0x008, NM / 4 > 0 ? NM / 4 : 1, 0);      // MFMA
-      __builtin_amdgcn_sched_group_barrier(0x100, (2 * (TM + TN) + 3) / 4, 0);     // DS read
-      __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);                            // VALU (the next stage's sources)
-    }
+    // (the VALU groups: the next stage's sources)
+    mfma_interleave<LPS, (NM / LPS > 0 ? NM / LPS : 1), 4, (NM / 4 > 0 ? NM / 4 : 1), (2 * (TM + TN) + 3) / 4, 4>();
   };
   for (int st = 0; st < C2_ST - 1; ++st) {
     prep(min(st, nk - 1));
@@ -469,8 +446,7 @@ __global__ void __launch_bounds__(512, 1) conv2_bf16_kernel(ConvArgs a) {
       if (m >= a.M || gcol >= a.Cout) continue;
       float e[4] = {v.x, v.y, v.z, v.w};
       if constexpr (RES == RES_BF16_PRE) {
-        typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-        const bf16x4_t r4 = *reinterpret_cast<const bf16x4_t*>(reinterpret_cast<const bf16*>(a.res) + (size_t)m * a.ldr + gcol);
+        const bf16x4 r4 = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const bf16*>(a.res) + (size_t)m * a.ldr + gcol);
 #pragma unroll
         for (int i = 0; i < 4; ++i) e[i] += (float)r4[i];
       }
@@ -481,8 +457,7 @@ __global__ void __launch_bounds__(512, 1) conv2_bf16_kernel(ConvArgs a) {
         if constexpr (ACT == ACT_RELU) e[i] = fmaxf(e[i], 0.f);
       }
       if constexpr (RES == RES_BF16) {
-        typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-        const bf16x4_t r4 = *reinterpret_cast<const bf16x4_t*>(reinterpret_cast<const bf16*>(a.res) + (size_t)m * a.ldr + gcol);
+        const bf16x4 r4 = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const bf16*>(a.res) + (size_t)m * a.ldr + gcol);
 #pragma unroll
         for (int i = 0; i < 4; ++i) e[i] += (float)r4[i];
       }
@@ -494,11 +469,10 @@ __global__ void __launch_bounds__(512, 1) conv2_bf16_kernel(ConvArgs a) {
         e[3] = fmaf(rsc.w, r4.w, e[3]);
       }
       if constexpr (OUT == OUT_BF16) {
-        typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-        bf16x4_t o;
+        bf16x4 o;
 #pragma unroll
         for (int i = 0; i < 4; ++i) o[i] = (bf16)e[i];
-        *reinterpret_cast<bf16x4_t*>(reinterpret_cast<bf16*>(a.out) + (size_t)m * a.ldo + gcol) = o;
+        *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16*>(a.out) + (size_t)m * a.ldo + gcol) = o;
       } else {
         float* o = reinterpret_cast<float*>(a.out) + (size_t)m * a.ldo + gcol;
         if (gcol + 4 <= a.Cout && (a.ldo & 3) == 0) {
@@ -527,34 +501,14 @@ __global__ void __launch_bounds__(512, 1) conv2_bf16_kernel(ConvArgs a) {
 // so the ~32 consecutive ids an XCD runs at once cover ~8 row panels x ~4 column panels (A and W panels re-read from
 // the XCD's L2 instead of the fabric when Cout spans many column panels; the same order as gemm_bf16_kernel's)
 constexpr int C2_GM = 8;
+// panel_tile<C2_GM> (vge_bf16_tile.h) with the sum that forms mt written the other way round: with panel_tile's order
+// hipcc allocates the scalar registers of the 16 conv2p_bf16_kernel instantiations differently (two change their SGPR
+// count), so until that is measured on the chip this kernel keeps its own copy
 __device__ __forceinline__ void c2_tile(int bid, int ntn, int mtn, int& mt, int& nt) {
   const int grp = bid / (C2_GM * ntn), rem = bid - grp * (C2_GM * ntn);
   const int gm = min(C2_GM, mtn - grp * C2_GM);
   mt = grp * C2_GM + rem % gm;
   nt = rem / gm;
-}
-
-template <int CTRL>
-__device__ __forceinline__ float dppq(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-// 4x4 transpose inside each quad: on entry lane i holds column i of rows 0..3 (v0..v3), on exit row i, columns 0..3
-__device__ __forceinline__ void quad_t4(float& v0, float& v1, float& v2, float& v3, bool o1, bool o2) {
-  float x = o1 ? v0 : v1, y = dppq<0xB1>(x);  // quad_perm [1,0,3,2]
-  v0 = o1 ? y : v0;
-  v1 = o1 ? v1 : y;
-  x = o1 ? v2 : v3;
-  y = dppq<0xB1>(x);
-  v2 = o1 ? y : v2;
-  v3 = o1 ? v3 : y;
-  x = o2 ? v0 : v2;
-  y = dppq<0x4E>(x);  // quad_perm [2,3,0,1]
-  v0 = o2 ? y : v0;
-  v2 = o2 ? v2 : y;
-  x = o2 ? v1 : v3;
-  y = dppq<0x4E>(x);
-  v1 = o2 ? y : v1;
-  v3 = o2 ? v3 : y;
 }
 
 template <int BN, int ACT, int OUT, int RES, int BM>
@@ -656,7 +610,6 @@ __global__ void __launch_bounds__(512, 1) conv2p_bf16_kernel(ConvArgs a) {
   const int qrow = 4 * h + (lane & 3), qcol = 4 * ((lane & 31) >> 2);
   constexpr int OE = OUT == OUT_BF16 ? 2 : 4;  // output element bytes
   constexpr int RE = RES == RES_F32S ? 4 : 2;  // residual element bytes
-  typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
   typedef typename std::conditional<RES == RES_F32S, uintx4_t, uintx2_t>::type RV;
   floatx4 bb[TN], rs[TN];
   auto tile_mn = [&](int i, int& m0, int& n0) {
@@ -732,7 +685,7 @@ __global__ void __launch_bounds__(512, 1) conv2p_bf16_kernel(ConvArgs a) {
           e[2] += bb[u].z;
           e[3] += bb[u].w;
           if constexpr (RES == RES_BF16_PRE) {
-            const bf16x4_t r4 = __builtin_bit_cast(bf16x4_t, rv[blk & 1][q]);
+            const bf16x4 r4 = __builtin_bit_cast(bf16x4, rv[blk & 1][q]);
 #pragma unroll
             for (int c = 0; c < 4; ++c) e[c] += (float)r4[c];
           }
@@ -743,7 +696,7 @@ __global__ void __launch_bounds__(512, 1) conv2p_bf16_kernel(ConvArgs a) {
             if constexpr (ACT == ACT_RELU) e[c] = fmaxf(e[c], 0.f);
           }
           if constexpr (RES == RES_BF16) {
-            const bf16x4_t r4 = __builtin_bit_cast(bf16x4_t, rv[blk & 1][q]);
+            const bf16x4 r4 = __builtin_bit_cast(bf16x4, rv[blk & 1][q]);
 #pragma unroll
             for (int c = 0; c < 4; ++c) e[c] += (float)r4[c];
           }
@@ -756,7 +709,7 @@ __global__ void __launch_bounds__(512, 1) conv2p_bf16_kernel(ConvArgs a) {
           }
           const int oo = offs(t, u, q, a.ldo, OE);
           if constexpr (OUT == OUT_BF16) {
-            bf16x4_t o;
+            bf16x4 o;
 #pragma unroll
             for (int c = 0; c < 4; ++c) o[c] = (bf16)e[c];
             __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uintx2_t, o), ob, oo, 0, 0);
@@ -788,17 +741,8 @@ __global__ void __launch_bounds__(512, 1) conv2p_bf16_kernel(ConvArgs a) {
     mma(cur, 0);
     mma(cur, 1);
     prep(g + ST);
-#pragma unroll
-    for (int j = 0; j < LPS; ++j) {
-      __builtin_amdgcn_sched_group_barrier(0x008, NM / LPS > 0 ? NM / LPS : 1, 0);  // MFMA
-      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                            // VMEM (global_load_lds)
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      __builtin_amdgcn_sched_group_barrier(0x008, NM / 4 > 0 ? NM / 4 : 1, 0);      // MFMA
-      __builtin_amdgcn_sched_group_barrier(0x100, (2 * (TM + TN) + 3) / 4, 0);     // DS read
-      __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);                            // VALU (the next stage's sources)
-    }
+    // (the VALU groups: the next stage's sources)
+    mfma_interleave<LPS, (NM / LPS > 0 ? NM / LPS : 1), 4, (NM / 4 > 0 ? NM / 4 : 1), (2 * (TM + TN) + 3) / 4, 4>();
   };
   auto last = [&](int g, int kk, int i, Frag& cur, Frag& nxt) {  // the tile's last stage + its epilogue
     body(g, kk, i, cur, nxt, 2);
@@ -877,7 +821,6 @@ __global__ void __launch_bounds__(256) dwconv_kernel(const bf16* __restrict__ x,
 // bf16x4 pixels slides down the column in registers, so each output row loads one new input row (5 pixels, 8 B
 // each): 1/5 of the loads of the form above, weights for the 4 channels held in registers.  Per output the taps
 // are summed in (kh, kw) order with out-of-range taps adding 0 -- the same sums as dwconv_kernel.
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
 template <int RB>
 __global__ void __launch_bounds__(256) dwconv5_rb_kernel(const bf16* __restrict__ x, long ldx, const float* __restrict__ w,
                                                          const float* __restrict__ b, bf16* __restrict__ y, long ldy,
@@ -899,20 +842,20 @@ __global__ void __launch_bounds__(256) dwconv5_rb_kernel(const bf16* __restrict_
   }
   const floatx4 bb = *reinterpret_cast<const floatx4*>(b + c4);
   const bf16* colp = x + img * H * W * ldx + c4;
-  auto load_row = [&](int ih, bf16x4_t (&raw)[5]) {
+  auto load_row = [&](int ih, bf16x4 (&raw)[5]) {
 #pragma unroll
     for (int kw = 0; kw < 5; ++kw) {
       const int iw = ow - 2 + kw;
-      raw[kw] = bf16x4_t{(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f};
+      raw[kw] = bf16x4{(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f};
       if ((unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W)
-        raw[kw] = *reinterpret_cast<const bf16x4_t*>(colp + ((long)ih * W + iw) * ldx);
+        raw[kw] = *reinterpret_cast<const bf16x4*>(colp + ((long)ih * W + iw) * ldx);
     }
   };
   // the window lives in f32, input row ih in slot (ih - oh0 + 2) % 5; the output loop is unrolled by 5 so every
   // slot index is static (no register moves); the next input row is loaded one output ahead
   float wf[5][5][4];
-  bf16x4_t nxt[5];
-  auto to_slot = [&](const bf16x4_t (&raw)[5], float (&slot)[5][4]) {
+  bf16x4 nxt[5];
+  auto to_slot = [&](const bf16x4 (&raw)[5], float (&slot)[5][4]) {
 #pragma unroll
     for (int kw = 0; kw < 5; ++kw)
 #pragma unroll
@@ -939,10 +882,10 @@ __global__ void __launch_bounds__(256) dwconv5_rb_kernel(const bf16* __restrict_
         for (int kw = 0; kw < 5; ++kw)
 #pragma unroll
           for (int c = 0; c < 4; ++c) acc[c] = fmaf(wr[kh * 5 + kw][c], wf[(j + kh) % 5][kw][c], acc[c]);
-      bf16x4_t o;
+      bf16x4 o;
 #pragma unroll
       for (int c = 0; c < 4; ++c) o[c] = (bf16)silu(acc[c]);
-      *reinterpret_cast<bf16x4_t*>(y + ((img * H + oh0 + r + j) * W + ow) * ldy + c4) = o;
+      *reinterpret_cast<bf16x4*>(y + ((img * H + oh0 + r + j) * W + ow) * ldy + c4) = o;
     }
   }
 }
@@ -1230,13 +1173,8 @@ static int ilog2(int v) {
 static int g_conv_persist = -1;  // VGE_CONV_PERSIST=0: one tile per workgroup (conv2_bf16_kernel, A/B timing)
 
 static int persistent_grid(int ntiles) {  // one workgroup per CU, a multiple of 8 (whole XCDs)
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      n = 256;
-    cus = std::max(8, n / 8 * 8);
-  }
+  const int n = device_cu_count();
+  const int cus = std::max(8, (n > 0 ? n : 256) / 8 * 8);
   return ntiles <= cus ? ntiles : cus;
 }
 
@@ -1342,18 +1280,29 @@ int conv_lib_epi(const ConvLaunch& c) {
   return -1;
 }
 
+// a 1x1 stride-1 conv over M pixels as the GEMM out[M][Cout] = x[M][Cin] w[Cout][Cin]^T (variants 9, 10 and 11)
+static GemmBf16 conv_as_gemm(const ConvLaunch& c, int M) {
+  GemmBf16 g{};
+  g.A = c.x;
+  g.lda = c.ldx;
+  g.W = c.w;
+  g.ldw = c.Kp;
+  g.out = c.out;
+  g.ldo = c.ldo;
+  g.bias = c.bias;
+  g.ldr = c.ldr;
+  g.resb = c.res;
+  g.M = M;
+  g.N = c.Cout;
+  g.K = c.Cin;
+  return g;
+}
+
 bool conv_gemm_persist_ok(const ConvLaunch& c) {
   const int epi = conv_gemm_epi(c);
   if (epi < 0) return false;
-  GemmBf16 g{};
-  g.lda = c.ldx;
-  g.ldw = c.Kp;
-  g.ldo = c.ldo;
-  g.bias = c.bias;
-  g.M = c.n_img * ((c.H + 2 * c.pad - c.KH) / c.stride + 1) * ((c.W + 2 * c.pad - c.KW) / c.stride + 1);
-  g.N = c.Cout;
-  g.K = c.Cin;
-  return gemm_persist_ok(epi, g);
+  const int M = c.n_img * ((c.H + 2 * c.pad - c.KH) / c.stride + 1) * ((c.W + 2 * c.pad - c.KW) / c.stride + 1);
+  return gemm_persist_ok(epi, conv_as_gemm(c, M));
 }
 
 hipError_t launch_conv_bf16(const ConvLaunch& c, hipStream_t s) {
@@ -1387,20 +1336,7 @@ hipError_t launch_conv_bf16(const ConvLaunch& c, hipStream_t s) {
   if (variant == 11) {  // the library GEMM (vge_blaslt.cpp; conv_tuned_launch's choice for the shapes it takes)
     const int epi = conv_lib_epi(c);
     if (epi >= 0) {
-      GemmBf16 g{};
-      g.A = c.x;
-      g.lda = c.ldx;
-      g.W = c.w;
-      g.ldw = c.Kp;
-      g.out = c.out;
-      g.ldo = c.ldo;
-      g.bias = c.bias;
-      g.ldr = c.ldr;
-      g.resb = c.res;
-      g.M = a.M;
-      g.N = c.Cout;
-      g.K = c.Cin;
-      const hipError_t e = launch_gemm_lib(epi, g, s);
+      const hipError_t e = launch_gemm_lib(epi, conv_as_gemm(c, a.M), s);
       if (e != hipErrorNotSupported) return e;
     }
     variant = 9;  // not on the library path: the GEMM kernel where it applies, else the default below
@@ -1408,19 +1344,7 @@ hipError_t launch_conv_bf16(const ConvLaunch& c, hipStream_t s) {
   if (variant == 9 || variant == 10) {  // the GEMM kernel (tuner candidates, or forced by vge_debug_set_conv_variant)
     const int epi = conv_gemm_epi(c);
     if (epi >= 0) {
-      GemmBf16 g{};
-      g.A = c.x;
-      g.lda = c.ldx;
-      g.W = c.w;
-      g.ldw = c.Kp;
-      g.out = c.out;
-      g.ldo = c.ldo;
-      g.bias = c.bias;
-      g.ldr = c.ldr;
-      g.resb = c.res;
-      g.M = a.M;
-      g.N = c.Cout;
-      g.K = c.Cin;
+      const GemmBf16 g = conv_as_gemm(c, a.M);
       if (variant == 10) {  // its persistent form (one workgroup per CU, the epilogue under the next tile's loads)
         if (gemm_persist_ok(epi, g)) return launch_gemm_bf16_persistent(epi, g, s);
         if (c.variant == 10) return hipErrorInvalidValue;

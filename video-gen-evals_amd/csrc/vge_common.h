@@ -15,6 +15,13 @@ typedef float floatx2 __attribute__((ext_vector_type(2)));
 #define VGE_LDX 260          // LDS row stride (floats) of a 256-wide activation panel: 16-B shift per
                              // row keeps ds_read_b128 fragment reads conflict-free (see vge_encoder.hip)
 
+// Workgroups are dealt to the 8 XCDs round robin (block b runs on XCD b % 8).  xcd_remap(b, nblk) is the bijection of
+// 0 .. nblk - 1 under which each XCD takes a contiguous range of ids, so neighbouring ids share an L2.
+__host__ __device__ __forceinline__ int xcd_remap(int b, int nblk) {
+  const int q8 = nblk >> 3, r8 = nblk & 7, x8 = b & 7;
+  return (x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8) + (b >> 3);
+}
+
 // ---- wave64 reductions (all lanes receive the result) ---------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

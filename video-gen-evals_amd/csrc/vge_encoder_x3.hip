@@ -23,6 +23,7 @@
 // B[k = 8h + j][col i], j = 0..7; C/D: col = l&31, row = (r&3) + 8(r>>2) + 4(l>>5), r = 0..15.
 // A weight chunk = 16 K x 256 columns: [plane][h][n][8] fp16 = 16 KB, so a lane's B fragment of a chunk
 // is one 16-B load per plane and a wave's 32 columns are two contiguous 512-B runs per plane.
+#include "vge_lds_attr.h"
 #include "vge_x3.h"
 #include <algorithm>
 #include <vector>
@@ -1293,14 +1294,8 @@ hipError_t launch_conv_encoders_x3(const float* feats, int n_windows, const EncD
 }
 
 int conv_cu_count() {
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1)
-      n_cu = 256;
-  }
-  return n_cu;
+  const int n_cu = device_cu_count();
+  return n_cu > 0 ? n_cu : 256;
 }
 
 // Unit table of conv_encoder_f16w_kernel for n_windows x n_enc (window, encoder) pairs on G = min(CUs, units)

@@ -23,7 +23,7 @@
 //       frame, clip, nonempty, and the gate's person count
 // Every float expression keeps its operations separately rounded (no contraction), as the oracle (oracle/frcnn.py)
 // evaluates them.
-#include "vge_common.h"
+#include "vge_bf16_tile.h"  // the vector typedefs
 #include "vge_lds_attr.h"
 #include "vge_frcnn_k.h"
 
@@ -33,11 +33,7 @@
 
 namespace {
 
-typedef __bf16 bf16;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned long long u64;
-typedef unsigned uintx4_t __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr float SCALE_CLAMP = 4.135166556742356f;  // log(1000 / 16), Box2BoxTransform
 
@@ -865,11 +861,10 @@ __global__ void __launch_bounds__(512, 1) frcnn_stem_pool_kernel(const bf16* __r
         for (int u = 0; u < 2; ++u)
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
-            typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-            bf16x4_t o;
+            bf16x4 o;
 #pragma unroll
             for (int j = 0; j < 4; ++j) o[j] = (bf16)fmaxf(acc[i][u][4 * g + j] + bq[u][g][j], 0.f);
-            *reinterpret_cast<bf16x4_t*>(stv + sidx * SP_SPITCH + (32 * u + 8 * g + 4 * h) * 2) = o;
+            *reinterpret_cast<bf16x4*>(stv + sidx * SP_SPITCH + (32 * u + 8 * g + 4 * h) * 2) = o;
           }
       }
     }
@@ -1146,9 +1141,8 @@ hipError_t launch_frcnn_stem_pool(const void* in, const void* w, int Kp, const f
   if (ntiles >= (1l << 31)) return hipErrorInvalidValue;
   static LdsAttrOnce attr;
   if (const hipError_t e = attr(reinterpret_cast<const void*>(&frcnn_stem_pool_kernel), SP_LDS); e != hipSuccess) return e;
-  int dev = 0, ncu = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return hipErrorUnknown;
+  const int ncu = device_cu_count();
+  if (ncu < 1) return hipErrorUnknown;
   const int grid = (int)std::min<long>(ntiles, ncu);
   hipLaunchKernelGGL(frcnn_stem_pool_kernel, dim3(grid), dim3(512), SP_LDS, s, static_cast<const bf16*>(in),
                      static_cast<const bf16*>(w), Kp, bias, static_cast<bf16*>(out), n, hp, wp, ty, tx);

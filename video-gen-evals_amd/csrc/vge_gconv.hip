@@ -22,7 +22,7 @@
 //     store.
 // K steps: a 16-channel output tile's inputs are its group's channels, max(group width, 16) of them (group width 8:
 // the 16 x 16 weight block holds two groups' 8 x 8 blocks and zeros, as packed by vge_frcnn.cpp's gconv_bn).
-#include "vge_common.h"
+#include "vge_bf16_tile.h"  // the vector typedefs
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -31,10 +31,6 @@
 namespace {
 
 typedef short short4v __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned uintx4_t __attribute__((ext_vector_type(4)));
-typedef unsigned uintx2_t __attribute__((ext_vector_type(2)));
 constexpr int GC_OOB = 0x7FFFFFF0;  // buffer offset past every record count: loads return 0, stores are dropped
 
 // LDS bytes per input pixel (64 bf16 channels + pad) and extra bytes per input row (the header's bank model)
@@ -56,13 +52,9 @@ struct GconvArgs {
 
 // Workgroup b of nblk -> its (tile, slice, image group) id.  Workgroups are dealt to the 8 XCDs round robin, so in
 // launch order a tile's neighbours -- which read its halo rows -- run on other XCDs and fetch those rows into their own
-// L2s; with xcd set each XCD takes a contiguous range of ids instead (bijective), the tiles of a slice and image group
+// L2s; with xcd set each XCD takes a contiguous range of ids instead (xcd_remap), the tiles of a slice and image group
 // run side by side on one XCD and the halo rows hit its L2.
-__device__ __forceinline__ int gc_xcd(int b, int nblk, int on) {
-  if (!on) return b;
-  const int q8 = nblk >> 3, r8 = nblk & 7, x8 = b & 7;
-  return (x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8) + (b >> 3);
-}
+__device__ __forceinline__ int gc_xcd(int b, int nblk, int on) { return on ? xcd_remap(b, nblk) : b; }
 #ifndef VGE_GC_NI
 #define VGE_GC_NI 8  // (r06ad, same box: 8 images per workgroup -0.6 % on the detector vs 4)
 #endif
@@ -144,7 +136,7 @@ __global__ void __launch_bounds__(256, KS <= 2 ? VGE_GC_OCC_SMALL : VGE_GC_OCC) 
   // lane); MF = 1, KS = 1: [tap pair][0] bf16x8 (lane half h -> tap 2p + h)
   constexpr int NT = MF && KS == 1 ? 5 : 9;
   constexpr int NJ = MF ? (KS == 1 ? 1 : KS / 2) : KS;
-  typedef typename std::conditional<MF != 0, bf16x8_t, short4v>::type Frag;
+  typedef typename std::conditional<MF != 0, bf16x8, short4v>::type Frag;
   Frag wa[NT][NJ];
   const int hh = lane >> 5;  // MF = 1, KS = 1: which tap of the pair
   const int cl = MF ? (KS == 1 ? 8 * ((lane >> 4) & 1) : 8 * (lane >> 4)) : 4 * (lane >> 4);
@@ -184,14 +176,14 @@ __global__ void __launch_bounds__(256, KS <= 2 ? VGE_GC_OCC_SMALL : VGE_GC_OCC) 
           const int ta = 2 * t, tb = 2 * t + 1 < 9 ? 2 * t + 1 : 8;  // (tap 9: zero weights on finite data)
           const int offa = ((ta / 3) * IW + (ta % 3)) * PITCH + (ta / 3) * ROWPAD;
           const int offb = ((tb / 3) * IW + (tb % 3)) * PITCH + (tb / 3) * ROWPAD;
-          const bf16x8_t b = *reinterpret_cast<const bf16x8_t*>(pb + (hh ? offb : offa));
+          const bf16x8 b = *reinterpret_cast<const bf16x8*>(pb + (hh ? offb : offa));
           acc[pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[t][0], b, acc[pt], 0, 0, 0);
         } else {
           const int off = ((t / 3) * IW + (t % 3)) * PITCH + (t / 3) * ROWPAD;
 #pragma unroll
           for (int j = 0; j < NJ; ++j) {
             if constexpr (MF) {
-              const bf16x8_t b = *reinterpret_cast<const bf16x8_t*>(pb + off + 64 * j);
+              const bf16x8 b = *reinterpret_cast<const bf16x8*>(pb + off + 64 * j);
               acc[pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[t][j], b, acc[pt], 0, 0, 0);
             } else {
               const short4v b = *reinterpret_cast<const short4v*>(pb + off + 32 * j);
@@ -208,7 +200,7 @@ __global__ void __launch_bounds__(256, KS <= 2 ? VGE_GC_OCC_SMALL : VGE_GC_OCC) 
     for (int pt = 0; pt < gc_npt<S>(); ++pt) {
       const int op = pt * 16 + px, r = gc_div(op, a.inv_tw), oy = oy0 + r, ox = ox0 + op - r * TW;
       const int oo = (op < NPX && oy < a.Ho && ox < a.Wo) ? ((oy * a.Wo + ox) * (int)a.ldo + ch) * 2 : GC_OOB;
-      bf16x4_t o;
+      bf16x4 o;
 #pragma unroll
       for (int i = 0; i < 4; ++i) o[i] = (__bf16)fmaxf(acc[pt][i] + bv[i], 0.f);
       __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uintx2_t, o), orr, oo, 0, 0);

@@ -1,6 +1,6 @@
 // The bf16 GEMM of vge_vit.hip (gemm_bf16_kernel): C = A W^T + epilogue on v_mfma_f32_32x32x16_bf16, 256 x 256 tiles.
-// Shared by the ViT-H extractor (vge_hmr.cpp) and, as a tuner candidate for 1x1 stride-1 convolutions, by the conv
-// launcher (vge_cnn.hip).  A rows: any M (the last row tile's loads clamp to row M - 1, its stores stop at M);
+// Used by the ViT-H extractor (vge_hmr.cpp) and, as a tuner candidate for 1x1 stride-1 convolutions, by the conv
+// launcher (vge_cnn.hip); the device pieces it shares with the conv kernels are in vge_bf16_tile.h.  A rows: any M (the last row tile's loads clamp to row M - 1, its stores stop at M);
 // N % 256 == 0, K % 64 == 0, 16-B aligned rows.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,8 +1,21 @@
-// Host helper of the launch paths that set a kernel's dynamic-LDS limit.
+// Host helpers of the launch paths: the device's CU count, and a kernel's dynamic-LDS limit set once per device.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+
+// Compute units of the calling thread's current device (looked up once per device), or 0 if the runtime cannot say:
+// each caller keeps its own fallback and rounding.
+inline int device_cu_count() {
+  static std::atomic<int> known[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
+  int n = known[dev & 63].load(std::memory_order_relaxed);
+  if (n > 0) return n;
+  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) return 0;
+  known[dev & 63].store(n, std::memory_order_relaxed);
+  return n;
+}
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) for a kernel on the calling thread's current device, once per device
 // (the attribute is per device: a process that moves to another GPU sets it there too; two threads racing here only

@@ -11,7 +11,7 @@
 //   kp120_kernel         onnxpose.postprocess (float64) + wholebody neck / OpenPose reorder + dwpose_init's
 //                        normalisation (/ W, / H; hand points with score < 0.3 -> -1, body points unmasked) +
 //                        flatten_first_person_no_padding
-#include "vge_common.h"
+#include "vge_bf16_tile.h"  // the vector typedefs
 #include "vge_lds_attr.h"
 #include "vge_cnn.h"
 
@@ -20,9 +20,6 @@
 #include <cstdlib>
 
 namespace {
-
-typedef __bf16 bf16;
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 __global__ void __launch_bounds__(256) head_sn_t_kernel(const float* __restrict__ y, long ldy, int hw, int K, int Kp,
                                                         float g, float inv_sqrt_hw, long n_rows, bf16* __restrict__ out) {

@@ -12,7 +12,8 @@
 //                          v_mfma_f32_32x32x16_bf16 (16x16x32 for the bf16-output epilogues), both operands
 //                          staged HBM -> LDS by global_load_lds (16 B per lane) through a 5-stage x 32-k ring
 //                          (160 KB, counted vmcnt), LDS image XOR-swizzled on the source address so the fragment
-//                          ds_read_b128 are conflict-free; XCD-grouped tile order.
+//                          ds_read_b128 are conflict-free; XCD-grouped tile order.  (Stage, tile walk, interleave and
+//                          epilogue conversions shared with the conv kernels: vge_bf16_tile.h.)
 //   gemm2_bf16_kernel<EPI> the same product on 128 x 256 tiles, two workgroups per CU (an A/B option, slower).
 //   ln_bf16_kernel         LayerNorm f32 -> bf16 (one wave per row).
 //   patchify_kernel        uint8 RGB crop -> normalised, zero-padded im2col rows of the 16x16 patches.
@@ -21,11 +22,13 @@
 //                          PV MFMA straight from the accumulators.
 //   xattn1_kernel          the decoder's one-query cross-attention over the 192 context tokens.
 //   softmax_rows_kernel, readout_kernel (6D -> rotation matrix, mean-pose residuals), small helpers.
-#include "vge_common.h"
+#include "vge_bf16_tile.h"
 #include "vge_gemm.h"
 #include "vge_hmr_k.h"
+#include "vge_lds_attr.h"
 #include <atomic>
 #include <cstdlib>
+#include <type_traits>
 
 #ifndef VGE_GABL
 #define VGE_GABL 0  // timing-only GEMM ablations (tools/ablate_gemm.sh): 1 no global_load_lds after the prologue,
@@ -33,12 +36,6 @@
 #endif
 
 namespace {
-
-typedef __bf16 bf16;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned uintx2_t __attribute__((ext_vector_type(2)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 // ------------------------------------------------------------------------------------------- GEMM
 // 256 x 256 output tile per 512-thread workgroup; K in 32-deep stages through a 5-slot LDS ring (A 16 KB + B 16 KB
@@ -63,28 +60,6 @@ struct GemmBf16Args {
   const bf16* resb;  // GEMM_RESB_*: bf16 residual [M][ldr]
 };
 
-// Stage a 256-row x 32-k operand tile (64-B rows) with NW waves: wave-instruction q (0..15) fills LDS bytes
-// [1024 q, 1024 q + 1024) = rows 16q .. 16q+15, lane L -> row 16q + L/4, physical 16-B chunk L%4.  Physical chunk
-// p of row r holds logical chunk p ^ ((r >> 2) & 3): the source address is pre-swizzled, the LDS image stays
-// lane-linear (global_load_lds), and the 16 rows a ds_read_b128 lane group reads land on 16 distinct 16-B slots.
-// rmax: the last valid row (rows past it re-read it: a partial last row tile of A)
-template <int NW, bool CLAMP>
-__device__ __forceinline__ void gb_stage(const bf16* __restrict__ X, long ld, int r0, int k0, char* tile, int wave,
-                                         int lane, int rmax) {
-#pragma unroll
-  for (int j = 0; j < 16 / NW; ++j) {
-    const int q = wave * (16 / NW) + j;
-    const int row = 16 * q + (lane >> 2);
-    const int ch = (lane & 3) ^ ((row >> 2) & 3);
-    glds16(X + (size_t)(CLAMP ? min(r0 + row, rmax) : r0 + row) * ld + k0 + ch * 8, tile + q * 1024);
-  }
-}
-
-__device__ __forceinline__ int gb_xcd_remap(int b, int nblk) {  // bijective: each XCD takes a contiguous range
-  const int q8 = nblk >> 3, r8 = nblk & 7, x8 = b & 7;
-  return (x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8) + (b >> 3);
-}
-
 // NW = 8: waves 2 (M) x 4 (N), 128 x 64 per wave (2 waves per SIMD); NW = 4: waves 2 x 2, 128 x 128 per wave
 // (one wave per SIMD, 256 accumulator registers): 25 % fewer LDS fragment bytes per MFMA.
 // SH = 1 (NW = 8 only): the same wave tile on v_mfma_f32_16x16x32_bf16 (8 x 4 tiles of 16 x 16, one MFMA per 32-k
@@ -101,14 +76,10 @@ __global__ void __launch_bounds__(64 * NW, 1) gemm_bf16_kernel(GemmBf16Args g) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / (NW / 2), wn = wave % (NW / 2);
-  // tile order: each XCD takes a contiguous range of ids (gb_xcd_remap); inside it, groups of GB_GM row panels
-  // walk the column panels with the row panel fastest, so the ~32 blocks an XCD runs at once cover ~8 A panels x
-  // ~4 W panels and read the same K slices at about the same time (L2 hits instead of fabric re-fetches)
+  // tile order: XCD-contiguous ids (xcd_remap), grouped panel walk (panel_tile)
   const int ntn = g.N / GB_N, mtn = (g.M + GB_M - 1) / GB_M;
-  const int bid = gb_xcd_remap(blockIdx.x, gridDim.x);
-  const int grp = bid / (GB_GM * ntn), rem = bid % (GB_GM * ntn);
-  const int gm = min(GB_GM, mtn - grp * GB_GM);
-  const int mt = grp * GB_GM + rem % gm, nt = rem / gm;
+  int mt, nt;
+  panel_tile<GB_GM>(xcd_remap(blockIdx.x, gridDim.x), ntn, mtn, mt, nt);
   const int m0 = mt * GB_M, n0 = nt * GB_N;
   const int nk = g.K / GB_K;                 // >= 2 (K % 64 == 0)
   const int h = lane >> 5;
@@ -133,8 +104,8 @@ __global__ void __launch_bounds__(64 * NW, 1) gemm_bf16_kernel(GemmBf16Args g) {
 
   auto issue = [&](int st) {
     char* slot = lds + (st % GB_ST) * 2 * GB_TILE;
-    gb_stage<NW, PM>(g.A, g.lda, m0, st * GB_K, slot, wave, lane, g.M - 1);
-    gb_stage<NW, false>(g.W, g.ldw, n0, st * GB_K, slot + GB_TILE, wave, lane, g.N - 1);
+    stage_rows<GB_M, NW, PM>(g.A, g.lda, m0, st * GB_K, slot, wave, lane, g.M - 1);
+    stage_rows<GB_N, NW, false>(g.W, g.ldw, n0, st * GB_K, slot + GB_TILE, wave, lane, g.N - 1);
   };
   struct Frag {
     bf16x8 a[2][4], b[2][TN];  // SH = 0: [16-k step][32-row / 32-column tile]; SH = 1: a = 8 16-row tiles, b = 4
@@ -201,16 +172,7 @@ __global__ void __launch_bounds__(64 * NW, 1) gemm_bf16_kernel(GemmBf16Args g) {
 #endif
     mma(cur, 0);
     mma(cur, 1);
-#pragma unroll
-    for (int j = 0; j < LPS; ++j) {
-      __builtin_amdgcn_sched_group_barrier(0x008, MPS * 8 / LPS, 0);  // MFMA
-      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);              // VMEM read (global_load_lds)
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      __builtin_amdgcn_sched_group_barrier(0x008, MPS * 2, 0);             // MFMA
-      __builtin_amdgcn_sched_group_barrier(0x100, (8 + 2 * TN) / 4, 0);    // DS read
-    }
+    mfma_interleave<LPS, MPS * 8 / LPS, 4, MPS * 2, (8 + 2 * TN) / 4>();
   };
   for (int st = 0; st < GB_ST - 1; ++st) issue(min(st, nk - 1));
   vmcnt_b<3 * LPS>();  // retire stage 0
@@ -262,8 +224,7 @@ __global__ void __launch_bounds__(64 * NW, 1) gemm_bf16_kernel(GemmBf16Args g) {
     const int grow = PM ? min(grow_of(half, it), g.M - 1) : grow_of(half, it);  // (PM: rows past M are not stored)
     if constexpr (EPI == GEMM_RES_F32) return *reinterpret_cast<const floatx4*>(g.res + ((long)grow * g.ldr + gcol));
     if constexpr (RB) {
-      const bf16x4 r = *reinterpret_cast<const bf16x4*>(g.resb + ((long)grow * g.ldr + gcol));
-      return floatx4{(float)r[0], (float)r[1], (float)r[2], (float)r[3]};
+      return to_floatx4(*reinterpret_cast<const bf16x4*>(g.resb + ((long)grow * g.ldr + gcol)));
     }
     if constexpr (EPI == GEMM_PE_F32)  // tokens per frame = 192 (checked by the host)
       return *reinterpret_cast<const floatx4*>(g.pos + ((1 + grow - (grow / 192) * 192) * g.N + gcol));
@@ -293,6 +254,11 @@ __global__ void __launch_bounds__(64 * NW, 1) gemm_bf16_kernel(GemmBf16Args g) {
           for (int r = 0; r < 4; ++r)
             my[(tt * 16 + 4 * (lane >> 4) + r) * WC + u * 16 + (lane & 15)] = acq[4 * half + tt][u][r];
     }
+    // NW = 4 only: there hipcc sank ds_writes of rows 4 k + 3 below the row-major ds_reads of those rows (other lanes
+    // read them), which corrupted the rows of the f32 epilogues that load a row vector.  The 8-wave forms keep the
+    // program order today (test_gemm_wave_modes_match_default and the conv variant tests pin their outputs); the
+    // ordering point changes their listings, so it goes in with the next measured change of this epilogue
+    if constexpr (NW == 4) wave_lds_order();
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       const int rl = it * RPI + lr;
@@ -305,8 +271,8 @@ __global__ void __launch_bounds__(64 * NW, 1) gemm_bf16_kernel(GemmBf16Args g) {
           if (it < NPF && half == 0) rr[it % NPF] = rowload(1, it);
         }
         if constexpr (EPI == GEMM_RELU_BF16 || EPI == GEMM_RESB_RELU_BF16)
-          v = floatx4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
-        bf16x4 ob;
+          v = relu4(v);
+        bf16x4 ob;  // (not to_bf16x4: with it the partial-M kernels' stores come out in another order)
         ob[0] = (bf16)v.x; ob[1] = (bf16)v.y; ob[2] = (bf16)v.z; ob[3] = (bf16)v.w;
         if (!PM || grow < g.M) *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16*>(g.out) + o) = ob;
       } else if constexpr (EPI == GEMM_BF16 || EPI == GEMM_GELU_BF16) {
@@ -315,7 +281,7 @@ __global__ void __launch_bounds__(64 * NW, 1) gemm_bf16_kernel(GemmBf16Args g) {
           gelu2_many(y);                              // chain's 1.5e-2 bound vs the bf16-point oracle (1.68e-2, r04 box)
           v = {y[0].x, y[0].y, y[1].x, y[1].y};
         }
-        bf16x4 ob;
+        bf16x4 ob;  // (not to_bf16x4: with it the partial-M kernels' stores come out in another order)
         ob[0] = (bf16)v.x; ob[1] = (bf16)v.y; ob[2] = (bf16)v.z; ob[3] = (bf16)v.w;
         if (!PM || grow < g.M) *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16*>(g.out) + o) = ob;
       } else {
@@ -324,12 +290,13 @@ __global__ void __launch_bounds__(64 * NW, 1) gemm_bf16_kernel(GemmBf16Args g) {
         if (it < NPF && half == 0) rr[it % NPF] = rowload(1, it);  // the next half's, in the freed register
       }
     }
+    if constexpr (NW == 4) wave_lds_order();
   }
 }
 
 // ------------------------------------------------------------- GEMM, persistent (gemmp)
 // The 16x16x32 8-wave tile of gemm_bf16_kernel (SH = 1), persistent: one workgroup per CU walks its tiles (virtual
-// block b + i G through gb_xcd_remap, G a multiple of 8, so an XCD's workgroups take consecutive tiles of that XCD's
+// block b + i G through xcd_remap, G a multiple of 8, so an XCD's workgroups take consecutive tiles of that XCD's
 // range at a time, as the one-tile kernel's do) through ONE continuous 5-slot ring: the next tile's first four stages
 // are issued during this tile's last four steps, and the epilogue -- bias, GELU / ReLU, bf16, 8-B stores straight from
 // the accumulators after a quad transpose (lane i of a quad takes row i, four consecutive columns), no LDS -- runs
@@ -348,31 +315,6 @@ constexpr int GP_LPS = 4;   // global_load_lds per thread per stage (2 A + 2 W)
 constexpr int GP_NST = 32;  // epilogue stores per thread: 8 row tiles x 4 column tiles of 16 x 16
 constexpr int GP_NCL = 4;   // bias loads per thread: one floatx4 per column tile
 
-template <int CTRL>
-__device__ __forceinline__ float gp_dpp(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-// 4x4 transpose inside each quad of lanes: on entry lane i holds column i of rows 0..3, on exit row i, columns 0..3
-__device__ __forceinline__ floatx4 gp_quad_t4(floatx4 v, bool o1, bool o2) {
-  float v0 = v.x, v1 = v.y, v2 = v.z, v3 = v.w;
-  float x = o1 ? v0 : v1, y = gp_dpp<0xB1>(x);  // quad_perm [1,0,3,2]
-  v0 = o1 ? y : v0;
-  v1 = o1 ? v1 : y;
-  x = o1 ? v2 : v3;
-  y = gp_dpp<0xB1>(x);
-  v2 = o1 ? y : v2;
-  v3 = o1 ? v3 : y;
-  x = o2 ? v0 : v2;
-  y = gp_dpp<0x4E>(x);  // quad_perm [2,3,0,1]
-  v0 = o2 ? y : v0;
-  v2 = o2 ? v2 : y;
-  x = o2 ? v1 : v3;
-  y = gp_dpp<0x4E>(x);
-  v1 = o2 ? y : v1;
-  v3 = o2 ? v3 : y;
-  return floatx4{v0, v1, v2, v3};
-}
-
 template <int EPI, bool PM>
 __global__ void __launch_bounds__(512, 1) gemmp_bf16_kernel(GemmBf16Args g) {
   static_assert(EPI == GEMM_BF16 || EPI == GEMM_GELU_BF16 || EPI == GEMM_RELU_BF16, "residual-free bf16 epilogues");
@@ -387,11 +329,10 @@ __global__ void __launch_bounds__(512, 1) gemmp_bf16_kernel(GemmBf16Args g) {
   const int nk = g.K / GB_K;               // even, >= 6 (host)
   const int total = T * nk;
   auto tile_mn = [&](int i, int& m0, int& n0) {
-    const int bid = gb_xcd_remap(b + i * G, ntiles);
-    const int grp = bid / (GB_GM * ntn), rem = bid - grp * (GB_GM * ntn);
-    const int gm = min(GB_GM, mtn - grp * GB_GM);
-    m0 = (grp * GB_GM + rem % gm) * GB_M;
-    n0 = (rem / gm) * GB_N;
+    int mt, nt;
+    panel_tile<GB_GM>(xcd_remap(b + i * G, ntiles), ntn, mtn, mt, nt);
+    m0 = mt * GB_M;
+    n0 = nt * GB_N;
   };
 
   // ---- issue side: the next stage to load (global stage index is_g = tile is_i, k stage is_k); past the last stage
@@ -400,8 +341,8 @@ __global__ void __launch_bounds__(512, 1) gemmp_bf16_kernel(GemmBf16Args g) {
   tile_mn(0, is_m0, is_n0);
   auto issue_next = [&]() {
     char* slot = lds + (is_g % GB_ST) * 2 * GB_TILE;
-    gb_stage<8, PM>(g.A, g.lda, is_m0, is_k * GB_K, slot, wave, lane, g.M - 1);
-    gb_stage<8, false>(g.W, g.ldw, is_n0, is_k * GB_K, slot + GB_TILE, wave, lane, g.N - 1);
+    stage_rows<GB_M, 8, PM>(g.A, g.lda, is_m0, is_k * GB_K, slot, wave, lane, g.M - 1);
+    stage_rows<GB_N, 8, false>(g.W, g.ldw, is_n0, is_k * GB_K, slot + GB_TILE, wave, lane, g.N - 1);
     if (is_g + 1 < total) {
       ++is_g;
       if (++is_k == nk) {
@@ -472,16 +413,7 @@ __global__ void __launch_bounds__(512, 1) gemmp_bf16_kernel(GemmBf16Args g) {
     read(min(gs + 1, total - 1), nxt);
     mma(cur, 0);
     mma(cur, 1);
-#pragma unroll
-    for (int j = 0; j < LPS; ++j) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 2 * 8 / LPS, 0);  // MFMA
-      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);            // VMEM read (global_load_lds)
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);  // MFMA
-      __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);  // DS read
-    }
+    mfma_interleave<LPS, 2 * 8 / LPS, 4, 4, 3>();
   };
   const bool o1 = lane & 1, o2 = lane & 2;
   auto epilogue = [&](int i) {
@@ -500,15 +432,13 @@ __global__ void __launch_bounds__(512, 1) gemmp_bf16_kernel(GemmBf16Args g) {
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         floatx4 v = acq[t][u] + bb[u];
-        if constexpr (EPI == GEMM_RELU_BF16) v = floatx4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
+        if constexpr (EPI == GEMM_RELU_BF16) v = relu4(v);
         if constexpr (EPI == GEMM_GELU_BF16) {
           floatx2 y[2] = {{v.x, v.y}, {v.z, v.w}};
           gelu2_many(y);
           v = floatx4{y[0].x, y[0].y, y[1].x, y[1].y};
         }
-        v = gp_quad_t4(v, o1, o2);
-        bf16x4 o;
-        o[0] = (bf16)v.x; o[1] = (bf16)v.y; o[2] = (bf16)v.z; o[3] = (bf16)v.w;
+        const bf16x4 o = to_bf16x4(quad_t4(v, o1, o2));
         const int off = ((r0 + 16 * t) * (int)g.ldo + c0 + 16 * u) * 2;  // < rows x ldo x 2 < 2^31 (host)
         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uintx2_t, o), ob, off, 0, 0);
       }
@@ -550,20 +480,6 @@ constexpr int G2_TA = G2_M * G2_K * 2;       // 8 KB of A per stage
 constexpr int G2_SLOT = G2_TA + G2_N * G2_K * 2;  // + 16 KB of W = 24 KB
 constexpr int G2_LDS = G2_ST * G2_SLOT;     // 72 KB
 
-// ROWS x 32-k operand tile with 4 waves: the layout and swizzle of gb_stage
-template <int ROWS, bool CLAMP>
-__device__ __forceinline__ void g2_stage(const bf16* __restrict__ X, long ld, int r0, int k0, char* tile, int wave,
-                                         int lane, int rmax) {
-  constexpr int PW = ROWS / 16 / 4;  // 1-KB wave instructions per wave
-#pragma unroll
-  for (int j = 0; j < PW; ++j) {
-    const int q = wave * PW + j;
-    const int row = 16 * q + (lane >> 2);
-    const int ch = (lane & 3) ^ ((row >> 2) & 3);
-    glds16(X + (size_t)(CLAMP ? min(r0 + row, rmax) : r0 + row) * ld + k0 + ch * 8, tile + q * 1024);
-  }
-}
-
 template <bool B>
 struct BoolC {
   static constexpr bool value = B;
@@ -577,10 +493,8 @@ __global__ void __launch_bounds__(256, 2) gemm2_bf16_kernel(GemmBf16Args g) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const int ntn = g.N / G2_N, mtn = (g.M + G2_M - 1) / G2_M;
-  const int bid = gb_xcd_remap(blockIdx.x, gridDim.x);
-  const int grp = bid / (G2_GM * ntn), rem = bid % (G2_GM * ntn);
-  const int gm = min(G2_GM, mtn - grp * G2_GM);
-  const int mt = grp * G2_GM + rem % gm, nt = rem / gm;
+  int mt, nt;
+  panel_tile<G2_GM>(xcd_remap(blockIdx.x, gridDim.x), ntn, mtn, mt, nt);
   const int m0 = mt * G2_M, n0 = nt * G2_N;
   const int nk = g.K / G2_K;  // >= 2, even
   const int h = lane >> 5;
@@ -597,8 +511,8 @@ __global__ void __launch_bounds__(256, 2) gemm2_bf16_kernel(GemmBf16Args g) {
 
   auto issue = [&](int st) {
     char* slot = lds + (st % G2_ST) * G2_SLOT;
-    g2_stage<G2_M, PM>(g.A, g.lda, m0, st * G2_K, slot, wave, lane, g.M - 1);
-    g2_stage<G2_N, false>(g.W, g.ldw, n0, st * G2_K, slot + G2_TA, wave, lane, g.N - 1);
+    stage_rows<G2_M, 4, PM>(g.A, g.lda, m0, st * G2_K, slot, wave, lane, g.M - 1);
+    stage_rows<G2_N, 4, false>(g.W, g.ldw, n0, st * G2_K, slot + G2_TA, wave, lane, g.N - 1);
   };
   struct Frag {
     bf16x8 a[2][2], b[2][4];  // [16-k step][tile]
@@ -635,16 +549,7 @@ __global__ void __launch_bounds__(256, 2) gemm2_bf16_kernel(GemmBf16Args g) {
     read(min(kt + 1, nk - 1), nxt);
     mma(cur, 0);
     mma(cur, 1);
-#pragma unroll
-    for (int j = 0; j < LPS; ++j) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
-      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // VMEM read (global_load_lds)
-    }
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
-      __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // DS read
-    }
+    mfma_interleave<LPS, 1, 6, 1, 2>();
   };
   issue(0);
   issue(1);
@@ -724,15 +629,13 @@ __global__ void __launch_bounds__(256, 2) gemm2_bf16_kernel(GemmBf16Args g) {
         for (int u = 0; u < UB; ++u)
 #pragma unroll
           for (int q = 0; q < 4; ++q)
-            v[u][q] += floatx4{(float)rv[u][q][0], (float)rv[u][q][1], (float)rv[u][q][2], (float)rv[u][q][3]};
+            v[u][q] += to_floatx4(rv[u][q]);
       }
       if constexpr (EPI == GEMM_RELU_BF16 || EPI == GEMM_RESB_RELU_BF16) {
 #pragma unroll
         for (int u = 0; u < UB; ++u)
 #pragma unroll
-          for (int q = 0; q < 4; ++q)
-            v[u][q] = floatx4{fmaxf(v[u][q].x, 0.f), fmaxf(v[u][q].y, 0.f), fmaxf(v[u][q].z, 0.f),
-                              fmaxf(v[u][q].w, 0.f)};
+          for (int q = 0; q < 4; ++q) v[u][q] = relu4(v[u][q]);
       }
       if constexpr (EPI == GEMM_GELU_BF16) {
 #pragma unroll
@@ -760,11 +663,7 @@ __global__ void __launch_bounds__(256, 2) gemm2_bf16_kernel(GemmBf16Args g) {
 #pragma unroll
           for (int u = 0; u < UB; ++u)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              bf16x4 ob;
-              ob[0] = (bf16)v[u][q].x; ob[1] = (bf16)v[u][q].y; ob[2] = (bf16)v[u][q].z; ob[3] = (bf16)v[u][q].w;
-              *reinterpret_cast<bf16x4*>(o + (u0 + u) * 32 + 8 * q) = ob;
-            }
+            for (int q = 0; q < 4; ++q) *reinterpret_cast<bf16x4*>(o + (u0 + u) * 32 + 8 * q) = to_bf16x4(v[u][q]);
         }
       }
     }
@@ -809,9 +708,7 @@ __global__ void __launch_bounds__(256) ln_bf16_kernel(const float* __restrict__ 
     const floatx4 ww = *reinterpret_cast<const floatx4*>(w + c);
     const floatx4 bb = *reinterpret_cast<const floatx4*>(b + c);
     const floatx4 o = (v[i] - mean) * rstd * ww + bb;
-    bf16x4 ob;
-    ob[0] = (bf16)o.x; ob[1] = (bf16)o.y; ob[2] = (bf16)o.z; ob[3] = (bf16)o.w;
-    *reinterpret_cast<bf16x4*>(yr + c) = ob;
+    *reinterpret_cast<bf16x4*>(yr + c) = to_bf16x4(o);
   }
 }
 
@@ -823,9 +720,7 @@ __global__ void cast_bf16_kernel(const float* __restrict__ x, long ldx, bf16* __
   if (i >= (long)rows * q) return;
   const int r = (int)(i / q), c = (int)(i % q) * 4;
   const floatx4 v = *reinterpret_cast<const floatx4*>(x + (size_t)r * ldx + c);
-  bf16x4 o;
-  o[0] = (bf16)v.x; o[1] = (bf16)v.y; o[2] = (bf16)v.z; o[3] = (bf16)v.w;
-  *reinterpret_cast<bf16x4*>(y + (size_t)r * ldy + c) = o;
+  *reinterpret_cast<bf16x4*>(y + (size_t)r * ldy + c) = to_bf16x4(v);
 }
 
 // rows [0, rows) of a [rows][D] f32 block = vec[D] (the decoder's input token: to_token_embedding of the
@@ -1103,77 +998,53 @@ __global__ void copy_rows_kernel(const float* __restrict__ x, long ldx, float* _
 // ================================================================================== host launchers
 namespace vge {
 
-template <int NW, int SH = 0>
-hipError_t gemm_setup_nw() {
-  const void* ks[8] = {(const void*)gemm_bf16_kernel<GEMM_BF16, NW, SH>, (const void*)gemm_bf16_kernel<GEMM_GELU_BF16, NW, SH>,
-                       (const void*)gemm_bf16_kernel<GEMM_RES_F32, NW, SH>, (const void*)gemm_bf16_kernel<GEMM_PE_F32, NW, SH>,
-                       (const void*)gemm_bf16_kernel<GEMM_F32, NW, SH>, (const void*)gemm_bf16_kernel<GEMM_RELU_BF16, NW, SH>,
-                       (const void*)gemm_bf16_kernel<GEMM_RESB_BF16, NW, SH>,
-                       (const void*)gemm_bf16_kernel<GEMM_RESB_RELU_BF16, NW, SH>};
-  for (auto k : ks) {
-    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, GB_LDS);
-    if (e != hipSuccess) return e;
+// The epilogues the GEMM kernels are instantiated for.  with_epi hands the runtime id to f as a compile-time constant,
+// f(EpiC<EPI>{}); the launchers and the dynamic-LDS setup all go through it (an id outside the list runs as GEMM_F32).
+template <int E>
+using EpiC = std::integral_constant<int, E>;
+constexpr int GEMM_EPIS[] = {GEMM_BF16, GEMM_GELU_BF16, GEMM_RES_F32,   GEMM_PE_F32,
+                             GEMM_F32,  GEMM_RELU_BF16, GEMM_RESB_BF16, GEMM_RESB_RELU_BF16};
+template <class F>
+void with_epi(int epi, F&& f) {
+  switch (epi) {
+    case GEMM_BF16: return f(EpiC<GEMM_BF16>{});
+    case GEMM_GELU_BF16: return f(EpiC<GEMM_GELU_BF16>{});
+    case GEMM_RES_F32: return f(EpiC<GEMM_RES_F32>{});
+    case GEMM_PE_F32: return f(EpiC<GEMM_PE_F32>{});
+    case GEMM_RELU_BF16: return f(EpiC<GEMM_RELU_BF16>{});
+    case GEMM_RESB_BF16: return f(EpiC<GEMM_RESB_BF16>{});
+    case GEMM_RESB_RELU_BF16: return f(EpiC<GEMM_RESB_RELU_BF16>{});
+    default: return f(EpiC<GEMM_F32>{});
   }
-  return hipSuccess;
 }
+template <int EPI>
+constexpr bool GEMMP_EPI = EPI == GEMM_BF16 || EPI == GEMM_GELU_BF16 || EPI == GEMM_RELU_BF16;  // gemmp_bf16_kernel's
 
-template <int SH>
-hipError_t gemm_setup_pm() {  // the partial-M kernels (8 waves): 1x1 convs over n x H x W rows
-  const void* ks[8] = {(const void*)gemm_bf16_kernel<GEMM_BF16, 8, SH, true>,
-                       (const void*)gemm_bf16_kernel<GEMM_GELU_BF16, 8, SH, true>,
-                       (const void*)gemm_bf16_kernel<GEMM_RES_F32, 8, SH, true>,
-                       (const void*)gemm_bf16_kernel<GEMM_PE_F32, 8, SH, true>,
-                       (const void*)gemm_bf16_kernel<GEMM_F32, 8, SH, true>,
-                       (const void*)gemm_bf16_kernel<GEMM_RELU_BF16, 8, SH, true>,
-                       (const void*)gemm_bf16_kernel<GEMM_RESB_BF16, 8, SH, true>,
-                       (const void*)gemm_bf16_kernel<GEMM_RESB_RELU_BF16, 8, SH, true>};
-  for (auto k : ks) {
-    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, GB_LDS);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+// the dynamic-LDS limit of kernel_of(EpiC<EPI>{}) for every epilogue (null = no such instantiation)
+template <class K>
+hipError_t gemm_lds_setup(int bytes, K kernel_of) {
+  hipError_t e = hipSuccess;
+  for (const int epi : GEMM_EPIS)
+    with_epi(epi, [&](auto E) {
+      const void* k = kernel_of(E);
+      if (k && e == hipSuccess) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    });
+  return e;
 }
-
-template <bool PM>
-hipError_t gemmp_setup() {
-  const void* ks[3] = {(const void*)gemmp_bf16_kernel<GEMM_BF16, PM>, (const void*)gemmp_bf16_kernel<GEMM_GELU_BF16, PM>,
-                       (const void*)gemmp_bf16_kernel<GEMM_RELU_BF16, PM>};
-  for (auto k : ks) {
-    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, GB_LDS);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+template <int NW, int SH = 0, bool PM = false>
+hipError_t gemm_setup() {
+  return gemm_lds_setup(GB_LDS, [](auto E) { return (const void*)gemm_bf16_kernel<decltype(E)::value, NW, SH, PM>; });
 }
-
 template <bool PM>
 hipError_t gemm2_setup() {
-  const void* ks[8] = {(const void*)gemm2_bf16_kernel<GEMM_BF16, PM>, (const void*)gemm2_bf16_kernel<GEMM_GELU_BF16, PM>,
-                       (const void*)gemm2_bf16_kernel<GEMM_RES_F32, PM>, (const void*)gemm2_bf16_kernel<GEMM_PE_F32, PM>,
-                       (const void*)gemm2_bf16_kernel<GEMM_F32, PM>, (const void*)gemm2_bf16_kernel<GEMM_RELU_BF16, PM>,
-                       (const void*)gemm2_bf16_kernel<GEMM_RESB_BF16, PM>,
-                       (const void*)gemm2_bf16_kernel<GEMM_RESB_RELU_BF16, PM>};
-  for (auto k : ks) {
-    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return gemm_lds_setup(G2_LDS, [](auto E) { return (const void*)gemm2_bf16_kernel<decltype(E)::value, PM>; });
 }
-
 template <bool PM>
-void launch_gemm2(int epi, const GemmBf16Args& g, hipStream_t s) {
-  const dim3 grid(((g.M + G2_M - 1) / G2_M) * (g.N / G2_N)), blk(256);
-  switch (epi) {
-    case GEMM_BF16: hipLaunchKernelGGL((gemm2_bf16_kernel<GEMM_BF16, PM>), grid, blk, G2_LDS, s, g); break;
-    case GEMM_GELU_BF16: hipLaunchKernelGGL((gemm2_bf16_kernel<GEMM_GELU_BF16, PM>), grid, blk, G2_LDS, s, g); break;
-    case GEMM_RES_F32: hipLaunchKernelGGL((gemm2_bf16_kernel<GEMM_RES_F32, PM>), grid, blk, G2_LDS, s, g); break;
-    case GEMM_PE_F32: hipLaunchKernelGGL((gemm2_bf16_kernel<GEMM_PE_F32, PM>), grid, blk, G2_LDS, s, g); break;
-    case GEMM_RELU_BF16: hipLaunchKernelGGL((gemm2_bf16_kernel<GEMM_RELU_BF16, PM>), grid, blk, G2_LDS, s, g); break;
-    case GEMM_RESB_BF16: hipLaunchKernelGGL((gemm2_bf16_kernel<GEMM_RESB_BF16, PM>), grid, blk, G2_LDS, s, g); break;
-    case GEMM_RESB_RELU_BF16:
-      hipLaunchKernelGGL((gemm2_bf16_kernel<GEMM_RESB_RELU_BF16, PM>), grid, blk, G2_LDS, s, g);
-      break;
-    default: hipLaunchKernelGGL((gemm2_bf16_kernel<GEMM_F32, PM>), grid, blk, G2_LDS, s, g); break;
-  }
+hipError_t gemmp_setup() {
+  return gemm_lds_setup(GB_LDS, [](auto E) -> const void* {
+    if constexpr (GEMMP_EPI<decltype(E)::value>) return (const void*)gemmp_bf16_kernel<decltype(E)::value, PM>;
+    return nullptr;
+  });
 }
 
 hipError_t vit_kernels_setup_dev();
@@ -1193,13 +1064,13 @@ hipError_t vit_kernels_setup() {
 }
 
 hipError_t vit_kernels_setup_dev() {
-  hipError_t e = gemm_setup_nw<8>();
+  hipError_t e = gemm_setup<8>();
   if (e == hipSuccess) e = gemm2_setup<false>();
   if (e == hipSuccess) e = gemm2_setup<true>();
-  if (e == hipSuccess) e = gemm_setup_pm<0>();
-  if (e == hipSuccess) e = gemm_setup_pm<1>();
-  if (e == hipSuccess) e = gemm_setup_nw<4>();
-  if (e == hipSuccess) e = gemm_setup_nw<8, 1>();
+  if (e == hipSuccess) e = gemm_setup<8, 0, true>();  // the partial-M kernels (8 waves): 1x1 convs over n x H x W rows
+  if (e == hipSuccess) e = gemm_setup<8, 1, true>();
+  if (e == hipSuccess) e = gemm_setup<4>();
+  if (e == hipSuccess) e = gemm_setup<8, 1>();
   if (e == hipSuccess) e = gemmp_setup<false>();
   if (e == hipSuccess) e = gemmp_setup<true>();
   if (e != hipSuccess) return e;
@@ -1211,26 +1082,25 @@ hipError_t vit_kernels_setup_dev() {
 }
 
 // VGE_GEMM_WAVES, read once: 1 (default) = by epilogue: the bf16-output epilogues (bias, GELU, the 1x1 convs' ReLU /
-// residual) on the 16x16x32 form of the 8-wave kernel, the f32-output ones on 32x32x16 (the 16x16x32 form is bit-identical and the chip holds a higher clock on
-// it: qkv +4-8 %, fc1 +2-3 %; proj / fc2 with their f32 residual 0-3 % slower: profiles/ab_r05p_gemm_ablation.json,
-// ab_r05q_gemm2.json); 8 / 16 = always 32x32x16 / 16x16x32; 4 = 4 waves of 128 x 128; 2 = gemm2
+// residual) on the 16x16x32 form of the 8-wave kernel, the f32-output ones on 32x32x16 (the 16x16x32 form is
+// bit-identical and the chip holds a higher clock on it: qkv +4-8 %, fc1 +2-3 %; proj / fc2 with their f32 residual
+// 0-3 % slower: profiles/ab_r05p_gemm_ablation.json, ab_r05q_gemm2.json); 8 / 16 = always 32x32x16 / 16x16x32;
+// 4 = 4 waves of 128 x 128; 2 = gemm2
 static int g_gemm_waves = 0;
 
 template <int NW, int SH = 0, bool PM = false>
 void launch_gemm_nw(int epi, dim3 grid, const GemmBf16Args& g, hipStream_t s) {
-  const dim3 blk(64 * NW);
-  switch (epi) {
-    case GEMM_BF16: hipLaunchKernelGGL((gemm_bf16_kernel<GEMM_BF16, NW, SH, PM>), grid, blk, GB_LDS, s, g); break;
-    case GEMM_GELU_BF16: hipLaunchKernelGGL((gemm_bf16_kernel<GEMM_GELU_BF16, NW, SH, PM>), grid, blk, GB_LDS, s, g); break;
-    case GEMM_RES_F32: hipLaunchKernelGGL((gemm_bf16_kernel<GEMM_RES_F32, NW, SH, PM>), grid, blk, GB_LDS, s, g); break;
-    case GEMM_PE_F32: hipLaunchKernelGGL((gemm_bf16_kernel<GEMM_PE_F32, NW, SH, PM>), grid, blk, GB_LDS, s, g); break;
-    case GEMM_RELU_BF16: hipLaunchKernelGGL((gemm_bf16_kernel<GEMM_RELU_BF16, NW, SH, PM>), grid, blk, GB_LDS, s, g); break;
-    case GEMM_RESB_BF16: hipLaunchKernelGGL((gemm_bf16_kernel<GEMM_RESB_BF16, NW, SH, PM>), grid, blk, GB_LDS, s, g); break;
-    case GEMM_RESB_RELU_BF16:
-      hipLaunchKernelGGL((gemm_bf16_kernel<GEMM_RESB_RELU_BF16, NW, SH, PM>), grid, blk, GB_LDS, s, g);
-      break;
-    default: hipLaunchKernelGGL((gemm_bf16_kernel<GEMM_F32, NW, SH, PM>), grid, blk, GB_LDS, s, g); break;
-  }
+  with_epi(epi, [&](auto E) {
+    hipLaunchKernelGGL((gemm_bf16_kernel<decltype(E)::value, NW, SH, PM>), grid, dim3(64 * NW), GB_LDS, s, g);
+  });
+}
+
+template <bool PM>
+void launch_gemm2(int epi, const GemmBf16Args& g, hipStream_t s) {
+  const dim3 grid(((g.M + G2_M - 1) / G2_M) * (g.N / G2_N));
+  with_epi(epi, [&](auto E) {
+    hipLaunchKernelGGL((gemm2_bf16_kernel<decltype(E)::value, PM>), grid, dim3(256), G2_LDS, s, g);
+  });
 }
 
 // shapes are validated by the callers (vge_hmr.cpp, vge_cnn.hip): N % 256 == K % 64 == 0, 16-B aligned rows; any M
@@ -1239,15 +1109,8 @@ void launch_gemm_nw(int epi, dim3 grid, const GemmBf16Args& g, hipStream_t s) {
 static int g_gemm_persist = -1;
 
 static int device_cus() {
-  static std::atomic<int> cus{0};
-  int c = cus.load(std::memory_order_relaxed);
-  if (c > 0) return c;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      c <= 0)
-    c = 256;
-  cus.store(c, std::memory_order_relaxed);
-  return c;
+  const int c = device_cu_count();
+  return c > 0 ? c : 256;
 }
 
 // the persistent kernel's conditions: a residual-free bf16 epilogue with a bias, K / 32 >= 6, more tiles than CUs (one
@@ -1260,27 +1123,7 @@ bool gemm_persist_ok(int epi, const GemmBf16& a) {
   return ntiles > device_cus() && (long)GB_M * a.ldo * 2 < (1L << 31);
 }
 
-template <int EPI, bool PM>
-static void launch_gemmp_t(const GemmBf16Args& g, int grid, hipStream_t s) {
-  hipLaunchKernelGGL((gemmp_bf16_kernel<EPI, PM>), dim3(grid), dim3(512), GB_LDS, s, g);
-}
-
-static hipError_t launch_gemmp(int epi, const GemmBf16Args& g, hipStream_t s) {
-  const int grid = device_cus() & ~7;  // one workgroup per CU, a multiple of 8 (the XCD-grouped tile walk)
-  const bool pm = g.M % GB_M != 0;
-  switch (epi) {
-    case GEMM_BF16: pm ? launch_gemmp_t<GEMM_BF16, true>(g, grid, s) : launch_gemmp_t<GEMM_BF16, false>(g, grid, s); break;
-    case GEMM_GELU_BF16:
-      pm ? launch_gemmp_t<GEMM_GELU_BF16, true>(g, grid, s) : launch_gemmp_t<GEMM_GELU_BF16, false>(g, grid, s);
-      break;
-    default: pm ? launch_gemmp_t<GEMM_RELU_BF16, true>(g, grid, s) : launch_gemmp_t<GEMM_RELU_BF16, false>(g, grid, s);
-  }
-  return hipGetLastError();
-}
-
-hipError_t launch_gemm_bf16_persistent(int epi, const GemmBf16& a, hipStream_t s) {
-  if (!gemm_persist_ok(epi, a)) return hipErrorInvalidValue;
-  if (const hipError_t e = vit_kernels_setup(); e != hipSuccess) return e;
+static GemmBf16Args to_args(const GemmBf16& a) {
   GemmBf16Args g;
   g.A = reinterpret_cast<const bf16*>(a.A);
   g.W = reinterpret_cast<const bf16*>(a.W);
@@ -1291,7 +1134,25 @@ hipError_t launch_gemm_bf16_persistent(int epi, const GemmBf16& a, hipStream_t s
   g.lda = a.lda; g.ldw = a.ldw; g.ldo = a.ldo; g.ldr = a.ldr;
   g.M = a.M; g.N = a.N; g.K = a.K; g.tokens = a.tokens;
   g.resb = reinterpret_cast<const bf16*>(a.resb);
-  return launch_gemmp(epi, g, s);
+  return g;
+}
+
+hipError_t launch_gemm_bf16_persistent(int epi, const GemmBf16& a, hipStream_t s) {
+  if (!gemm_persist_ok(epi, a)) return hipErrorInvalidValue;
+  if (const hipError_t e = vit_kernels_setup(); e != hipSuccess) return e;
+  const GemmBf16Args g = to_args(a);
+  const dim3 grid(device_cus() & ~7);  // one workgroup per CU, a multiple of 8 (the XCD-grouped tile walk)
+  const bool pm = g.M % GB_M != 0;
+  with_epi(epi, [&](auto E) {
+    constexpr int EPI = decltype(E)::value;
+    if constexpr (GEMMP_EPI<EPI>) {  // (gemm_persist_ok: no other id comes here)
+      if (pm)
+        hipLaunchKernelGGL((gemmp_bf16_kernel<EPI, true>), grid, dim3(512), GB_LDS, s, g);
+      else
+        hipLaunchKernelGGL((gemmp_bf16_kernel<EPI, false>), grid, dim3(512), GB_LDS, s, g);
+    }
+  });
+  return hipGetLastError();
 }
 
 hipError_t launch_gemm_bf16(int epi, const GemmBf16& a, hipStream_t s) {
@@ -1300,16 +1161,7 @@ hipError_t launch_gemm_bf16(int epi, const GemmBf16& a, hipStream_t s) {
     g_gemm_persist = (e && e[0] == '1') ? 1 : 0;
   }
   if (g_gemm_persist == 1 && gemm_persist_ok(epi, a)) return launch_gemm_bf16_persistent(epi, a, s);
-  GemmBf16Args g;
-  g.A = reinterpret_cast<const bf16*>(a.A);
-  g.W = reinterpret_cast<const bf16*>(a.W);
-  g.out = a.out;
-  g.bias = a.bias;
-  g.res = a.res;
-  g.pos = a.pos;
-  g.lda = a.lda; g.ldw = a.ldw; g.ldo = a.ldo; g.ldr = a.ldr;
-  g.M = a.M; g.N = a.N; g.K = a.K; g.tokens = a.tokens;
-  g.resb = reinterpret_cast<const bf16*>(a.resb);
+  const GemmBf16Args g = to_args(a);
   const bool rb = epi == GEMM_RESB_BF16 || epi == GEMM_RESB_RELU_BF16;
   if (a.M < 1 || a.N % GB_N || a.K % 64 || (rb && !a.resb) || (epi == GEMM_PE_F32 && a.tokens != AT_T))
     return hipErrorInvalidValue;

@@ -150,11 +150,6 @@ __device__ __forceinline__ void run_stream(Acc<R, N>& acc, const void* gw, int n
   }
 }
 
-__host__ __device__ __forceinline__ int xcd_remap(int b, int nblk) {
-  const int q8 = nblk >> 3, r8 = nblk & 7, x8 = b & 7;
-  return (x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8) + (b >> 3);
-}
-
 // Unit u of a ConvSched: encoder e, first window w0, quad (true) or pair.  Uniform over the block (scalar loop over
 // the <= 16 prefix sums in kernel-argument memory).
 __host__ __device__ __forceinline__ bool conv_unit(const vge::ConvSched& cs, int u, int& e, int& w0) {
