@@ -6,8 +6,10 @@
  * chroma upsampling, the 16-bit fixed-point YCbCr -> RGB).  This ABI reproduces those pixels exactly, split at the
  * host/device line:
  *   probe            headers only: size, component count, luma sampling factors
- *   entropy decode   host threads: marker parsing + Huffman decoding -> int16 coefficients (natural order) and the
- *                    uint16 quantisation tables, into caller-provided (normally pinned) buffers
+ *   entropy decode   marker parsing + Huffman decoding -> int16 coefficients (natural order) and the uint16
+ *                    quantisation tables.  Host threads, one frame each, from paths or from files in memory, into
+ *                    caller-provided (normally pinned) buffers; or the device, parallel inside a frame, from file
+ *                    bytes in device memory into device buffers (vge_jpeg_entropy_decode_device, below)
  *   reconstruct      device (HIP, caller's stream) or host (plain C++): dequantise, IDCT, upsample, colour convert
  *                    -> uint8 [F, H, W, 3] RGB; grayscale is replicated to three channels (cv2.imread's default flag)
  * Both reconstructs share their arithmetic through one host/device header (csrc/vge_jpeg_math.h).
@@ -154,6 +156,53 @@ int vge_jpeg_entropy_plan(const int16_t* coef, const vge_jpeg_layout* layout, in
 int vge_jpeg_entropy_emit(const void* workspace, const uint16_t* qtab, const vge_jpeg_layout* layout, int n_frames,
                           const int64_t* offsets, uint8_t* out, int64_t out_bytes, void* stream);
 int vge_jpeg_entropy_segment_blocks(void);
+
+/* ---- Files held in memory: the probe's and the entropy decoder's twins for a packed buffer.
+ *
+ * File i is sizes[i] bytes at data + offsets[i] of a buffer of data_bytes bytes -- the (data, offsets) pair the
+ * in-memory encoders above produce.  Files may be packed with gaps and in any order.  A file with a negative offset or
+ * size, or one that does not lie inside [0, data_bytes), gets VGE_JPEG_ERR_ARG and none of its bytes is read; an empty
+ * file is VGE_JPEG_ERR_IO, as an empty file on disk is.  Everything else -- outputs, per-frame statuses, the frame that
+ * fails alone -- is vge_jpeg_probe's and vge_jpeg_entropy_decode's contract, to the bit; the path calls map the file
+ * and run the same code.  status may be NULL on the host calls. */
+/* Host threads over files, for callers that want the raw files in one (pinned) buffer: sizes[i] is the length of
+ * paths[i] (0 for a path that is no readable regular file); read_files then reads sizes[i] bytes of paths[i] to
+ * data + offsets[i].  A file that cannot be read or has become shorter gets VGE_JPEG_ERR_IO (_ARG when it does
+ * not lie inside data_bytes) and zero bytes in its place, and does not disturb the others.  status may be NULL. */
+int vge_jpeg_file_sizes(const char* const* paths, int n, int n_threads, int64_t* sizes);
+int vge_jpeg_read_files(const char* const* paths, int n, int n_threads, const int64_t* offsets, const int64_t* sizes,
+                        uint8_t* data, int64_t data_bytes, int32_t* status);
+
+int vge_jpeg_probe_mem(const uint8_t* data, int64_t data_bytes, const int64_t* offsets, const int64_t* sizes, int n,
+                       int n_threads, vge_jpeg_info* info);
+int vge_jpeg_entropy_decode_mem(const uint8_t* data, int64_t data_bytes, const int64_t* offsets, const int64_t* sizes,
+                                int n, int n_threads, const vge_jpeg_layout* layout, int16_t* coef, uint16_t* qtab,
+                                int32_t* status);
+
+/* Device entropy decoder (csrc/vge_jpeg_dehuff.hip): the same files in device memory -> coef / qtab / status in device
+ * memory, equal to the host decoder's; Huffman decoding is parallel inside a frame by self-synchronisation.  Every
+ * pointer but the layout is a device pointer (workspace and coef 16-byte aligned, offsets / sizes 8-byte, status /
+ * rounds 4-byte).  The call is asynchronous on `stream`, allocates nothing and learns nothing from the device: its
+ * return value covers the arguments the host can see and the launches (VGE_JPEG_ERR_ARG / _HIP); the per-frame codes
+ * are in status[] only.  The kernels own every block of every frame: coef need not be cleared, a failed frame is zeroed
+ * with tables of 1.  rounds (may be NULL): int32 [n], the most synchronisation rounds any tile of frame i needed (1: a
+ * single subsequence; 2: every guess was right after one carry).
+ *   workspace_bytes  for n_frames files inside a buffer of total_file_bytes; pass the same value as data_bytes.  The
+ *                    workspace holds one unstuffed copy of every scan: sizes that add up to no more than
+ *                    total_file_bytes always fit; where files overlap so far that the copies do not, the files from
+ *                    the first that no longer fits get VGE_JPEG_ERR_ARG.
+ * A file of 2^28 bytes or more gets VGE_JPEG_ERR_ARG (bit positions are 32-bit).
+ * One class of corrupt stream is outside the equality with the host: a restart interval with a whole surplus byte or
+ * more between its last MCU and its marker.  The host's verdict there depends on how far its 64-bit reader has read
+ * ahead; the device always gives VGE_JPEG_ERR_IO.
+ * subsequence_bytes: the scan bytes one lane starts on; tile_bytes: the scan bytes one workgroup covers per pass over a
+ * restart interval (exported for the tests, which make sure a case spans several). */
+size_t vge_jpeg_entropy_decode_workspace_bytes(const vge_jpeg_layout* layout, int n_frames, int64_t total_file_bytes);
+int vge_jpeg_entropy_decode_device(const uint8_t* data, int64_t data_bytes, const int64_t* offsets,
+                                   const int64_t* sizes, int n_frames, const vge_jpeg_layout* layout, void* workspace,
+                                   int16_t* coef, uint16_t* qtab, int32_t* status, int32_t* rounds, void* stream);
+int vge_jpeg_entropy_decode_subsequence_bytes(void);
+int vge_jpeg_entropy_decode_tile_bytes(void);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 """Frames per second of vge.frames.load_frames on JPEG frame folders, split into its stages, beside Pillow.
 
     python tools/bench_frames.py [--frames 1024] [--size 256] [--quality 95] [--threads 16] [--folder DIR]
-                                 [--out profiles/jpeg_decode.json]
+                                 [--entropy host|device] [--out profiles/jpeg_decode.json]
 
 Writes its own JPEGs with Pillow (vge.synth.make_frames content, 4:2:0, quality 95: what cv2.imwrite writes) into a
 temporary folder, or reads the *.jpg files of --folder (cycled up to --frames).  Needs a GPU: there is no fallback.
@@ -12,6 +12,14 @@ Stages, each warmed up and repeated, reported as median [min, max] over the repe
   kernel    vge_jpeg_reconstruct, --inner launches per repeat                      (device events / launches)
   e2e       load_frames(paths, device) ending in a device synchronise              (host clock)
   pillow    PIL decode of the same files on --threads host threads                 (host clock; when Pillow imports)
+With --entropy device the rows of the device entropy decoder are measured as well (and written to
+profiles/jpeg_decode_device.json unless --out says otherwise):
+  read_upload     host threads read the raw files into one pinned buffer + its upload    (host clock, ends in a sync)
+  prepare         headers + scan preparation: the same call stopped before its decode kernel   (device events)
+  device_entropy  the whole vge_jpeg_entropy_decode_device call: prepare + decode (all rounds) + write + DC
+                  (device events); decode_write_dc is the difference of the two medians
+  rounds          mean and max of rounds[]
+  e2e_device      load_frames(paths, device, entropy="device") ending in a device synchronise   (host clock)
 The kernel's HBM floor is (coefficient + table + RGB bytes) / 6.3 TB/s (the achievable rate of a float4 copy).
 """
 from __future__ import annotations
@@ -62,8 +70,11 @@ def main(argv=None) -> int:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=9)
     ap.add_argument("--inner", type=int, default=50, help="kernel launches per timed repeat")
-    ap.add_argument("--out", default=str(REPO / "profiles" / "jpeg_decode.json"))
+    ap.add_argument("--entropy", choices=("host", "device"), default="host")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
+    if args.out is None:
+        args.out = str(REPO / "profiles" / ("jpeg_decode.json" if args.entropy == "host" else "jpeg_decode_device.json"))
 
     import torch
     from vge import frames as FR
@@ -156,6 +167,65 @@ def main(argv=None) -> int:
         p = [pillow() for _ in range(args.repeats)]
         res["pillow_decode_s"] = spread([t for t, _ in p])
         exact = bool(np.array_equal(frames.cpu().numpy(), np.stack(p[-1][1])))
+    device_rows = None
+    if args.entropy == "device":
+        raw, raw_off, raw_size = FR._read_files(paths, args.threads, pin=True)
+        raw_d = raw.to(dev)
+        nbytes = int(raw.numel())
+        table = torch.from_numpy(np.stack([raw_off, raw_size])).to(dev)
+        ws = torch.empty(int(lib.vge_jpeg_entropy_decode_workspace_bytes(C.byref(lay), n, nbytes)), dtype=torch.uint8,
+                         device=dev)
+        status_d = torch.empty(n, dtype=torch.int32, device=dev)
+        rounds_d = torch.empty(n, dtype=torch.int32, device=dev)
+
+        def read_upload():
+            t = time.perf_counter()
+            r, _, _ = FR._read_files(paths, args.threads, pin=True)
+            r.to(dev, non_blocking=True)
+            torch.cuda.synchronize()
+            return time.perf_counter() - t
+
+        def device_entropy():
+            L.check(lib.vge_jpeg_entropy_decode_device(raw_d.data_ptr(), nbytes, table[0].data_ptr(),
+                                                       table[1].data_ptr(), n,
+                                                       C.byref(lay), ws.data_ptr(), coef_d.data_ptr(),
+                                                       qtab_d.data_ptr(), status_d.data_ptr(), rounds_d.data_ptr(),
+                                                       stream.cuda_stream), "vge_jpeg_entropy_decode_device")
+
+        def prepare():   # the same call stopped after headers + scan preparation (a hook of the library for this tool)
+            lib.vge_debug_jpeg_dehuff_prepare_only(1)
+            try:
+                return events(device_entropy)
+            finally:
+                lib.vge_debug_jpeg_dehuff_prepare_only(0)
+
+        def e2e_device():
+            t = time.perf_counter()
+            fr, kept = FR.load_frames(paths, device=dev, threads=args.threads, entropy="device")
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t
+            assert kept.size == n
+            return dt, fr
+
+        for _ in range(args.warmup):
+            read_upload(); events(device_entropy); prepare(); e2e_device()
+        res["read_upload_s"] = spread([read_upload() for _ in range(args.repeats)])
+        res["prepare_s"] = spread([prepare() for _ in range(args.repeats)])
+        res["device_entropy_s"] = spread([events(device_entropy) for _ in range(args.repeats)])
+        ed = [e2e_device() for _ in range(args.repeats)]
+        res["e2e_device_s"] = spread([t for t, _ in ed])
+        device_entropy()
+        torch.cuda.synchronize()
+        assert int(status_d.abs().sum()) == 0
+        r = rounds_d.cpu().numpy()
+        device_rows = {
+            "file_bytes": nbytes, "rounds_mean": float(r.mean()), "rounds_max": int(r.max()),
+            "decode_write_dc_s": res["device_entropy_s"]["median"] - res["prepare_s"]["median"],
+            "subsequence_bytes": int(lib.vge_jpeg_entropy_decode_subsequence_bytes()),
+            "tile_bytes": int(lib.vge_jpeg_entropy_decode_tile_bytes()),
+            "equals_host_path": bool(torch.equal(ed[-1][1], frames)),
+            "coefficients_equal_host": bool(torch.equal(coef_d.cpu(), coef) and torch.equal(qtab_d.cpu(), qtab)),
+        }
     coef_b, tab_b, rgb_b = coef.numel() * 2, qtab.numel() * 2, out.numel()
     floor = (coef_b + tab_b + rgb_b) / HBM_ACHIEVABLE
     k = res["kernel_s"]["median"]
@@ -173,6 +243,8 @@ def main(argv=None) -> int:
         "equals_pillow": exact if exact is not None else "not measured (Pillow not importable)",
         "pillow": getattr(PIL, "__version__", None),
     }
+    if device_rows is not None:
+        report["device_entropy"] = device_rows
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(report, f, indent=1)

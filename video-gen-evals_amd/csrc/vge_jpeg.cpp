@@ -1,7 +1,8 @@
 // Host half of the JPEG frame front end (include/vge_frames.h): header probe, the baseline entropy decoder (marker
-// parsing + Huffman decoding into int16 coefficients, a pool of host threads over frames) and the plain-C++
-// reconstruct that the no-GPU path and the CPU tests use.  The device reconstruct is vge_jpeg.hip; both take their
-// arithmetic from vge_jpeg_math.h.  Below them the mirror images for encoding: libjpeg's quantisation tables, the
+// parsing + Huffman decoding into int16 coefficients, a pool of host threads over frames; from paths or from files in
+// memory) and the plain-C++ reconstruct that the no-GPU path and the CPU tests use.  The device reconstruct is
+// vge_jpeg.hip; both take their arithmetic from vge_jpeg_math.h.  The header parser is vge_jpeg_header.h, shared with the
+// device entropy decoder (vge_jpeg_dehuff.hip).  Below them the mirror images for encoding: libjpeg's quantisation tables, the
 // plain-C++ forward transform (the device one is vge_jpeg_enc.hip) and the baseline Huffman encoder, into files or into
 // memory (the device one is vge_jpeg_huff.hip; the Huffman tables both carry are vge_jpeg_huff_tables.h).
 #include <fcntl.h>
@@ -21,6 +22,7 @@
 #include "../../include/vge_frames.h"
 #include "../../include/vge_ingest.h"
 #include "vge_error.h"
+#include "vge_jpeg_header.h"
 #include "vge_jpeg_huff_tables.h"
 #include "vge_jpeg_math.h"
 
@@ -88,144 +90,20 @@ const char* status_name(int st) {
   }
 }
 
-// ------------------------------------------------------------------ headers
-struct Huff {
-  bool ok = false;
-  uint8_t look_len[512];  // 9-bit lookahead: code length (0: longer than 9 bits)
-  uint8_t look_sym[512];
-  int32_t maxcode[18];    // largest code of each length, -1 if none
-  int32_t valoff[17];     // index of the first value of a length minus its first code
-  uint8_t vals[256];
+// ------------------------------------------------------------------ headers: vge_jpeg_header.h, shared with the device
+using vge_jpeg::Header;
+using vge_jpeg::Huff;
+using vge_jpeg::parse_header;
+using vge_jpeg::same_shape;
+
+// A heap Header (~12 KB of tables: off the worker's stack) in parse_header's start state.
+struct HeaderBox {
+  Header* h;
+  HeaderBox() : h(new Header()) { vge_jpeg::header_init(*h); }
+  ~HeaderBox() { delete h; }
+  HeaderBox(const HeaderBox&) = delete;
+  HeaderBox& operator=(const HeaderBox&) = delete;
 };
-
-bool build_huff(const uint8_t* bits /*[16]*/, const uint8_t* vals, int nvals, Huff& h) {
-  memset(h.look_len, 0, sizeof(h.look_len));
-  memcpy(h.vals, vals, (size_t)nvals);
-  int code = 0, k = 0;
-  for (int l = 1; l <= 16; ++l) {
-    const int cnt = bits[l - 1];
-    h.valoff[l] = k - code;
-    if (cnt) {
-      if (code + cnt > (1 << l)) return false;  // over-subscribed
-      if (l <= 9)
-        for (int i = 0; i < cnt; ++i) {
-          const int first = (code + i) << (9 - l);
-          for (int j = 0; j < (1 << (9 - l)); ++j) {
-            h.look_len[first + j] = (uint8_t)l;
-            h.look_sym[first + j] = vals[k + i];
-          }
-        }
-      k += cnt;
-      code += cnt;
-      h.maxcode[l] = code - 1;
-    } else {
-      h.maxcode[l] = -1;
-    }
-    code <<= 1;
-  }
-  h.maxcode[17] = 0x7fffffff;
-  h.ok = true;
-  return true;
-}
-
-struct Header {
-  int width = 0, height = 0, n_comp = 0;
-  int cid[3] = {0, 0, 0}, h[3] = {1, 1, 1}, v[3] = {1, 1, 1}, tq[3] = {0, 0, 0};
-  int td[3] = {0, 0, 0}, ta[3] = {0, 0, 0};
-  uint16_t q[4][64];  // natural order
-  bool q_ok[4] = {false, false, false, false};
-  Huff dc[4], ac[4];
-  int restart = 0;
-  size_t scan = 0;  // offset of the entropy-coded data
-};
-
-inline int be16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
-
-// Parses SOI .. SOS.  Returns a status; `tables` false: sizes only (the probe), the tables are still validated.
-int parse_header(const uint8_t* p, size_t n, Header& H) {
-  if (n < 4 || p[0] != 0xFF || p[1] != 0xD8) return VGE_JPEG_ERR_IO;
-  size_t q = 2;
-  bool sof = false;
-  while (true) {
-    if (q + 4 > n) return VGE_JPEG_ERR_IO;
-    if (p[q] != 0xFF) return VGE_JPEG_ERR_IO;
-    while (q < n && p[q] == 0xFF) ++q;  // fill bytes
-    if (q >= n) return VGE_JPEG_ERR_IO;
-    const int m = p[q++];
-    if (m == 0xD8 || m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;  // no payload
-    if (m == 0xD9) return VGE_JPEG_ERR_IO;                             // EOI before any scan
-    if (q + 2 > n) return VGE_JPEG_ERR_IO;
-    const int len = be16(p + q);
-    if (len < 2 || q + (size_t)len > n) return VGE_JPEG_ERR_IO;
-    const uint8_t* s = p + q + 2;
-    const int sl = len - 2;
-    if (m == 0xC0 || m == 0xC1 || m == 0xC2 || m == 0xC3 || (m >= 0xC5 && m <= 0xC7) || (m >= 0xC9 && m <= 0xCB) ||
-        (m >= 0xCD && m <= 0xCF)) {
-      if (sl < 6) return VGE_JPEG_ERR_IO;
-      H.height = be16(s + 1);
-      H.width = be16(s + 3);
-      H.n_comp = s[5];
-      if (m >= 0xC9) return VGE_JPEG_ERR_ARITHMETIC;
-      if (m != 0xC0 && m != 0xC1) return VGE_JPEG_ERR_PROGRESSIVE;
-      if (s[0] != 8) return VGE_JPEG_ERR_PRECISION;
-      if (m == 0xC1) return VGE_JPEG_ERR_PROGRESSIVE;  // extended sequential: not the baseline process
-      if (H.n_comp != 1 && H.n_comp != 3) return VGE_JPEG_ERR_COMPONENTS;
-      if (sl < 6 + 3 * H.n_comp || H.width < 1 || H.height < 1 || sof) return VGE_JPEG_ERR_IO;
-      for (int c = 0; c < H.n_comp; ++c) {
-        H.cid[c] = s[6 + 3 * c];
-        H.h[c] = s[7 + 3 * c] >> 4;
-        H.v[c] = s[7 + 3 * c] & 15;
-        H.tq[c] = s[8 + 3 * c];
-        if (H.h[c] < 1 || H.h[c] > 4 || H.v[c] < 1 || H.v[c] > 4 || H.tq[c] > 3) return VGE_JPEG_ERR_IO;
-      }
-      if (H.n_comp == 1) {
-        H.h[0] = H.v[0] = 1;  // a single-component scan is not interleaved: one block per MCU whatever the factors
-      } else {
-        const bool luma = (H.h[0] == 1 && H.v[0] == 1) || (H.h[0] == 2 && H.v[0] == 1) || (H.h[0] == 2 && H.v[0] == 2);
-        if (!luma || H.h[1] != 1 || H.v[1] != 1 || H.h[2] != 1 || H.v[2] != 1) return VGE_JPEG_ERR_SAMPLING;
-      }
-      sof = true;
-    } else if (m == 0xDB) {  // DQT
-      int o = 0;
-      while (o < sl) {
-        const int pq = s[o] >> 4, t = s[o] & 15;
-        if (pq != 0) return pq == 1 ? VGE_JPEG_ERR_PRECISION : VGE_JPEG_ERR_IO;
-        if (t > 3 || o + 65 > sl) return VGE_JPEG_ERR_IO;
-        for (int k = 0; k < 64; ++k) H.q[t][kZigzag[k]] = s[o + 1 + k];
-        H.q_ok[t] = true;
-        o += 65;
-      }
-    } else if (m == 0xC4) {  // DHT
-      int o = 0;
-      while (o < sl) {
-        if (o + 17 > sl) return VGE_JPEG_ERR_IO;
-        const int tc = s[o] >> 4, t = s[o] & 15;
-        int cnt = 0;
-        for (int k = 0; k < 16; ++k) cnt += s[o + 1 + k];
-        if (tc > 1 || t > 3 || cnt > 256 || o + 17 + cnt > sl) return VGE_JPEG_ERR_IO;
-        if (!build_huff(s + o + 1, s + o + 17, cnt, tc ? H.ac[t] : H.dc[t])) return VGE_JPEG_ERR_IO;
-        o += 17 + cnt;
-      }
-    } else if (m == 0xDD) {  // DRI
-      if (sl < 2) return VGE_JPEG_ERR_IO;
-      H.restart = be16(s);
-    } else if (m == 0xDA) {  // SOS
-      if (!sof) return VGE_JPEG_ERR_IO;
-      if (sl < 1 || s[0] != H.n_comp || sl < 1 + 2 * H.n_comp + 3) return VGE_JPEG_ERR_IO;  // one interleaved scan
-      for (int c = 0; c < H.n_comp; ++c) {
-        if (s[1 + 2 * c] != H.cid[c]) return VGE_JPEG_ERR_IO;
-        H.td[c] = s[2 + 2 * c] >> 4;
-        H.ta[c] = s[2 + 2 * c] & 15;
-        if (H.td[c] > 3 || H.ta[c] > 3 || !H.dc[H.td[c]].ok || !H.ac[H.ta[c]].ok || !H.q_ok[H.tq[c]])
-          return VGE_JPEG_ERR_IO;
-      }
-      H.scan = q + (size_t)len;
-      return VGE_JPEG_OK;
-    }
-    // APPn, COM, DAC, DNL, ...: skipped
-    q += (size_t)len;
-  }
-}
 
 // ------------------------------------------------------------------ entropy-coded segment
 struct Bits {
@@ -307,19 +185,15 @@ bool decode_block(Bits& b, const Huff& dc, const Huff& ac, const uint16_t* q, in
   return l1 <= VGE_JPEG_BLOCK_L1_MAX;  // the reconstructs' 32-bit IDCT bound (vge_jpeg_math.h)
 }
 
-bool same_shape(const Header& H, const vge_jpeg_layout& L) {
-  return H.width == L.width && H.height == L.height && H.n_comp == L.n_comp && H.h[0] == L.h0 && H.v[0] == L.v0;
-}
-
-int decode_frame(const char* path, const vge_jpeg_layout& L, int16_t* coef, uint16_t* qtab) {
-  Mapped f(path);
-  if (!f.ok) return VGE_JPEG_ERR_IO;
-  Header* Hp = new Header();  // ~6 KB of tables: off the worker's stack
-  struct Del {
-    Header* h;
-    ~Del() { delete h; }
-  } del{Hp};
-  Header& H = *Hp;
+// One file in memory, data[0 .. size).  An empty file is what an unreadable one is: VGE_JPEG_ERR_IO.
+int decode_frame_mem(const uint8_t* data, size_t size, const vge_jpeg_layout& L, int16_t* coef, uint16_t* qtab) {
+  if (size == 0) return VGE_JPEG_ERR_IO;
+  struct {
+    const uint8_t* p;
+    size_t n;
+  } f{data, size};
+  HeaderBox box;
+  Header& H = *box.h;
   const int st = parse_header(f.p, f.n, H);
   if (st != VGE_JPEG_OK) return st;
   if (!same_shape(H, L)) return VGE_JPEG_ERR_SHAPE;
@@ -352,6 +226,39 @@ int decode_frame(const char* path, const vge_jpeg_layout& L, int16_t* coef, uint
     if (b.overrun()) return VGE_JPEG_ERR_IO;  // ran past the end of the data: truncated
     if (until_restart > 0) --until_restart;
   }
+  return VGE_JPEG_OK;
+}
+
+int decode_frame(const char* path, const vge_jpeg_layout& L, int16_t* coef, uint16_t* qtab) {
+  Mapped f(path);
+  if (!f.ok) return VGE_JPEG_ERR_IO;
+  return decode_frame_mem(f.p, f.n, L, coef, qtab);
+}
+
+// Headers only of one file in memory -> I; the probe's status.
+int probe_mem(const uint8_t* data, size_t size, vge_jpeg_info& I) {
+  if (size == 0) return VGE_JPEG_ERR_IO;
+  HeaderBox box;
+  const int s = parse_header(data, size, *box.h);
+  I.width = box.h->width;
+  I.height = box.h->height;
+  I.n_comp = box.h->n_comp;
+  I.h0 = box.h->h[0];
+  I.v0 = box.h->v[0];
+  return s;
+}
+
+// File i of a packed buffer lies inside it.
+bool range_ok(int64_t off, int64_t size, int64_t data_bytes) {
+  return off >= 0 && size >= 0 && off <= data_bytes && size <= data_bytes - off;
+}
+
+int first_failure_mem(const int32_t* st, int n, const char* what) {
+  for (int i = 0; i < n; ++i)
+    if (st[i] != VGE_JPEG_OK) {
+      set_last_error(std::string(what) + ": file " + std::to_string(i) + ": " + status_name(st[i]));
+      return st[i];
+    }
   return VGE_JPEG_OK;
 }
 
@@ -839,22 +746,101 @@ int vge_jpeg_probe(const char* const* paths, int n, int n_threads, vge_jpeg_info
     int s = VGE_JPEG_ERR_ARG;
     if (paths[i]) {
       Mapped f(paths[i]);
-      if (!f.ok) {
-        s = VGE_JPEG_ERR_IO;
-      } else {
-        Header* H = new Header();
-        s = parse_header(f.p, f.n, *H);
-        I.width = H->width;
-        I.height = H->height;
-        I.n_comp = H->n_comp;
-        I.h0 = H->h[0];
-        I.v0 = H->v[0];
-        delete H;
-      }
+      s = f.ok ? probe_mem(f.p, f.n, I) : VGE_JPEG_ERR_IO;
     }
     I.status = st[(size_t)i] = s;
   });
   return first_failure(st.data(), n, paths, "vge_jpeg_probe");
+}
+
+int vge_jpeg_file_sizes(const char* const* paths, int n, int n_threads, int64_t* sizes) {
+  if (n < 0 || (n > 0 && (!paths || !sizes))) {
+    set_last_error("vge_jpeg_file_sizes: bad argument");
+    return VGE_JPEG_ERR_ARG;
+  }
+  parallel_for(n, n_threads, [&](int i) {
+    struct stat st;
+    sizes[i] = (paths[i] && ::stat(paths[i], &st) == 0 && S_ISREG(st.st_mode)) ? (int64_t)st.st_size : 0;
+  });
+  return VGE_JPEG_OK;
+}
+
+int vge_jpeg_read_files(const char* const* paths, int n, int n_threads, const int64_t* offsets, const int64_t* sizes,
+                        uint8_t* data, int64_t data_bytes, int32_t* status) {
+  if (n < 0 || data_bytes < 0 || (n > 0 && (!paths || !offsets || !sizes || !data))) {
+    set_last_error("vge_jpeg_read_files: bad argument");
+    return VGE_JPEG_ERR_ARG;
+  }
+  std::vector<int32_t> st((size_t)n, VGE_JPEG_OK);
+  parallel_for(n, n_threads, [&](int i) {
+    if (!paths[i] || !range_ok(offsets[i], sizes[i], data_bytes)) {
+      st[(size_t)i] = VGE_JPEG_ERR_ARG;
+      return;
+    }
+    uint8_t* dst = data + offsets[i];
+    const size_t want = (size_t)sizes[i];
+    size_t done = 0;
+    const int fd = want ? ::open(paths[i], O_RDONLY | O_CLOEXEC) : -1;
+    if (fd >= 0) {
+      while (done < want) {
+        const ssize_t k = ::read(fd, dst + done, want - done);
+        if (k <= 0) break;
+        done += (size_t)k;
+      }
+      ::close(fd);
+    }
+    if (done != want) {  // shorter than it was, or unreadable: no JPEG is left in its place
+      memset(dst, 0, want);
+      st[(size_t)i] = VGE_JPEG_ERR_IO;
+    }
+  });
+  if (status) memcpy(status, st.data(), (size_t)n * sizeof(int32_t));
+  return first_failure(st.data(), n, paths, "vge_jpeg_read_files");
+}
+
+int vge_jpeg_probe_mem(const uint8_t* data, int64_t data_bytes, const int64_t* offsets, const int64_t* sizes, int n,
+                       int n_threads, vge_jpeg_info* info) {
+  if (n < 0 || data_bytes < 0 || (n > 0 && (!data || !offsets || !sizes || !info))) {
+    set_last_error("vge_jpeg_probe_mem: bad argument");
+    return VGE_JPEG_ERR_ARG;
+  }
+  std::vector<int32_t> st((size_t)n, VGE_JPEG_OK);
+  parallel_for(n, n_threads, [&](int i) {
+    vge_jpeg_info& I = info[i];
+    I.width = I.height = I.n_comp = I.h0 = I.v0 = 0;
+    I.status = st[(size_t)i] = range_ok(offsets[i], sizes[i], data_bytes)
+                                   ? probe_mem(data + offsets[i], (size_t)sizes[i], I)
+                                   : VGE_JPEG_ERR_ARG;
+  });
+  return first_failure_mem(st.data(), n, "vge_jpeg_probe_mem");
+}
+
+int vge_jpeg_entropy_decode_mem(const uint8_t* data, int64_t data_bytes, const int64_t* offsets, const int64_t* sizes,
+                                int n, int n_threads, const vge_jpeg_layout* layout, int16_t* coef, uint16_t* qtab,
+                                int32_t* status) {
+  if (n < 0 || data_bytes < 0 || !layout_ok(layout) || (n > 0 && (!data || !offsets || !sizes || !coef || !qtab))) {
+    set_last_error("vge_jpeg_entropy_decode_mem: bad argument");
+    return VGE_JPEG_ERR_ARG;
+  }
+  const vge_jpeg_layout L = *layout;
+  const size_t per = (size_t)L.blocks_per_frame * 64;
+  std::vector<int32_t> st((size_t)n, VGE_JPEG_OK);
+  parallel_for(n, n_threads, [&](int i) {
+    int16_t* c = coef + per * (size_t)i;
+    uint16_t* q = qtab + 192 * (size_t)i;
+    memset(c, 0, per * sizeof(int16_t));
+    for (int k = 0; k < 192; ++k) q[k] = 1;
+    const int s = range_ok(offsets[i], sizes[i], data_bytes)
+                      ? decode_frame_mem(data + offsets[i], (size_t)sizes[i], L, c, q)
+                      : VGE_JPEG_ERR_ARG;  // a file outside the buffer: nothing of it is read
+    if (s != VGE_JPEG_OK) {
+      memset(c, 0, per * sizeof(int16_t));
+      for (int k = 0; k < 192; ++k) q[k] = 1;
+    }
+    st[(size_t)i] = s;
+  });
+  if (status) memcpy(status, st.data(), (size_t)n * sizeof(int32_t));
+  return first_failure_mem(st.data(), n, "vge_jpeg_entropy_decode_mem");
 }
 
 int vge_jpeg_make_layout(int width, int height, int n_comp, int h0, int v0, vge_jpeg_layout* L) {

@@ -312,7 +312,8 @@ def _save_json(path: Path, data) -> None:
 
 
 def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root, log_root, actions=None,
-                       max_frames: int = 1024, device=None, threads: int = 0, crop=None) -> Dict[str, Dict[str, list]]:
+                       max_frames: int = 1024, device=None, threads: int = 0, crop=None,
+                       entropy: str = "host") -> Dict[str, Dict[str, list]]:
     """extract_mesh.py:150-241 and process_video.py:59-94 together, over the frame folders the reference leaves on
     disk: <frames_root>/<action>/<video>/*.jpg, decoded by vge.frames (the pixels cv2.imread gives the reference).
 
@@ -328,6 +329,7 @@ def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root
     Outputs: <mesh_root>/<action>/<video>.npz (kept frames only; frame_idx indexes the folder's sorted *.jpg list, so
     a frame that failed to decode shows as a gap; meta carries action / video / source_path) and
     <kp_root>/<action>/<video>/keypoints.npy.  actions: None (every folder of frames_root), a name or a list of names.
+    entropy: where the frames' Huffman decoding runs, "host" or "device" (vge.frames.load_frames).
     Returns {action: {"single": [...], "not_single": [...], "errors": [...], "skipped": [...]}} for this run."""
     from . import frames as FR
     frames_root, log_root = Path(frames_root), Path(log_root)
@@ -384,12 +386,13 @@ def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root
         for group in _pack_passes([(v, paths, len(paths)) for v, paths in todo], max_frames):
             # decode and validate: one call for the pass; a video that makes it raise is found one by one
             try:
-                decoded = FR.load_videos([paths for _, paths, _ in group], device=device, threads=threads)
+                decoded = FR.load_videos([paths for _, paths, _ in group], device=device, threads=threads,
+                                         entropy=entropy)
             except Exception:
                 decoded = []
                 for _, paths, _ in group:
                     try:
-                        decoded.append(FR.load_frames(paths, device=device, threads=threads))
+                        decoded.append(FR.load_frames(paths, device=device, threads=threads, entropy=entropy))
                     except Exception as e:
                         decoded.append(e)
             good = []
@@ -465,6 +468,8 @@ def main(argv=None) -> int:
     ap.add_argument("--max-frames", type=int, default=1024, help="frames per GPU pass")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--threads", type=int, default=0, help="JPEG entropy-decode threads (0: the ingest default)")
+    ap.add_argument("--entropy", choices=("host", "device"), default="host",
+                    help="where the frames' Huffman decoding runs (vge.frames.load_frames)")
     args = ap.parse_args(argv)
     from . import synth
     from .dwpose import RTMPOSE_L, YOLOX_L, DwposeExtractor, Wholebody, YoloxDetector
@@ -488,7 +493,8 @@ def main(argv=None) -> int:
                    DwposeExtractor(weights(args.rtmpose_ckpt, lambda: synth.make_rtmpose_state_dict(RTMPOSE_L), "rtmpose"),
                                    RTMPOSE_L, device=dev, max_instances=2 * fc))
     summary = extract_frame_tree(hmr, wb, gdet, args.frames_root, args.mesh_root, args.kp_root, args.log_root,
-                                 actions=args.action, max_frames=fc, device=dev, threads=args.threads)
+                                 actions=args.action, max_frames=fc, device=dev, threads=args.threads,
+                                 entropy=args.entropy)
     for action, d in summary.items():
         print(f"[DONE] {action}: {len(d['single'])} single, {len(d['not_single'])} not single, "
               f"{len(d['errors'])} errors, {len(d['skipped'])} skipped")

@@ -12,7 +12,9 @@ would give without leaving the device (vge_jpeg_forward, then vge_jpeg_reconstru
 reference's frame_%06d.jpg cache byte for byte as libjpeg does (vge_jpeg_forward + vge_jpeg_entropy_encode).
 encode_frames gives the same files in memory; on a GPU tensor it also Huffman-codes on the device
 (vge_jpeg_entropy_plan / vge_jpeg_entropy_emit, csrc/vge_jpeg_huff.hip), and save_frames(entropy="device") writes
-its bytes.
+its bytes.  decode_frames is the inverse of encode_frames: files held in memory, on either side, back to frames; for
+files on a GPU, and for load_frames(entropy="device"), Huffman decoding runs on the device too
+(vge_jpeg_entropy_decode_device, csrc/vge_jpeg_dehuff.hip) and what is uploaded is the file bytes.
 """
 from __future__ import annotations
 
@@ -52,8 +54,7 @@ def probe(paths: Sequence[PathLike], threads: int = 0) -> np.ndarray:
     info = (L.JpegInfo * max(len(paths), 1))()
     if paths:
         L.load().vge_jpeg_probe(_paths_array(paths), len(paths), int(threads), info)
-    return np.array([[i.width, i.height, i.n_comp, i.h0, i.v0, i.status] for i in info[:len(paths)]],
-                    dtype=np.int32).reshape(-1, 6)
+    return _info_rows(info, len(paths))
 
 
 def make_layout(width: int, height: int, n_comp: int, h0: int, v0: int) -> L.JpegLayout:
@@ -93,6 +94,186 @@ def _decode_group(paths: List[str], lay: L.JpegLayout, device, threads: int):
         L.check(lib.vge_jpeg_reconstruct_host(coef.data_ptr(), qtab.data_ptr(), C.byref(lay), n, int(threads),
                                               out.data_ptr()), "vge_jpeg_reconstruct_host")
     return out, status
+
+
+def _info_rows(info, n: int) -> np.ndarray:
+    return np.array([[i.width, i.height, i.n_comp, i.h0, i.v0, i.status] for i in info[:n]],
+                    dtype=np.int32).reshape(-1, 6)
+
+
+def probe_mem(data: np.ndarray, offsets: np.ndarray, sizes: np.ndarray, threads: int = 0) -> np.ndarray:
+    """probe() for files in host memory: file i is data[offsets[i]:offsets[i] + sizes[i]] (vge_jpeg_probe_mem)."""
+    n = len(offsets)
+    info = (L.JpegInfo * max(n, 1))()
+    if n:
+        L.load().vge_jpeg_probe_mem(data.ctypes.data, data.size, offsets.ctypes.data, sizes.ctypes.data, n,
+                                    int(threads), info)
+    return _info_rows(info, n)
+
+
+def _read_files(paths: Sequence[str], threads: int, pin: bool):
+    """The raw bytes of the files, back to back in one (pinned) uint8 tensor, read on host threads
+    (vge_jpeg_file_sizes / vge_jpeg_read_files) -> (tensor, offsets int64 [n], sizes int64 [n]).  An unreadable file
+    has size 0 and one that can no longer be read zero bytes, which decode to ERR_IO as an unreadable path does."""
+    import torch
+    lib = L.load()
+    n = len(paths)
+    arr = _paths_array(paths)
+    sizes, offsets = np.zeros(n, np.int64), np.zeros(n, np.int64)
+    L.check(lib.vge_jpeg_file_sizes(arr, n, int(threads), sizes.ctypes.data), "vge_jpeg_file_sizes")
+    np.cumsum(sizes[:-1], out=offsets[1:])
+    buf = torch.empty(int(sizes.sum()), dtype=torch.uint8, pin_memory=pin)
+    lib.vge_jpeg_read_files(arr, n, int(threads), offsets.ctypes.data, sizes.ctypes.data, buf.data_ptr(),
+                            int(buf.numel()), None)   # a file that fails shows in the decoder's status
+    return buf, offsets, sizes
+
+
+def _decode_group_device(data_d, offsets: np.ndarray, sizes: np.ndarray, lay: L.JpegLayout, rounds=None):
+    """One layout's files, bytes already on the GPU (data_d: uint8 tensor) -> (uint8 [n, H, W, 3] tensor on that GPU,
+    int32 status [n]): vge_jpeg_entropy_decode_device feeds vge_jpeg_reconstruct on the current stream; the one host
+    synchronisation is the copy of the statuses at the end.  rounds: an int32 [n] tensor on the device to fill."""
+    import torch
+    lib = L.load()
+    dev = data_d.device
+    n = len(offsets)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        table = torch.from_numpy(np.stack([np.ascontiguousarray(offsets, np.int64),
+                                           np.ascontiguousarray(sizes, np.int64)])).to(dev)
+        nbytes = int(data_d.numel())
+        ws = torch.empty(int(lib.vge_jpeg_entropy_decode_workspace_bytes(C.byref(lay), n, nbytes)),
+                         dtype=torch.uint8, device=dev)
+        coef = torch.empty((n, lay.blocks_per_frame, 64), dtype=torch.int16, device=dev)
+        qtab = torch.empty((n, 3, 64), dtype=torch.int16, device=dev)
+        status_d = torch.empty(n, dtype=torch.int32, device=dev)
+        out = torch.empty((n, lay.height, lay.width, 3), dtype=torch.uint8, device=dev)
+        L.check(lib.vge_jpeg_entropy_decode_device(data_d.data_ptr(), nbytes, table[0].data_ptr(), table[1].data_ptr(),
+                                                   n, C.byref(lay), ws.data_ptr(), coef.data_ptr(), qtab.data_ptr(),
+                                                   status_d.data_ptr(),
+                                                   rounds.data_ptr() if rounds is not None else None,
+                                                   stream.cuda_stream), "vge_jpeg_entropy_decode_device")
+        L.check(lib.vge_jpeg_reconstruct(coef.data_ptr(), qtab.data_ptr(), C.byref(lay), n, out.data_ptr(),
+                                         stream.cuda_stream), "vge_jpeg_reconstruct")
+        status = status_d.cpu().numpy()
+    return out, status
+
+
+def _decode_group_mem(data, offsets: np.ndarray, sizes: np.ndarray, lay: L.JpegLayout, device, threads: int):
+    """_decode_group for files in host memory (data: a uint8 CPU tensor): vge_jpeg_entropy_decode_mem, then the
+    reconstruct on `device`."""
+    import torch
+    n = len(offsets)
+    lib = L.load()
+    on_gpu = device.type == "cuda"
+    coef = torch.empty((n, lay.blocks_per_frame, 64), dtype=torch.int16, pin_memory=on_gpu)
+    qtab = torch.empty((n, 3, 64), dtype=torch.int16, pin_memory=on_gpu)  # uint16 bits
+    status = np.zeros(n, np.int32)
+    offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
+    lib.vge_jpeg_entropy_decode_mem(data.data_ptr(), int(data.numel()), offsets.ctypes.data, sizes.ctypes.data, n,
+                                    int(threads), C.byref(lay), coef.data_ptr(), qtab.data_ptr(), status.ctypes.data)
+    out = torch.empty((n, lay.height, lay.width, 3), dtype=torch.uint8, device=device)
+    if on_gpu:
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device)
+            coef_d = coef.to(device, non_blocking=True)
+            qtab_d = qtab.to(device, non_blocking=True)
+            L.check(lib.vge_jpeg_reconstruct(coef_d.data_ptr(), qtab_d.data_ptr(), C.byref(lay), n, out.data_ptr(),
+                                             stream.cuda_stream), "vge_jpeg_reconstruct")
+    else:
+        L.check(lib.vge_jpeg_reconstruct_host(coef.data_ptr(), qtab.data_ptr(), C.byref(lay), n, int(threads),
+                                              out.data_ptr()), "vge_jpeg_reconstruct_host")
+    return out, status
+
+
+def _raise_unsupported(names, statuses) -> None:
+    for p, s in zip(names, statuses):
+        if int(s) in L.JPEG_UNSUPPORTED:
+            raise UnsupportedJpegError(f"{p}: unsupported JPEG: {L.JPEG_UNSUPPORTED[int(s)]} "
+                                       f"({L.JPEG_STATUS[int(s)]})")
+
+
+_PROBE_HEAD = 1 << 16   # bytes of a device-resident file copied to the host for its header
+
+
+def _probe_on_device(data, off: int, size: int) -> np.ndarray:
+    """The probe row of one device-resident file from its first kilobytes (the whole file only when the header is
+    longer than that)."""
+    for take in (min(size, _PROBE_HEAD), size):
+        head = data[off:off + take].cpu().numpy()
+        row = probe_mem(head, np.zeros(1, np.int64), np.array([take], np.int64), 1)[0]
+        if int(row[5]) != 7 or take == size:
+            break
+    return row
+
+
+def decode_frames(data, offsets, device=None, threads: int = 0, entropy: Optional[str] = None):
+    """The inverse of encode_frames: (data, offsets[F + 1]) -- complete JPEG files in one uint8 tensor, file i at
+    data[offsets[i]:offsets[i + 1]] -- -> (frames, kept) as load_frames gives them.
+    data on a GPU: the layout comes from the header of the first readable file (its first kilobytes are copied to the
+    host for vge_jpeg_probe_mem), then vge_jpeg_entropy_decode_device and vge_jpeg_reconstruct run on the current
+    stream and one copy of the statuses gives `kept`: no file byte and no coefficient crosses to the host.  The frames
+    are on data's device.
+    data on the CPU: entropy "host" (the default) decodes on host threads (vge_jpeg_entropy_decode_mem) and
+    reconstructs on `device` (default: the current GPU when there is one, else the CPU); entropy "device" uploads the
+    file bytes instead and decodes them there.
+    Raises UnsupportedJpegError for a file of an unsupported kind; a file that does not decode is dropped with a log
+    message."""
+    import torch
+    if not (isinstance(data, torch.Tensor) and data.dtype == torch.uint8 and data.dim() == 1):
+        raise ValueError("data must be a one-dimensional uint8 tensor")
+    off = np.ascontiguousarray(offsets.cpu().numpy() if isinstance(offsets, torch.Tensor) else offsets, np.int64)
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError("offsets must be int64 [F + 1]")
+    data_on_gpu = data.device.type == "cuda"
+    if entropy is None:
+        entropy = "device" if data_on_gpu else "host"
+    if entropy not in ("host", "device"):
+        raise ValueError(f"entropy must be 'host' or 'device', not {entropy!r}")
+    if entropy == "host" and data_on_gpu:
+        raise ValueError("entropy='host' needs data on the CPU")
+    device = data.device if data_on_gpu else _resolve_device(device)
+    if entropy == "device" and device.type != "cuda":
+        raise ValueError("entropy='device' needs a GPU")
+    data = data.contiguous()
+    F = off.size - 1
+    starts, sizes = off[:F].copy(), np.diff(off)
+    names = [f"file {i}" for i in range(F)]
+    empty = (torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=device), np.zeros(0, np.int64))
+    if F == 0:
+        return empty
+    if (sizes < 0).any() or off[0] < 0 or off[F] > data.numel():
+        raise ValueError("offsets must be non-decreasing and inside data")
+    key = None
+    if data_on_gpu:
+        for i in range(F):   # the first readable file decides the layout, as in load_videos
+            row = _probe_on_device(data, int(starts[i]), int(sizes[i]))
+            _raise_unsupported(names[i:i + 1], row[5:6])
+            if int(row[5]) == 0:
+                key = tuple(int(x) for x in row[:5])
+                break
+    else:
+        info = probe_mem(data.numpy(), starts, sizes, threads)
+        _raise_unsupported(names, info[:, 5])
+        good = np.flatnonzero(info[:, 5] == 0)
+        key = tuple(int(x) for x in info[good[0], :5]) if good.size else None
+    if key is None:
+        for p in names:
+            log.warning("dropping frame %s: unreadable", p)
+        return empty
+    lay = make_layout(*key)
+    if entropy == "device":
+        data_d = data if data_on_gpu else data.to(device)
+        out, status = _decode_group_device(data_d, starts, sizes, lay)
+        _raise_unsupported(names, status)
+    else:
+        out, status = _decode_group_mem(data, starts, sizes, lay, device, threads)
+    for p, s in zip(names, status):
+        if s != 0:
+            log.warning("dropping frame %s: %s", p, L.JPEG_STATUS.get(int(s), int(s)))
+    kept = np.flatnonzero(status == 0)
+    if kept.size != F:
+        out = out[torch.as_tensor(kept, device=device)]
+    return out, kept
 
 
 SUBSAMPLING = {"420": (2, 2), "422": (2, 1), "444": (1, 1)}   # luma sampling factors (h0, v0)
@@ -286,19 +467,31 @@ def save_frames(frames, folder: PathLike, quality: int = 95, subsampling: str = 
     return paths
 
 
-def load_videos(videos: Sequence[Union[PathLike, Sequence[PathLike]]], device=None, threads: int = 0):
+def load_videos(videos: Sequence[Union[PathLike, Sequence[PathLike]]], device=None, threads: int = 0,
+                entropy: str = "host"):
     """Several videos in one go: each entry is a frame folder or a list of JPEG paths.  Videos of one frame size and
     sampling share one entropy-decode call, one upload and one kernel launch.  Returns a list of (frames, kept) as
-    load_frames does."""
+    load_frames does.  entropy "host": Huffman decoding on host threads, the coefficients are uploaded.  entropy
+    "device" (needs a GPU): host threads only read the raw files into one pinned buffer, the file bytes are uploaded
+    once -- a quarter of the coefficients' bytes -- and vge_jpeg_entropy_decode_device decodes them; frames, kept,
+    dropped frames and errors are the same."""
     import torch
     device = _resolve_device(device)
+    if entropy not in ("host", "device"):
+        raise ValueError(f"entropy must be 'host' or 'device', not {entropy!r}")
+    if entropy == "device" and device.type != "cuda":
+        raise ValueError("entropy='device' needs a GPU")
     vids = [list_frames(v) if isinstance(v, (str, os.PathLike)) else [os.fspath(p) for p in v] for v in videos]
     flat = [p for v in vids for p in v]
-    info = probe(flat, threads)
-    for p, row in zip(flat, info):
-        if int(row[5]) in L.JPEG_UNSUPPORTED:
-            raise UnsupportedJpegError(f"{p}: unsupported JPEG: {L.JPEG_UNSUPPORTED[int(row[5])]} "
-                                       f"({L.JPEG_STATUS[int(row[5])]})")
+    if entropy == "device":
+        raw, raw_off, raw_size = _read_files(flat, threads, pin=True)
+        info = probe_mem(raw.numpy(), raw_off, raw_size, threads)
+        with torch.cuda.device(device):
+            raw_d = raw.to(device, non_blocking=True)   # the one upload: every group decodes out of this buffer
+        first_of = np.concatenate([[0], np.cumsum([len(v) for v in vids])]).astype(np.int64)
+    else:
+        info = probe(flat, threads)
+    _raise_unsupported(flat, info[:, 5])
     # a video's layout is its first readable frame's; frames of another size get the shape status and are dropped
     groups, keys, f0 = {}, [], 0
     for vi, v in enumerate(vids):
@@ -313,7 +506,12 @@ def load_videos(videos: Sequence[Union[PathLike, Sequence[PathLike]]], device=No
     for key, members in groups.items():
         lay = make_layout(*key)
         paths = [p for vi in members for p in vids[vi]]
-        out, status = _decode_group(paths, lay, device, threads)
+        if entropy == "device":
+            idx = np.concatenate([np.arange(first_of[vi], first_of[vi + 1]) for vi in members])
+            with torch.cuda.device(device):
+                out, status = _decode_group_device(raw_d, raw_off[idx], raw_size[idx], lay)
+        else:
+            out, status = _decode_group(paths, lay, device, threads)
         o = 0
         for vi in members:
             n = len(vids[vi])
@@ -335,10 +533,12 @@ def load_videos(videos: Sequence[Union[PathLike, Sequence[PathLike]]], device=No
     return results
 
 
-def load_frames(paths_or_dir: Union[PathLike, Sequence[PathLike]], device=None, threads: int = 0):
+def load_frames(paths_or_dir: Union[PathLike, Sequence[PathLike]], device=None, threads: int = 0,
+                entropy: str = "host"):
     """load_frames_from_images (extract_mesh.py:72-82) on the GPU.  paths_or_dir: a frame folder (its *.jpg files in
     sorted order) or a list of JPEG paths.  Returns (frames, kept): uint8 [F', H, W, 3] RGB on `device` (default: the
     current GPU when there is one, else the CPU) and the indices of the frames that decoded.  A frame that fails to
     decode is dropped with a log message, as the reference drops a None from cv2.imread; an unsupported kind of JPEG
-    raises UnsupportedJpegError naming the kind and the file."""
-    return load_videos([paths_or_dir], device=device, threads=threads)[0]
+    raises UnsupportedJpegError naming the kind and the file.  entropy: where Huffman decoding runs, "host" or "device"
+    (load_videos)."""
+    return load_videos([paths_or_dir], device=device, threads=threads, entropy=entropy)[0]

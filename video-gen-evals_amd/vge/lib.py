@@ -43,6 +43,10 @@ EXPORTS = ["vge_featurize", "vge_featurize_layout", "vge_layout_feat_dim", "vge_
            "vge_jpeg_quant_tables", "vge_jpeg_forward", "vge_jpeg_forward_host", "vge_jpeg_entropy_encode",
            "vge_jpeg_entropy_encode_mem", "vge_jpeg_write_files", "vge_jpeg_entropy_workspace_bytes",
            "vge_jpeg_entropy_plan", "vge_jpeg_entropy_emit", "vge_jpeg_entropy_segment_blocks",
+           "vge_jpeg_file_sizes", "vge_jpeg_read_files",
+           "vge_jpeg_probe_mem", "vge_jpeg_entropy_decode_mem", "vge_jpeg_entropy_decode_workspace_bytes",
+           "vge_jpeg_entropy_decode_device", "vge_jpeg_entropy_decode_subsequence_bytes",
+           "vge_jpeg_entropy_decode_tile_bytes",
            "vge_time_gather", "vge_tcl_workspace_bytes", "vge_tcl_loss", "vge_hardneg_loss", "vge_centroid_distance"]
 
 
@@ -155,6 +159,14 @@ def load() -> C.CDLL:
         "vge_jpeg_entropy_plan": [vp, C.POINTER(JpegLayout), i32, vp, vp, vp, vp],
         "vge_jpeg_entropy_emit": [vp, vp, C.POINTER(JpegLayout), i32, vp, vp, C.c_int64, vp],
         "vge_jpeg_entropy_segment_blocks": [],
+        "vge_jpeg_file_sizes": [C.POINTER(C.c_char_p), i32, i32, vp],
+        "vge_jpeg_read_files": [C.POINTER(C.c_char_p), i32, i32, vp, vp, vp, C.c_int64, vp],
+        "vge_jpeg_probe_mem": [vp, C.c_int64, vp, vp, i32, i32, C.POINTER(JpegInfo)],
+        "vge_jpeg_entropy_decode_mem": [vp, C.c_int64, vp, vp, i32, i32, C.POINTER(JpegLayout), vp, vp, vp],
+        "vge_jpeg_entropy_decode_workspace_bytes": [C.POINTER(JpegLayout), i32, C.c_int64],
+        "vge_jpeg_entropy_decode_device": [vp, C.c_int64, vp, vp, i32, C.POINTER(JpegLayout), vp, vp, vp, vp, vp, vp],
+        "vge_jpeg_entropy_decode_subsequence_bytes": [],
+        "vge_jpeg_entropy_decode_tile_bytes": [],
         "vge_time_gather": [vp, vp, i32, i32, i32, vp, vp],
         "vge_tcl_workspace_bytes": [i32],
         "vge_tcl_loss": [vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, vp, C.c_size_t, vp, vp],
@@ -168,6 +180,7 @@ def load() -> C.CDLL:
     lib.vge_stats_workspace_bytes.restype = C.c_size_t
     lib.vge_tcl_workspace_bytes.restype = C.c_size_t
     lib.vge_jpeg_entropy_workspace_bytes.restype = C.c_size_t
+    lib.vge_jpeg_entropy_decode_workspace_bytes.restype = C.c_size_t
     lib.vge_last_error.restype = C.c_char_p
     lib.vge_version.restype = C.c_char_p
     _lib = lib
