@@ -29,6 +29,19 @@
 extern "C" {
 #endif
 
+/* The TokenHMR values, and what vge_hmr_create accepts (anything else: VGE_ERR_ARG before any GPU work):
+ *   crop        img_h == in_h, 0 < img_w <= in_w with an even margin in_w - img_w (the margin may be 0)
+ *   patch grid  patch 16 and (img_h + 2 pad - 16) / 16 + 1 == 16, (img_w + 2 pad - 16) / 16 + 1 == 12: exactly 192
+ *               tokens.  pad 2: img_h 252..267, img_w 188..203; pad 0: 256..271, 192..207; rows and columns the grid
+ *               does not reach are dropped, as Conv2d drops them
+ *   backbone    embed_dim 256, 512, 768, 1024 or 1280 with head dim embed_dim / heads 64 or 80 (4, 8, 12, 16 or 20
+ *               heads of 64; 16 of 80); mlp_dim % 256 == 0; depth >= 0 (0: patch embed + last_norm only)
+ *   decoder     dec_dim 256..1280 in steps of 256, independent of embed_dim; dec_dim_head 64; dec_heads a positive
+ *               multiple of 4 (dec_heads * 64 need not equal dec_dim); dec_mlp % 256 == 0; dec_depth >= 0 (0: the
+ *               readouts see the input token alone)
+ *   classifier  tok_num > 0, tok_classes % 256 == 0, tok_code_dim % 256 == 0
+ * Frame counts are free: token rows pad to a multiple of 256, head rows to a multiple of 256 frames.  The configs
+ * pinned by tests are listed in DESIGN.md section 7. */
 typedef struct {
   int in_h, in_w;           /* input crop: 256 x 256 (ViTDetDataset output size) */
   int img_h, img_w;         /* backbone input: all rows, columns (in_w - img_w)/2 .. : 256 x 192 */
@@ -91,6 +104,33 @@ int vge_op_vit_attention(const void* qkv, void* out, int F, int D, int heads, vg
 /* LayerNorm f32 [rows][D] -> bf16, D in {256, 512, 768, 1024, 1280} */
 int vge_op_layernorm_bf16(const float* x, void* y, const float* w, const float* b, int rows, int D, float eps,
                           vge_stream_t stream);
+
+/* The kernels around the GEMMs, one entry each (tests/test_hmr_ops.py).  Each checks its arguments first
+ * (VGE_ERR_ARG, vge_last_error names the entry and the rule, no GPU work), then calls the launcher the model calls.
+ *
+ * Patch-embed input rows: frames uint8 [F][in_h][in_w][3] -> out bf16 [F * 192][768], row f * 192 + py * 12 + px,
+ * column c * 256 + ky * 16 + kx = (frame[f][py 16 - pad + ky][x0 + px 16 - pad + kx][c] - mean[c]) / std[c] with
+ * x0 = (in_w - img_w) / 2, zero outside the img_h x img_w crop.  The geometry rule is vge_hmr_create's. */
+int vge_op_patchify(const uint8_t* frames, int F, int in_h, int in_w, int img_h, int img_w, int patch, int pad,
+                    void* out, vge_stream_t stream);
+/* The decoder's one-query cross-attention, dim_head 64, scale 1/8: q bf16 [F][ldq] (64 heads columns), kv bf16
+ * [F * ctx][ldkv] (k in columns [0, 64 heads), v in [64 heads, 128 heads)) -> out bf16 [F][ldo].  ctx in [1, 256];
+ * ldq, ldo >= 64 heads, ldkv >= 128 heads, all multiples of 8. */
+int vge_op_xattn1(const void* q, long ldq, const void* kv, long ldkv, void* out, long ldo, int F, int heads, int ctx,
+                  vge_stream_t stream);
+/* softmax over each row: x f32 [rows][C] -> y bf16 [rows][C] (the token classifier's probabilities) */
+int vge_op_softmax_rows_bf16(const float* x, void* y, int rows, int C, vge_stream_t stream);
+/* Readout: rd f32 [F][ldrd] (grot 0..5 | hands 6..17 | shape 18..27 | cam 28..30, ldrd >= 31), bp f32 [F][ldbp]
+ * (21 body joints of 6, ldbp >= 126), init_pose [144], init_betas [10] -> rot6d_to_rotmat of joint 0 = grot, 1..21 =
+ * bp, 22..23 = hands, each plus its init_pose: gori [F][9], pose [F][207]; betas [F][10] = shape + init_betas. */
+int vge_op_hmr_readout(const float* rd, int ldrd, const float* bp, int ldbp, const float* init_pose,
+                       const float* init_betas, float* pose, float* gori, float* betas, int F, vge_stream_t stream);
+/* x f32 [rows][ldx] -> y bf16 [rows][ldy], D columns, round to nearest even; D, ldx, ldy multiples of 4, ld >= D */
+int vge_op_cast_rows_bf16(const float* x, long ldx, void* y, long ldy, int rows, int D, vge_stream_t stream);
+/* y f32 [rows][D] (contiguous) = vec [D] in every row */
+int vge_op_bcast_rows(const float* vec, float* y, int rows, int D, vge_stream_t stream);
+/* y f32 [rows][ldy] = x f32 [rows][ldx] in D columns; ldx, ldy >= D */
+int vge_op_copy_rows(const float* x, long ldx, float* y, long ldy, int rows, int D, vge_stream_t stream);
 
 #ifdef __cplusplus
 }

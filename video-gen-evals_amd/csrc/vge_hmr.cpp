@@ -98,21 +98,32 @@ int gemm(int epi, const void* A, long lda, const Lin& L, void* out, long ldo, in
   return VGE_OK;
 }
 
-bool cfg_ok(const vge_hmr_config& c, std::string& why) {
-  if (c.in_h <= 0 || c.in_w <= 0 || c.img_h != c.in_h || c.img_w <= 0 || c.img_w > c.in_w || (c.in_w - c.img_w) % 2)
+// ImageNet mean / std times 255 (hmr2 DEFAULT_MEAN / DEFAULT_STD): patchify normalises the uint8 crop with them
+const float IMG_MEAN[3] = {123.675f, 116.28f, 103.53f}, IMG_STD[3] = {58.395f, 57.12f, 57.375f};
+
+// The crop / patch-grid rule of the extractor and of vge_op_patchify: every row of the crop, img_w columns centred in
+// in_w, and a 16-pixel patch whose grid over the zero-padded crop is 16 x 12 (rows and columns the grid does not
+// reach are dropped, as Conv2d does).
+bool geom_ok(int in_h, int in_w, int img_h, int img_w, int patch, int pad, std::string& why) {
+  if (in_h <= 0 || in_w <= 0 || img_h != in_h || img_w <= 0 || img_w > in_w || (in_w - img_w) % 2)
     return why = "crop geometry (img_h must equal in_h, img_w <= in_w, even margin)", false;
-  if (c.patch != 16 || (c.img_h + 2 * c.pad - c.patch) / c.patch + 1 != 16 ||
-      (c.img_w + 2 * c.pad - c.patch) / c.patch + 1 != 12)
+  if (patch != 16 || (img_h + 2 * pad - patch) / patch + 1 != 16 || (img_w + 2 * pad - patch) / patch + 1 != 12)
     return why = "patch grid must be 16 x 12 (192 tokens) with a 16-pixel patch", false;
-  if (c.embed_dim % 256 || c.embed_dim > 1280 || c.heads <= 0 || c.embed_dim % c.heads ||
+  return true;
+}
+
+bool cfg_ok(const vge_hmr_config& c, std::string& why) {
+  if (!geom_ok(c.in_h, c.in_w, c.img_h, c.img_w, c.patch, c.pad, why)) return false;
+  if (c.embed_dim <= 0 || c.embed_dim % 256 || c.embed_dim > 1280 || c.heads <= 0 || c.embed_dim % c.heads ||
       (c.embed_dim / c.heads != 64 && c.embed_dim / c.heads != 80))
     return why = "embed_dim must be a multiple of 256 (<= 1280) with head dim 64 or 80", false;
-  if (c.mlp_dim % 256 || c.depth < 0) return why = "mlp_dim must be a multiple of 256", false;
-  if (c.dec_dim % 256 || c.dec_dim > 1280 || c.dec_dim_head != 64 || c.dec_heads <= 0 ||
-      (c.dec_heads * 64) % 256 || c.dec_mlp % 256 || c.dec_depth < 0)
-    return why = "decoder: dim % 256, dim_head 64, heads * 64 % 256, mlp % 256", false;
-  if (c.tok_num <= 0 || c.tok_classes % 256 || c.tok_code_dim % 256 || (c.tok_num * c.tok_code_dim) % 64)
-    return why = "token classifier: classes and code dim multiples of 256", false;
+  if (c.mlp_dim <= 0 || c.mlp_dim % 256 || c.depth < 0)
+    return why = "mlp_dim must be a positive multiple of 256, depth >= 0", false;
+  if (c.dec_dim <= 0 || c.dec_dim % 256 || c.dec_dim > 1280 || c.dec_dim_head != 64 || c.dec_heads <= 0 ||
+      (c.dec_heads * 64) % 256 || c.dec_mlp <= 0 || c.dec_mlp % 256 || c.dec_depth < 0)
+    return why = "decoder: dim a positive multiple of 256 (<= 1280), dim_head 64, heads * 64 % 256, mlp % 256", false;
+  if (c.tok_num <= 0 || c.tok_classes <= 0 || c.tok_classes % 256 || c.tok_code_dim <= 0 || c.tok_code_dim % 256)
+    return why = "token classifier: tok_num positive, classes and code dim positive multiples of 256", false;
   return true;
 }
 
@@ -362,9 +373,8 @@ int vge_hmr_extract(vge_hmr* m, const uint8_t* frames, int F, float* pose, float
   const int E = c.embed_dim, K0 = 3 * c.patch * c.patch;
   m->prof.start_call();
 #define STAGE(kind, expr) VGE_STAGE(m->prof, s, kind, expr)
-  static const float mean[3] = {123.675f, 116.28f, 103.53f}, stdv[3] = {58.395f, 57.12f, 57.375f};
   STAGE(2, VGE_HIP(vge::launch_patchify(frames, F, c.in_h, c.in_w, (c.in_w - c.img_w) / 2, c.img_h, c.img_w, c.patch,
-                                        c.pad, 16, 12, mean, stdv, m->ape, s)));
+                                        c.pad, 16, 12, IMG_MEAN, IMG_STD, m->ape, s)));
   STAGE(0, gemm(vge::GEMM_PE_F32, m->ape, K0, m->pe, m->x, E, Mv, s, nullptr, 0, m->pos.p, NTOK));
   for (int i = 0; i < c.depth; ++i) {
     const VitBlock& B = m->blocks[i];
@@ -425,6 +435,82 @@ int vge_op_layernorm_bf16(const float* x, void* y, const float* w, const float* 
   if (!x || !y || !w || !b || rows <= 0 || (D != 256 && D != 512 && D != 768 && D != 1024 && D != 1280))
     return fail(VGE_ERR_ARG, "vge_op_layernorm_bf16: unsupported width");
   HIPCHK(vge::launch_ln_bf16(x, D, y, D, w, b, rows, D, eps, S(stream)));
+  return VGE_OK;
+}
+
+// ---- the non-GEMM kernels (tests): arguments are checked, then the launcher the model calls runs and nothing else
+#define OP_REFUSE(cond, msg) \
+  if (cond) return fail(VGE_ERR_ARG, std::string(OP) + ": " + (msg))
+
+int vge_op_patchify(const uint8_t* frames, int F, int in_h, int in_w, int img_h, int img_w, int patch, int pad,
+                    void* out, vge_stream_t stream) {
+  static const char* OP = "vge_op_patchify";
+  std::string why;
+  OP_REFUSE(!geom_ok(in_h, in_w, img_h, img_w, patch, pad, why), why);
+  OP_REFUSE(F <= 0, "F must be positive");
+  OP_REFUSE(!frames || !out, "null pointer");
+  HIPCHK(vge::launch_patchify(frames, F, in_h, in_w, (in_w - img_w) / 2, img_h, img_w, patch, pad, 16, 12, IMG_MEAN,
+                              IMG_STD, out, S(stream)));
+  return VGE_OK;
+}
+
+int vge_op_xattn1(const void* q, long ldq, const void* kv, long ldkv, void* out, long ldo, int F, int heads, int ctx,
+                  vge_stream_t stream) {
+  static const char* OP = "vge_op_xattn1";
+  OP_REFUSE(ctx < 1 || ctx > 256, "ctx must be in [1, 256] (the kernel stages its scores in 256 floats of LDS)");
+  OP_REFUSE(F <= 0 || heads <= 0, "F, heads must be positive");
+  const long inner = 64L * heads;
+  OP_REFUSE(ldq % 8 || ldkv % 8 || ldo % 8, "ldq / ldkv / ldo must be multiples of 8");
+  OP_REFUSE(ldq < inner || ldo < inner || ldkv < 2 * inner, "ldq / ldo must be >= 64 heads, ldkv >= 128 heads");
+  OP_REFUSE(!q || !kv || !out, "null pointer");
+  HIPCHK(vge::launch_xattn1(q, ldq, kv, ldkv, out, ldo, F, (int)inner, heads, ctx, S(stream)));
+  return VGE_OK;
+}
+
+int vge_op_softmax_rows_bf16(const float* x, void* y, int rows, int C, vge_stream_t stream) {
+  static const char* OP = "vge_op_softmax_rows_bf16";
+  OP_REFUSE(rows <= 0 || C <= 0, "rows, C must be positive");
+  OP_REFUSE(!x || !y, "null pointer");
+  HIPCHK(vge::launch_softmax_rows(x, y, rows, C, S(stream)));
+  return VGE_OK;
+}
+
+int vge_op_hmr_readout(const float* rd, int ldrd, const float* bp, int ldbp, const float* init_pose,
+                       const float* init_betas, float* pose, float* gori, float* betas, int F, vge_stream_t stream) {
+  static const char* OP = "vge_op_hmr_readout";
+  OP_REFUSE(F <= 0 || F > (1 << 26), "F must be in [1, 2^26]");
+  OP_REFUSE(ldrd < 31, "ldrd must be >= 31 (grot 6 | hands 12 | shape 10 | cam 3)");
+  OP_REFUSE(ldbp < 126, "ldbp must be >= 126 (21 joints of 6)");
+  OP_REFUSE(!rd || !bp || !init_pose || !init_betas || !pose || !gori || !betas, "null pointer");
+  HIPCHK(vge::launch_readout(rd, ldrd, bp, ldbp, init_pose, init_betas, pose, gori, betas, F, S(stream)));
+  return VGE_OK;
+}
+
+int vge_op_cast_rows_bf16(const float* x, long ldx, void* y, long ldy, int rows, int D, vge_stream_t stream) {
+  static const char* OP = "vge_op_cast_rows_bf16";
+  OP_REFUSE(D <= 0 || D % 4, "D must be a positive multiple of 4");
+  OP_REFUSE(ldx < D || ldy < D, "ldx / ldy must be >= D");
+  OP_REFUSE(ldx % 4 || ldy % 4, "ldx / ldy must be multiples of 4 (4-wide loads and stores)");
+  OP_REFUSE(rows <= 0, "rows must be positive");
+  OP_REFUSE(!x || !y, "null pointer");
+  HIPCHK(vge::launch_cast_bf16(x, ldx, y, ldy, rows, D, S(stream)));
+  return VGE_OK;
+}
+
+int vge_op_bcast_rows(const float* vec, float* y, int rows, int D, vge_stream_t stream) {
+  static const char* OP = "vge_op_bcast_rows";
+  OP_REFUSE(rows <= 0 || D <= 0, "rows, D must be positive");
+  OP_REFUSE(!vec || !y, "null pointer");
+  HIPCHK(vge::launch_bcast_rows(vec, y, rows, D, S(stream)));
+  return VGE_OK;
+}
+
+int vge_op_copy_rows(const float* x, long ldx, float* y, long ldy, int rows, int D, vge_stream_t stream) {
+  static const char* OP = "vge_op_copy_rows";
+  OP_REFUSE(rows <= 0 || D <= 0, "rows, D must be positive");
+  OP_REFUSE(ldx < D || ldy < D, "ldx / ldy must be >= D");
+  OP_REFUSE(!x || !y, "null pointer");
+  HIPCHK(vge::launch_copy_rows(x, ldx, y, ldy, rows, D, S(stream)));
   return VGE_OK;
 }
 

@@ -1261,6 +1261,7 @@ hipError_t launch_vit_attn(const void* qkv, long ldq, void* out, long ldo, int F
 
 hipError_t launch_xattn1(const void* q, long ldq, const void* kv, long ldkv, void* out, long ldo, int F, int inner,
                          int heads, int ctx, hipStream_t s) {
+  if (ctx < 1 || ctx > 256) return hipErrorInvalidValue;  // the kernel's score buffer: __shared__ float p[256]
   hipLaunchKernelGGL(xattn1_kernel, dim3(F * heads), dim3(64), 0, s, reinterpret_cast<const bf16*>(q), ldq,
                      reinterpret_cast<const bf16*>(kv), ldkv, reinterpret_cast<bf16*>(out), ldo, inner, heads, ctx,
                      0.125f);

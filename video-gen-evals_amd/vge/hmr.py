@@ -67,6 +67,13 @@ _SIG = {
     "vge_op_vit_attention": [_vp, _vp, _i32, _i32, _i32, _vp],
     "vge_hmr_crop": [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp],
     "vge_op_layernorm_bf16": [_vp, _vp, _vp, _vp, _i32, _i32, C.c_float, _vp],
+    "vge_op_patchify": [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
+    "vge_op_xattn1": [_vp, C.c_long, _vp, C.c_long, _vp, C.c_long, _i32, _i32, _i32, _vp],
+    "vge_op_softmax_rows_bf16": [_vp, _vp, _i32, _i32, _vp],
+    "vge_op_hmr_readout": [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp],
+    "vge_op_cast_rows_bf16": [_vp, C.c_long, _vp, C.c_long, _i32, _i32, _vp],
+    "vge_op_bcast_rows": [_vp, _vp, _i32, _i32, _vp],
+    "vge_op_copy_rows": [_vp, C.c_long, _vp, C.c_long, _i32, _i32, _vp],
 }
 
 
@@ -150,23 +157,75 @@ def gemm_lib(A: torch.Tensor, W: torch.Tensor, epi: str = "bf16", bias=None, res
     return out
 
 
-def vit_attention(qkv: torch.Tensor, heads: int) -> torch.Tensor:
+def vit_attention(qkv: torch.Tensor, heads: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out: bf16, at least [rows, D] contiguous; rows behind qkv's are not written."""
     lib = _sig(L.load())
     rows, D3 = qkv.shape
     D = D3 // 3
-    out = torch.empty((rows, D), device=qkv.device, dtype=torch.bfloat16)
+    if out is None:
+        out = torch.empty((rows, D), device=qkv.device, dtype=torch.bfloat16)
     L.check(lib.vge_op_vit_attention(_ptr(qkv), _ptr(out), rows // 192, D, heads, _stream(qkv.device)),
             "vge_op_vit_attention")
     return out
 
 
-def layernorm_bf16(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float) -> torch.Tensor:
+def layernorm_bf16(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float,
+                   out: Optional[torch.Tensor] = None, rows: Optional[int] = None) -> torch.Tensor:
+    """out: bf16, at least [rows, D] contiguous; rows behind x's are not written.  rows: the leading rows of x to
+    normalise (all of them when None)."""
     lib = _sig(L.load())
-    rows, D = x.shape
-    out = torch.empty((rows, D), device=x.device, dtype=torch.bfloat16)
+    D = x.shape[1]
+    rows = x.shape[0] if rows is None else rows
+    if out is None:
+        out = torch.empty((rows, D), device=x.device, dtype=torch.bfloat16)
     L.check(lib.vge_op_layernorm_bf16(_ptr(x), _ptr(out), _ptr(w), _ptr(b), rows, D, eps, _stream(x.device)),
             "vge_op_layernorm_bf16")
     return out
+
+
+# The kernels around the GEMMs.  Tensors are passed by their first element with explicit row strides, so a caller may
+# hand in a view into a larger buffer (canary rows behind it, a row stride wider than the columns used).
+def _dp(t: Optional[torch.Tensor]) -> Optional[int]:
+    if t is None:
+        return None
+    if not t.is_cuda:
+        raise L.VgeError("vge ops need device (cuda/HIP) tensors")
+    return t.data_ptr()
+
+
+def _op(name: str, *args) -> None:
+    L.check(getattr(_sig(L.load()), name)(*args), name)
+
+
+def patchify(frames: torch.Tensor, out: torch.Tensor, img_w: int = 192, pad: int = 2, patch: int = 16) -> None:
+    """frames uint8 [F, in_h, in_w, 3] -> out bf16 [F * 192, 768] patch-embed rows (img_h = in_h)."""
+    F_, in_h, in_w = (int(v) for v in frames.shape[:3])
+    _op("vge_op_patchify", _ptr(frames), F_, in_h, in_w, in_h, img_w, patch, pad, _dp(out), _stream(frames.device))
+
+
+def xattn1(q, ldq: int, kv, ldkv: int, out, ldo: int, F_: int, heads: int, ctx: int) -> None:
+    _op("vge_op_xattn1", _dp(q), ldq, _dp(kv), ldkv, _dp(out), ldo, F_, heads, ctx, _stream(q.device))
+
+
+def softmax_rows_bf16(x: torch.Tensor, out: torch.Tensor, rows: int, Cc: int) -> None:
+    _op("vge_op_softmax_rows_bf16", _dp(x), _dp(out), rows, Cc, _stream(x.device))
+
+
+def hmr_readout(rd, ldrd: int, bp, ldbp: int, init_pose, init_betas, pose, gori, betas, F_: int) -> None:
+    _op("vge_op_hmr_readout", _dp(rd), ldrd, _dp(bp), ldbp, _dp(init_pose), _dp(init_betas), _dp(pose), _dp(gori),
+        _dp(betas), F_, _stream(rd.device))
+
+
+def cast_rows_bf16(x, ldx: int, y, ldy: int, rows: int, D: int) -> None:
+    _op("vge_op_cast_rows_bf16", _dp(x), ldx, _dp(y), ldy, rows, D, _stream(x.device))
+
+
+def bcast_rows(vec, y, rows: int, D: int) -> None:
+    _op("vge_op_bcast_rows", _dp(vec), _dp(y), rows, D, _stream(vec.device))
+
+
+def copy_rows(x, ldx: int, y, ldy: int, rows: int, D: int) -> None:
+    _op("vge_op_copy_rows", _dp(x), ldx, _dp(y), ldy, rows, D, _stream(x.device))
 
 
 def crop_persons(frames: torch.Tensor, boxes, frame_of=None) -> torch.Tensor:

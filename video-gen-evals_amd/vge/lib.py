@@ -28,6 +28,8 @@ EXPORTS = ["vge_featurize", "vge_featurize_layout", "vge_layout_feat_dim", "vge_
            "vge_ingest_default_threads",
            "vge_hmr_create", "vge_hmr_reserve", "vge_hmr_destroy", "vge_hmr_extract", "vge_hmr_profile_begin",
            "vge_hmr_profile_read", "vge_op_gemm_bf16", "vge_op_gemm_lib", "vge_op_vit_attention", "vge_op_layernorm_bf16",
+           "vge_op_patchify", "vge_op_xattn1", "vge_op_softmax_rows_bf16", "vge_op_hmr_readout",
+           "vge_op_cast_rows_bf16", "vge_op_bcast_rows", "vge_op_copy_rows",
            "vge_dwpose_create", "vge_dwpose_reserve", "vge_dwpose_destroy", "vge_dwpose_keypoints",
            "vge_dwpose_profile_begin", "vge_dwpose_profile_read", "vge_op_conv_bf16",
            "vge_op_dwconv_bf16", "vge_op_spp_pool_bf16", "vge_op_chan_attn_bf16", "vge_op_upsample2x_bf16",
