@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/vge_ingest.h"
+#include "vge_inflate_tables.h"
 
 namespace {
 
@@ -47,6 +48,12 @@ struct Mapped {
   Mapped& operator=(const Mapped&) = delete;
 };
 
+// a file's bytes, mapped or held in the caller's buffer
+struct Span {
+  const uint8_t* p = nullptr;
+  size_t n = 0;
+};
+
 inline uint16_t rd16(const uint8_t* p) { return (uint16_t)(p[0] | (p[1] << 8)); }
 inline uint32_t rd32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 inline uint64_t rd64(const uint8_t* p) { return (uint64_t)rd32(p) | ((uint64_t)rd32(p + 4) << 32); }
@@ -59,7 +66,7 @@ struct Member {
   const uint8_t* data = nullptr;  // compressed bytes
 };
 
-bool zip_members(const Mapped& f, std::vector<Member>& out) {
+bool zip_members(const Span& f, std::vector<Member>& out) {
   if (f.n < 22) return false;
   // end of central directory: the last 0x06054b50 within the trailing 64 KiB + 22 bytes
   size_t eocd = (size_t)-1;
@@ -278,36 +285,31 @@ bool shape_is(const NpyHeader& h, std::initializer_list<int64_t> tail, int64_t* 
 }
 
 // keypoints.npy: a plain (uncompressed) .npy file, [T',120] (any shape with 120 per row accepted)
-int kp_probe(const char* path, int32_t* rows, NpyHeader* hdr, Mapped** keep) {
+struct KpFile {
+  enum { ABSENT, OK, UNREADABLE } state = ABSENT;  // ABSENT: no path / no file: the caller decides
+  Span s;
+};
+
+int kp_probe(const KpFile& f, int32_t* rows, NpyHeader* hdr) {
   *rows = -1;
-  if (!path) return VGE_INGEST_OK;
-  if (::access(path, F_OK) != 0) return VGE_INGEST_OK;  // absent: the caller decides
-  Mapped* f = new Mapped(path);
-  if (!f->ok) {
-    delete f;
-    return VGE_INGEST_ERR_KP;
-  }
+  if (f.state == KpFile::ABSENT) return VGE_INGEST_OK;
+  if (f.state == KpFile::UNREADABLE) return VGE_INGEST_ERR_KP;
   NpyHeader h;
   size_t need = 0;
-  if (!parse_npy(f->p, f->n, h, need) || h.shape.empty() || h.count() < 0 || h.count() % 120 != 0 ||
-      h.header_bytes > f->n || (uint64_t)h.count() > (f->n - h.header_bytes) / (uint64_t)h.itemsize) {
-    delete f;
+  if (!parse_npy(f.s.p, f.s.n, h, need) || h.shape.empty() || h.count() < 0 || h.count() % 120 != 0 ||
+      h.header_bytes > f.s.n || (uint64_t)h.count() > (f.s.n - h.header_bytes) / (uint64_t)h.itemsize)
     return VGE_INGEST_ERR_KP;
-  }
   *rows = (int32_t)(h.count() / 120);
   if (hdr) *hdr = h;
-  if (keep) *keep = f;
-  else delete f;
   return VGE_INGEST_OK;
 }
 
-int probe_one(const char* npz, const char* kpp, vge_clip_info* info) {
+int probe_one(const Span& f, const KpFile& kpf, vge_clip_info* info) {
   info->n_frames = 0;
   info->vit_dim = 0;
   info->kp_frames = -1;
-  Mapped f(npz);
   std::vector<Member> ms;
-  if (!f.ok || !zip_members(f, ms)) return VGE_INGEST_ERR_IO;
+  if (f.n == 0 || !zip_members(f, ms)) return VGE_INGEST_ERR_IO;
   const Member* mp = find_member(ms, "pose");
   const Member* mv = find_member(ms, "vit");
   if (!mp || !mv) return VGE_INGEST_ERR_IO;
@@ -320,28 +322,29 @@ int probe_one(const char* npz, const char* kpp, vge_clip_info* info) {
   info->n_frames = (int32_t)T;
   info->vit_dim = (int32_t)hv.shape[1];
   int32_t rows = -1;
-  const int kr = kp_probe(kpp, &rows, nullptr, nullptr);
+  const int kr = kp_probe(kpf, &rows, nullptr);
   info->kp_frames = rows;
   return kr;
 }
 
-int decode_one(const char* npz, const char* kpp, const int32_t* vid, int vit_dim, float* pose, float* gori,
-               float* betas, float* vit, float* kp) {
-  Mapped f(npz);
+struct Want {
+  const char* key;
+  std::initializer_list<int64_t> tail;
+  int64_t width;
+};
+
+// Video `vid`'s streams -> d[5] (include/vge_ingest.h), checked as decode_one checks them; members' headers only.
+int plan_one(const uint8_t* base, const Span& f, const KpFile& kpf, const int32_t* vid, int vit_dim,
+             vge_inflate_desc* d, int video) {
   std::vector<Member> ms;
-  if (!f.ok || !zip_members(f, ms)) return VGE_INGEST_ERR_IO;
+  if (f.n == 0 || !zip_members(f, ms)) return VGE_INGEST_ERR_IO;
   const int64_t off = vid[0], T = vid[1];
-  struct Want {
-    const char* key;
-    std::initializer_list<int64_t> tail;
-    float* dst;
-    int64_t width;
-  };
-  const Want wants[4] = {{"pose", {23, 3, 3}, pose, 207},
-                         {"global_orient", {1, 3, 3}, gori, 9},
-                         {"betas", {10}, betas, 10},
-                         {"vit", {(int64_t)vit_dim}, vit, (int64_t)vit_dim}};
-  for (const Want& w : wants) {
+  const Want wants[4] = {{"pose", {23, 3, 3}, 207},
+                         {"global_orient", {1, 3, 3}, 9},
+                         {"betas", {10}, 10},
+                         {"vit", {(int64_t)vit_dim}, (int64_t)vit_dim}};
+  for (int a = 0; a < 4; ++a) {
+    const Want& w = wants[a];
     const Member* m = find_member(ms, w.key);
     if (!m) return VGE_INGEST_ERR_IO;
     MemberReader r(*m);
@@ -349,19 +352,66 @@ int decode_one(const char* npz, const char* kpp, const int32_t* vid, int vit_dim
     int64_t t = 0;
     if (!r.header(h)) return VGE_INGEST_ERR_IO;
     if (!shape_is(h, w.tail, &t) || t != T) return VGE_INGEST_ERR_SHAPE;
-    if (!r.data(w.dst + off * w.width, T * w.width)) return VGE_INGEST_ERR_IO;
+    if (m->method != 0 && m->method != 8) return VGE_INGEST_ERR_IO;
+    if (m->csize >= (1ull << 28)) return VGE_INGEST_ERR_ARG;
+    d[a].src_off = (int64_t)(m->data - base);
+    d[a].csize = (int64_t)m->csize;
+    d[a].count = T * w.width;
+    d[a].dst_off = off * w.width;
+    d[a].method = m->method;
+    d[a].skip = (int32_t)h.header_bytes;
+    d[a].itemsize = h.itemsize;
+    d[a].array = a;
+    d[a].video = video;
   }
   const int64_t koff = vid[2], kT = vid[3];
   if (kT > 0) {
-    Mapped* kf = nullptr;
     NpyHeader h;
     int32_t rows = -1;
-    const int kr = kp_probe(kpp, &rows, &h, &kf);
-    if (kr != VGE_INGEST_OK || rows != kT) {
-      delete kf;
-      return kr != VGE_INGEST_OK ? kr : VGE_INGEST_ERR_KP;
-    }
-    const uint8_t* src = kf->p + h.header_bytes;
+    const int kr = kp_probe(kpf, &rows, &h);
+    if (kr != VGE_INGEST_OK || rows != kT) return kr != VGE_INGEST_OK ? kr : VGE_INGEST_ERR_KP;
+    if (kpf.s.n >= (1ull << 28)) return VGE_INGEST_ERR_ARG;
+    d[4].src_off = (int64_t)(kpf.s.p - base);
+    d[4].csize = (int64_t)kpf.s.n;
+    d[4].count = kT * 120;
+    d[4].dst_off = koff * 120;
+    d[4].method = 0;
+    d[4].skip = (int32_t)h.header_bytes;
+    d[4].itemsize = h.itemsize;
+    d[4].array = 4;
+    d[4].video = video;
+  }
+  return VGE_INGEST_OK;
+}
+
+int decode_one(const Span& f, const KpFile& kpf, const int32_t* vid, int vit_dim, float* pose, float* gori,
+               float* betas, float* vit, float* kp) {
+  std::vector<Member> ms;
+  if (f.n == 0 || !zip_members(f, ms)) return VGE_INGEST_ERR_IO;
+  const int64_t off = vid[0], T = vid[1];
+  const Want wants[4] = {{"pose", {23, 3, 3}, 207},
+                         {"global_orient", {1, 3, 3}, 9},
+                         {"betas", {10}, 10},
+                         {"vit", {(int64_t)vit_dim}, (int64_t)vit_dim}};
+  float* const dsts[4] = {pose, gori, betas, vit};
+  for (int a = 0; a < 4; ++a) {
+    const Want& w = wants[a];
+    const Member* m = find_member(ms, w.key);
+    if (!m) return VGE_INGEST_ERR_IO;
+    MemberReader r(*m);
+    NpyHeader h;
+    int64_t t = 0;
+    if (!r.header(h)) return VGE_INGEST_ERR_IO;
+    if (!shape_is(h, w.tail, &t) || t != T) return VGE_INGEST_ERR_SHAPE;
+    if (!r.data(dsts[a] + off * w.width, T * w.width)) return VGE_INGEST_ERR_IO;
+  }
+  const int64_t koff = vid[2], kT = vid[3];
+  if (kT > 0) {
+    NpyHeader h;
+    int32_t rows = -1;
+    const int kr = kp_probe(kpf, &rows, &h);
+    if (kr != VGE_INGEST_OK || rows != kT) return kr != VGE_INGEST_OK ? kr : VGE_INGEST_ERR_KP;
+    const uint8_t* src = kpf.s.p + h.header_bytes;
     float* dst = kp + koff * 120;
     if (h.itemsize == 4) {
       memcpy(dst, src, (size_t)kT * 120 * 4);
@@ -372,9 +422,42 @@ int decode_one(const char* npz, const char* kpp, const int32_t* vid, int vit_dim
         dst[i] = (float)v;
       }
     }
-    delete kf;
   }
   return VGE_INGEST_OK;
+}
+
+// A video's two files from paths: mapped for the lifetime of the object.
+struct PathFiles {
+  Mapped npz;
+  Mapped* kpm = nullptr;
+  Span f;
+  KpFile kp;
+  PathFiles(const char* npz_path, const char* kp_path) : npz(npz_path) {
+    if (npz.ok) f = Span{npz.p, npz.n};
+    if (kp_path && ::access(kp_path, F_OK) == 0) {
+      kpm = new Mapped(kp_path);
+      kp.state = kpm->ok ? KpFile::OK : KpFile::UNREADABLE;
+      if (kpm->ok) kp.s = Span{kpm->p, kpm->n};
+    }
+  }
+  ~PathFiles() { delete kpm; }
+  PathFiles(const PathFiles&) = delete;
+  PathFiles& operator=(const PathFiles&) = delete;
+};
+
+// A video's two files from a packed buffer (entries 2i, 2i + 1); false: an entry outside the buffer.
+bool mem_files(const uint8_t* data, int64_t data_bytes, const int64_t* offsets, const int64_t* sizes, int i, Span& f,
+               KpFile& kp) {
+  auto inside = [&](int64_t off, int64_t size) {
+    return off >= 0 && size >= 0 && off <= data_bytes && size <= data_bytes - off;
+  };
+  if (!inside(offsets[2 * i], sizes[2 * i])) return false;
+  f = Span{data + offsets[2 * i], (size_t)sizes[2 * i]};
+  if (sizes[2 * i + 1] < 0) return true;  // no keypoint file
+  if (!inside(offsets[2 * i + 1], sizes[2 * i + 1])) return false;
+  kp.state = sizes[2 * i + 1] > 0 ? KpFile::OK : KpFile::UNREADABLE;
+  kp.s = Span{data + offsets[2 * i + 1], (size_t)sizes[2 * i + 1]};
+  return true;
 }
 
 // CPU share of this process: the cgroup v2 quota (cpu.max "quota period") when one is set, else the
@@ -436,14 +519,44 @@ void parallel_for(int n, int n_threads, Fn fn) {
 
 }  // namespace
 
+
+namespace {
+
+int first_failure(const int32_t* st, int n, int32_t* status) {
+  int rc = VGE_INGEST_OK;
+  for (int i = 0; i < n; ++i) {
+    if (status) status[i] = st[i];
+    if (rc == VGE_INGEST_OK) rc = st[i];
+  }
+  return rc;
+}
+
+bool decode_args_ok(int n, const int32_t* videos, int vit_dim, const float* pose, const float* gori,
+                    const float* betas, const float* vit, const float* kp) {
+  if (n < 0 || vit_dim < 1 || (n > 0 && (!videos || !pose || !gori || !betas || !vit))) return false;
+  for (int i = 0; i < n; ++i)
+    if (videos[4 * i + 3] > 0 && !kp) return false;
+  return true;
+}
+
+bool mem_args_ok(const uint8_t* data, int64_t data_bytes, const int64_t* offsets, const int64_t* sizes, int n) {
+  return n >= 0 && data_bytes >= 0 && (n == 0 || (data && offsets && sizes));
+}
+
+}  // namespace
+
 extern "C" {
 
 int vge_ingest_probe(const char* const* npz_paths, const char* const* kp_paths, int n, int n_threads,
                      vge_clip_info* info) {
   if (n < 0 || (n > 0 && (!npz_paths || !info))) return VGE_INGEST_ERR_ARG;
   parallel_for(n, n_threads, [&](int i) {
-    info[i].status = npz_paths[i] ? probe_one(npz_paths[i], kp_paths ? kp_paths[i] : nullptr, &info[i])
-                                  : VGE_INGEST_ERR_ARG;
+    if (!npz_paths[i]) {
+      info[i].status = VGE_INGEST_ERR_ARG;
+      return;
+    }
+    const PathFiles pf(npz_paths[i], kp_paths ? kp_paths[i] : nullptr);
+    info[i].status = probe_one(pf.f, pf.kp, &info[i]);
   });
   for (int i = 0; i < n; ++i)
     if (info[i].status != VGE_INGEST_OK) return info[i].status;
@@ -453,22 +566,96 @@ int vge_ingest_probe(const char* const* npz_paths, const char* const* kp_paths, 
 int vge_ingest_decode(const char* const* npz_paths, const char* const* kp_paths, int n, int n_threads,
                       const int32_t* videos, int vit_dim, float* pose, float* gori, float* betas, float* vit,
                       float* kp, int32_t* status) {
-  if (n < 0 || vit_dim < 1 || (n > 0 && (!npz_paths || !videos || !pose || !gori || !betas || !vit)))
+  if (!decode_args_ok(n, videos, vit_dim, pose, gori, betas, vit, kp) || (n > 0 && !npz_paths))
     return VGE_INGEST_ERR_ARG;
-  for (int i = 0; i < n; ++i)
-    if (videos[4 * i + 3] > 0 && !kp) return VGE_INGEST_ERR_ARG;
   std::vector<int32_t> st((size_t)n, VGE_INGEST_OK);
   parallel_for(n, n_threads, [&](int i) {
-    st[(size_t)i] = npz_paths[i] ? decode_one(npz_paths[i], kp_paths ? kp_paths[i] : nullptr, videos + 4 * i,
-                                              vit_dim, pose, gori, betas, vit, kp)
-                                 : VGE_INGEST_ERR_ARG;
+    if (!npz_paths[i]) {
+      st[(size_t)i] = VGE_INGEST_ERR_ARG;
+      return;
+    }
+    const PathFiles pf(npz_paths[i], kp_paths && videos[4 * i + 3] > 0 ? kp_paths[i] : nullptr);
+    st[(size_t)i] = decode_one(pf.f, pf.kp, videos + 4 * i, vit_dim, pose, gori, betas, vit, kp);
   });
-  int rc = VGE_INGEST_OK;
-  for (int i = 0; i < n; ++i) {
-    if (status) status[i] = st[(size_t)i];
-    if (rc == VGE_INGEST_OK) rc = st[(size_t)i];
-  }
-  return rc;
+  return first_failure(st.data(), n, status);
+}
+
+int vge_ingest_probe_mem(const uint8_t* data, int64_t data_bytes, const int64_t* offsets, const int64_t* sizes, int n,
+                         int n_threads, vge_clip_info* info) {
+  if (!mem_args_ok(data, data_bytes, offsets, sizes, n) || (n > 0 && !info)) return VGE_INGEST_ERR_ARG;
+  parallel_for(n, n_threads, [&](int i) {
+    Span f;
+    KpFile kp;
+    if (!mem_files(data, data_bytes, offsets, sizes, i, f, kp)) {
+      info[i] = vge_clip_info{0, 0, -1, VGE_INGEST_ERR_ARG};
+      return;
+    }
+    info[i].status = probe_one(f, kp, &info[i]);
+  });
+  for (int i = 0; i < n; ++i)
+    if (info[i].status != VGE_INGEST_OK) return info[i].status;
+  return VGE_INGEST_OK;
+}
+
+int vge_ingest_decode_mem(const uint8_t* data, int64_t data_bytes, const int64_t* offsets, const int64_t* sizes, int n,
+                          int n_threads, const int32_t* videos, int vit_dim, float* pose, float* gori, float* betas,
+                          float* vit, float* kp, int32_t* status) {
+  if (!mem_args_ok(data, data_bytes, offsets, sizes, n) ||
+      !decode_args_ok(n, videos, vit_dim, pose, gori, betas, vit, kp))
+    return VGE_INGEST_ERR_ARG;
+  std::vector<int32_t> st((size_t)n, VGE_INGEST_OK);
+  parallel_for(n, n_threads, [&](int i) {
+    Span f;
+    KpFile kpf;
+    st[(size_t)i] = mem_files(data, data_bytes, offsets, sizes, i, f, kpf)
+                        ? decode_one(f, kpf, videos + 4 * i, vit_dim, pose, gori, betas, vit, kp)
+                        : VGE_INGEST_ERR_ARG;
+  });
+  return first_failure(st.data(), n, status);
+}
+
+int vge_ingest_plan_mem(const uint8_t* data, int64_t data_bytes, const int64_t* offsets, const int64_t* sizes, int n,
+                        int n_threads, const int32_t* videos, int vit_dim, vge_inflate_desc* descs,
+                        vge_clip_info* info, int64_t* workspace_bytes) {
+  if (!mem_args_ok(data, data_bytes, offsets, sizes, n) || vit_dim < 1 || (n > 0 && (!videos || !descs || !info)))
+    return VGE_INGEST_ERR_ARG;
+  parallel_for(n, n_threads, [&](int i) {
+    vge_inflate_desc* d = descs + 5 * (size_t)i;
+    auto unused = [&]() {
+      for (int a = 0; a < 5; ++a) d[a] = vge_inflate_desc{0, 0, 0, 0, -1, 0, 0, 0, -1, i, 0};
+    };
+    unused();
+    Span f;
+    KpFile kp;
+    if (!mem_files(data, data_bytes, offsets, sizes, i, f, kp)) {
+      info[i] = vge_clip_info{0, 0, -1, VGE_INGEST_ERR_ARG};
+      return;
+    }
+    int s = probe_one(f, kp, &info[i]);
+    if (s == VGE_INGEST_ERR_KP && videos[4 * i + 3] == 0) s = VGE_INGEST_OK;  // unread, as vge_ingest_decode
+    if (s == VGE_INGEST_OK) s = plan_one(data, f, kp, videos + 4 * i, vit_dim, d, i);
+    if (s != VGE_INGEST_OK) unused();
+    info[i].status = s;
+  });
+  // float64 streams inflate into the workspace: one 8-byte aligned region each, assigned in slot order
+  int64_t ws = 0;
+  for (size_t k = 0; k < 5 * (size_t)n; ++k)
+    if (descs[k].array >= 0 && descs[k].itemsize == 8) {
+      descs[k].ws_off = ws;
+      ws += descs[k].count * 8;
+    }
+  if (workspace_bytes) *workspace_bytes = ws > 8 ? ws : 8;
+  for (int i = 0; i < n; ++i)
+    if (info[i].status != VGE_INGEST_OK) return info[i].status;
+  return VGE_INGEST_OK;
+}
+
+int vge_inflate_check_lengths(const uint8_t* lens, int n, int kind) {
+  if (!lens || n < 0 || n > vge_inflate::MAX_LITLEN || kind < 0 || kind > 2) return -1;
+  for (int i = 0; i < n; ++i)
+    if (lens[i] > vge_inflate::MAX_BITS) return -1;
+  vge_inflate::Table t;
+  return vge_inflate::build_table(t, lens, n, kind);
 }
 
 }  // extern "C"

@@ -150,7 +150,8 @@ def run_eval_distributed(generated_meshes_dir: str, real_meshes_dir: str, model_
                          real_kp_dir: str, clip_len: int = 32, stride: int = 8,
                          out_json: Optional[str] = "video_scores.json", device="cuda", compute: str = "f32x3",
                          timings: Optional[dict] = None, human_scores_path: Optional[str] = None,
-                         save_features: Optional[str] = None, stats_cache: Optional[str] = None):
+                         save_features: Optional[str] = None, stats_cache: Optional[str] = None,
+                         ingest: str = "host"):
     """vge.eval.run_eval sharded over the ranks of the initialised process group.  Returns the merged
     {video: {ac, tc}} dict on rank 0 (None elsewhere); rank 0 writes out_json, the Spearman correlations
     against `human_scores_path` (eval.py:456-464) and, with `save_features`, window_features.pt
@@ -158,8 +159,11 @@ def run_eval_distributed(generated_meshes_dir: str, real_meshes_dir: str, model_
     sorted generated list).  stats_cache: the real set's stats + centroid artifact (vge/stats_cache.py); when every
     rank reads a matching one the real set is skipped: no stats or centroid exchange, only int32 flag gathers (the
     cache-hit agreement and agree()'s error flags) before the score gather; otherwise the full flow runs and rank 0
-    writes the artifact after the exchanges."""
+    writes the artifact after the exchanges.  ingest "device" (vge.eval.device_frame_store): the archives are inflated
+    on the GPU, and what runs in the background is the read of the generated set's raw files."""
     from . import eval as VE
+    if ingest not in VE.INGEST_ROUTES:
+        raise ValueError(f"ingest must be one of {VE.INGEST_ROUTES}, not {ingest!r}")
     from .data import NpzVideoDataset, create_dataset_from_generated_meshes
     rank, ws = world()
     t0 = time.perf_counter()
@@ -178,13 +182,17 @@ def run_eval_distributed(generated_meshes_dir: str, real_meshes_dir: str, model_
         model_sha = guarded("stats cache fingerprint", model_digest, model_path)
     pool = ThreadPoolExecutor(max_workers=2)
     need_kp = keypoint_dir is not None
-    gen_fs = pool.submit(VE.load_frame_store, mine.items, keypoint_dir, need_kp) if mine.items and overlap else None
+    if ingest == "device":
+        from .ingest import read_item_files
+        gen_fs = pool.submit(read_item_files, mine.items, keypoint_dir) if mine.items and overlap else None
+    else:
+        gen_fs = pool.submit(VE.load_frame_store, mine.items, keypoint_dir, need_kp) if mine.items and overlap else None
     if overlap and isinstance(model_path, (str, os.PathLike)):  # the checkpoint read overlaps the real set's phases
         model_path = pool.submit(VE._load_state_dict, model_path)
     try:
         return _run_eval_phases(real_meshes_dir, model_path, keypoint_dir, real_kp_dir, clip_len, stride, out_json,
                                 device, compute, timings, rank, ws, t0, mine, gen_fs, human_scores_path,
-                                save_features, stats_cache, model_sha)
+                                save_features, stats_cache, model_sha, ingest)
     finally:
         pool.shutdown(wait=True)
 
@@ -203,7 +211,7 @@ def all_agree(flag: bool) -> bool:
 
 def _run_eval_phases(real_meshes_dir, model_path, keypoint_dir, real_kp_dir, clip_len, stride, out_json, device,
                      compute, timings, rank, ws, t0, mine, gen_fs, human_scores_path, save_features, stats_cache=None,
-                     model_sha=None):
+                     model_sha=None, ingest="host"):
     """Three rank-local phases, each closed by agree() before its exchange, so an error on one rank (a missing
     keypoints.npy, an unreadable checkpoint) makes every rank raise instead of leaving peers in a collective."""
     from . import eval as VE
@@ -240,15 +248,20 @@ def _run_eval_phases(real_meshes_dir, model_path, keypoint_dir, real_kp_dir, cli
     else:
         model, stats, centroids, t1, t2 = _real_set_phases(VE, ops, real_meshes_dir, model_path, real_kp_dir, clip_len,
                                                            stride, device, compute, rank, ws, train_ds, label_dict,
-                                                           load_clip, stats_cache, fp)
+                                                           load_clip, stats_cache, fp, ingest)
 
     # phase 3: this rank's generated videos -> (ac, tc); no collective until the gather to rank 0
     def local_scores():
         combined, feats_host = {}, None
         if mine.items:
-            fs = gen_fs.result() if gen_fs is not None else VE.load_frame_store(mine.items, keypoint_dir,
-                                                                                 keypoint_dir is not None)
-            store = ops.DeviceFrameStore.from_host(fs, device)
+            if ingest == "device":
+                from .ingest import load_device_frame_store
+                store = load_device_frame_store(mine.items, keypoint_dir, keypoint_dir is not None, device,
+                                                raw=gen_fs.result() if gen_fs is not None else None)
+            else:
+                fs = gen_fs.result() if gen_fs is not None else VE.load_frame_store(mine.items, keypoint_dir,
+                                                                                     keypoint_dir is not None)
+                store = ops.DeviceFrameStore.from_host(fs, device)
             feats = VE.extract_window_features(model, mine, keypoint_dir, stats, clip_len, stride, device,
                                                store=store, frame_embed=bool(save_features))
             ac = VE.compute_action_consistency_scores(feats, centroids, label_dict)
@@ -287,7 +300,7 @@ def _run_eval_phases(real_meshes_dir, model_path, keypoint_dir, real_kp_dir, cli
 
 
 def _real_set_phases(VE, ops, real_meshes_dir, model_path, real_kp_dir, clip_len, stride, device, compute, rank, ws,
-                     train_ds, label_dict, load_clip, stats_cache=None, fp=None):
+                     train_ds, label_dict, load_clip, stats_cache=None, fp=None, ingest="host"):
     """Phases 1-2 of the flow: the real-train shard's stats and centroid sufficient statistics, each exchanged after
     agree(); rank 0 writes the stats cache (when asked) from the exchanged sums."""
     my_train = shard(train_ds.items, rank, ws)
@@ -297,7 +310,7 @@ def _real_set_phases(VE, ops, real_meshes_dir, model_path, real_kp_dir, clip_len
         counts = np.zeros(2, np.int64)
         store = None
         if my_train:  # an empty shard still takes part in the exchange with zeros
-            store = ops.DeviceFrameStore.from_host(VE.load_frame_store(my_train, real_kp_dir, False), device)
+            store = VE.device_frame_store(my_train, real_kp_dir, False, device, ingest)
             ops.stats_accumulate(store, range(store.n_videos), sums, counts)
         return store, sums, counts
 

@@ -42,6 +42,22 @@ def load_frame_store(items: Sequence[VideoItem], keypoint_dir: Optional[str], re
     return load_frame_store_native(items, keypoint_dir, require_kp, threads=workers)
 
 
+INGEST_ROUTES = ("host", "device")
+
+
+def device_frame_store(items: Sequence[VideoItem], keypoint_dir: Optional[str], require_kp: bool, device,
+                       ingest: str = "host") -> ops.DeviceFrameStore:
+    """The frame store of `items` resident on `device`.  ingest "host": decoded by host threads into pinned memory
+    and uploaded (load_frame_store + from_host); "device": the raw files are uploaded and inflated on the GPU
+    (vge.ingest.load_device_frame_store).  Same contents, same exceptions."""
+    if ingest == "host":
+        return ops.DeviceFrameStore.from_host(load_frame_store(items, keypoint_dir, require_kp), device)
+    if ingest == "device":
+        from .ingest import load_device_frame_store
+        return load_device_frame_store(items, keypoint_dir, require_kp, device)
+    raise ValueError(f"ingest must be one of {INGEST_ROUTES}, not {ingest!r}")
+
+
 def load_frame_store_numpy(items: Sequence[VideoItem], keypoint_dir: Optional[str], require_kp: bool,
                            workers: int = 8) -> FrameStore:
     """The np.load reader (the reference's own, utils.py:383-424) in a thread pool: kept as the ingest
@@ -67,12 +83,13 @@ def stats_layout(counts) -> str:
 
 
 def compute_stats_from_npz(train_items: Sequence[VideoItem], keypoint_dir: str, device="cuda",
-                           store: Optional[ops.DeviceFrameStore] = None, reduce_fn=None) -> ModalityStatsGPU:
+                           store: Optional[ops.DeviceFrameStore] = None, reduce_fn=None,
+                           ingest: str = "host") -> ModalityStatsGPU:
     """utils.py:595-801.  `reduce_fn(sums, counts)` (optional) all-reduces the sufficient statistics
     across ranks before finalising (sharded real set)."""
     assert len(train_items) > 0, "compute_stats_from_npz: train_items is empty"
     if store is None:
-        store = ops.DeviceFrameStore.from_host(load_frame_store(train_items, keypoint_dir, require_kp=False), device)
+        store = device_frame_store(train_items, keypoint_dir, False, device, ingest)
     sums = torch.zeros((2, ops.FEAT_DIM), device=device, dtype=torch.float64)
     counts = np.zeros(2, np.int64)
     ops.stats_accumulate(store, range(store.n_videos), sums, counts)
@@ -176,7 +193,7 @@ def encode_windows(model: ops.Encoder, store: ops.DeviceFrameStore, windows: tor
 
 def build_real_centroids(model: ops.Encoder, real_meshes_dir: str, real_kp_dir: str, stats: ModalityStatsGPU,
                          clip_len: int = 32, stride: int = 8, device="cuda", train_items=None, label_dict=None,
-                         store: Optional[ops.DeviceFrameStore] = None, reduce_fn=None):
+                         store: Optional[ops.DeviceFrameStore] = None, reduce_fn=None, ingest: str = "host"):
     """eval.py:260-286 / utils.py:1018-1045 -> (centroids [C,256] device, label_dict, counts)."""
     if train_items is None or label_dict is None:
         real_ds = NpzVideoDataset(real_meshes_dir, filter_classes=ACTION_CLASSES)
@@ -189,8 +206,7 @@ def build_real_centroids(model: ops.Encoder, real_meshes_dir: str, real_kp_dir: 
     if len(train_items):
         samples = enumerate_test_windows(NpzVideoDataset("", items=list(train_items)), clip_len, stride)
         if store is None:
-            store = ops.DeviceFrameStore.from_host(load_frame_store(train_items, real_kp_dir,
-                                                                    require_kp=real_kp_dir is not None), device)
+            store = device_frame_store(train_items, real_kp_dir, real_kp_dir is not None, device, ingest)
         idx = {it.path: i for i, it in enumerate(train_items)}
         win = _window_tensor(samples, idx, device)
         seq, _, _ = encode_windows(model, store, win, stats)
@@ -203,7 +219,8 @@ def build_real_centroids(model: ops.Encoder, real_meshes_dir: str, real_kp_dir: 
 
 def extract_window_features(model: ops.Encoder, dataset: NpzVideoDataset, keypoint_dir: str, stats: ModalityStatsGPU,
                             clip_len: int = 32, stride: int = 8, device="cuda", frame_embed: bool = False,
-                            store: Optional[ops.DeviceFrameStore] = None, save_path: Optional[str] = None):
+                            store: Optional[ops.DeviceFrameStore] = None, save_path: Optional[str] = None,
+                            ingest: str = "host"):
     """eval.py:168-206 over all windows of `dataset` (sample_all_windows_npz order).  save_path: torch.save of
     {seq_embeds [Nw,256], frame_embeds [Nw,33,256], cls_names, vid_names} on the CPU like eval.py:197-204
     (frame embeddings are then produced too)."""
@@ -214,8 +231,7 @@ def extract_window_features(model: ops.Encoder, dataset: NpzVideoDataset, keypoi
                          f"layout but the real-set stats are {stats.layout!r}: pass both keypoint dirs or neither")
     samples = sample_all_windows_npz(dataset, clip_len, stride)
     if store is None:
-        store = ops.DeviceFrameStore.from_host(load_frame_store(dataset.items, keypoint_dir,
-                                                                require_kp=keypoint_dir is not None), device)
+        store = device_frame_store(dataset.items, keypoint_dir, keypoint_dir is not None, device, ingest)
     idx = {it.path: i for i, it in enumerate(dataset.items)}
     win = _window_tensor(samples, idx, device)
     seq, fe, tcw = encode_windows(model, store, win, stats, frame_embed=frame_embed or bool(save_path))
@@ -337,12 +353,16 @@ def stats_from_sums(sums, counts, device) -> ModalityStatsGPU:
 def run_eval(generated_meshes_dir: str, real_meshes_dir: str, model_path, keypoint_dir: str, real_kp_dir: str,
              human_scores_path: Optional[str] = None, clip_len: int = 32, stride: int = 8,
              out_json: Optional[str] = "video_scores.json", device="cuda", timings: Optional[dict] = None,
-             compute: str = "f32x3", save_features: Optional[str] = None, stats_cache: Optional[str] = None):
-    """eval.py __main__ (350-466) on one GPU; returns the combined {video: {ac, tc}} dict.  save_features: the
+             compute: str = "f32x3", save_features: Optional[str] = None, stats_cache: Optional[str] = None,
+             ingest: str = "host"):
+    """eval.py __main__ (350-466) on one GPU; returns the combined {video: {ac, tc}} dict.  ingest: where the npz
+    archives are inflated (device_frame_store).  save_features: the
     window_features.pt of eval.py:439-443 (off by default: it copies every frame embedding to the host).
     stats_cache: path of the real set's stats + centroid artifact (vge/stats_cache.py): read when its fingerprint
     matches (the real set is then neither decoded nor encoded), else computed and written."""
     from . import stats_cache as SC
+    if ingest not in INGEST_ROUTES:
+        raise ValueError(f"ingest must be one of {INGEST_ROUTES}, not {ingest!r}")
     t0 = time.perf_counter()
     real_ds = NpzVideoDataset(real_meshes_dir, filter_classes=ACTION_CLASSES)
     train_ds, _ = train_test_split(real_ds, train_ratio=0.8, seed=1337)
@@ -361,8 +381,7 @@ def run_eval(generated_meshes_dir: str, real_meshes_dir: str, model_path, keypoi
         centroids = ops.centroid_finalize(torch.from_numpy(hit["cent_sums"]).to(device),
                                           torch.from_numpy(hit["cent_counts"]).to(device))
     else:
-        real_store = ops.DeviceFrameStore.from_host(load_frame_store(train_ds.items, real_kp_dir, require_kp=False),
-                                                    device)
+        real_store = device_frame_store(train_ds.items, real_kp_dir, False, device, ingest)
         stats = compute_stats_from_npz(train_ds.items, real_kp_dir, device=device, store=real_store)
         dims_raw, dims_diff = infer_dims_from_stats(stats)
         model = load_model(model_path, dims_raw, dims_diff, device=device, compute=compute)
@@ -386,7 +405,7 @@ def run_eval(generated_meshes_dir: str, real_meshes_dir: str, model_path, keypoi
     t2 = time.perf_counter()
     dataset = create_dataset_from_generated_meshes(generated_meshes_dir)
     feats = extract_window_features(model, dataset, keypoint_dir, stats, clip_len, stride, device,
-                                    save_path=save_features)
+                                    save_path=save_features, ingest=ingest)
     ac = compute_action_consistency_scores(feats, centroids, label_dict)
     tc = compute_temporal_coherence_scores(feats, centroids, label_dict)
     combined = combine_scores(ac, tc)
@@ -432,6 +451,8 @@ def main(argv=None):
     ap.add_argument("--compute", default="f32x3", choices=["f32x3", "f32", "f16"])
     ap.add_argument("--stats-cache", default=None,
                     help="real-set stats + centroid artifact (.npz): reused when its fingerprint matches, else written")
+    ap.add_argument("--ingest", default="host", choices=list(INGEST_ROUTES),
+                    help="where the npz archives are inflated: host threads (default) or the GPU")
     a = ap.parse_args(argv)
     if (a.keypoints is None) != (a.real_keypoints is None):
         ap.error("--keypoints and --real-keypoints go together (both: the 5-modality layout; neither: keypoint-less)")
@@ -452,13 +473,13 @@ def main(argv=None):
             res = run_eval_distributed(a.generated_meshes, a.real_meshes, a.model, a.keypoints, a.real_keypoints,
                                        a.clip_len, a.stride, out_json=a.out, device=f"cuda:{local}",
                                        compute=a.compute, human_scores_path=a.human_scores,
-                                       save_features=a.save_features, stats_cache=a.stats_cache)
+                                       save_features=a.save_features, stats_cache=a.stats_cache, ingest=a.ingest)
         finally:
             dist.destroy_process_group()
     else:
         res = run_eval(a.generated_meshes, a.real_meshes, a.model, a.keypoints, a.real_keypoints, a.human_scores,
                        a.clip_len, a.stride, out_json=a.out, compute=a.compute, save_features=a.save_features,
-                       stats_cache=a.stats_cache)
+                       stats_cache=a.stats_cache, ingest=a.ingest)
     if res is not None:
         print(f"Saved AC/TC scores for {len(res)} videos to {a.out}")
     return 0

@@ -26,6 +26,9 @@ EXPORTS = ["vge_featurize", "vge_featurize_layout", "vge_layout_feat_dim", "vge_
            "vge_encoder_set_tail_stream", "vge_encoder_status", "vge_encoder_clear_status",
            "vge_ingest_decode",
            "vge_ingest_default_threads",
+           "vge_ingest_probe_mem", "vge_ingest_decode_mem", "vge_ingest_plan_mem", "vge_ingest_decode_device",
+           "vge_ingest_decode_device_workspace_bytes", "vge_ingest_decode_device_batch_symbols",
+           "vge_ingest_decode_device_ring_bytes", "vge_ingest_decode_device_stage_bytes", "vge_inflate_check_lengths",
            "vge_hmr_create", "vge_hmr_reserve", "vge_hmr_destroy", "vge_hmr_extract", "vge_hmr_profile_begin",
            "vge_hmr_profile_read", "vge_op_gemm_bf16", "vge_op_gemm_lib", "vge_op_vit_attention", "vge_op_layernorm_bf16",
            "vge_op_patchify", "vge_op_xattn1", "vge_op_softmax_rows_bf16", "vge_op_hmr_readout",
@@ -79,7 +82,13 @@ class ClipInfo(C.Structure):  # include/vge_ingest.h vge_clip_info
     _fields_ = [("n_frames", C.c_int32), ("vit_dim", C.c_int32), ("kp_frames", C.c_int32), ("status", C.c_int32)]
 
 
-INGEST_STATUS = {0: "OK", 1: "ERR_ARG", 7: "ERR_IO", 8: "ERR_SHAPE", 9: "ERR_KP"}
+class InflateDesc(C.Structure):  # include/vge_ingest.h vge_inflate_desc
+    _fields_ = [("src_off", C.c_int64), ("csize", C.c_int64), ("count", C.c_int64), ("dst_off", C.c_int64),
+                ("ws_off", C.c_int64), ("method", C.c_int32), ("skip", C.c_int32), ("itemsize", C.c_int32),
+                ("array", C.c_int32), ("video", C.c_int32), ("reserved", C.c_int32)]
+
+
+INGEST_STATUS = {0: "OK", 1: "ERR_ARG", 2: "ERR_HIP", 7: "ERR_IO", 8: "ERR_SHAPE", 9: "ERR_KP"}
 
 
 class JpegInfo(C.Structure):  # include/vge_frames.h vge_jpeg_info
@@ -146,6 +155,17 @@ def load() -> C.CDLL:
         "vge_ingest_probe": [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), i32, i32, C.POINTER(ClipInfo)],
         "vge_ingest_decode": [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), i32, i32, vp, i32, vp, vp, vp, vp, vp,
                               vp],
+        "vge_ingest_probe_mem": [vp, C.c_int64, vp, vp, i32, i32, C.POINTER(ClipInfo)],
+        "vge_ingest_decode_mem": [vp, C.c_int64, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp],
+        "vge_ingest_plan_mem": [vp, C.c_int64, vp, vp, i32, i32, vp, i32, C.POINTER(InflateDesc), C.POINTER(ClipInfo),
+                                i64p],
+        "vge_ingest_decode_device": [vp, C.c_int64, vp, i32, i32, C.c_int64, C.c_int64, i32, vp, vp, vp, vp, vp, vp,
+                                     C.c_int64, vp, vp],
+        "vge_ingest_decode_device_workspace_bytes": [C.POINTER(InflateDesc), i32],
+        "vge_ingest_decode_device_batch_symbols": [],
+        "vge_ingest_decode_device_ring_bytes": [],
+        "vge_ingest_decode_device_stage_bytes": [],
+        "vge_inflate_check_lengths": [vp, i32, i32],
         "vge_jpeg_probe": [C.POINTER(C.c_char_p), i32, i32, C.POINTER(JpegInfo)],
         "vge_jpeg_make_layout": [i32, i32, i32, i32, i32, C.POINTER(JpegLayout)],
         "vge_jpeg_entropy_decode": [C.POINTER(C.c_char_p), i32, i32, C.POINTER(JpegLayout), vp, vp, vp],
@@ -183,6 +203,7 @@ def load() -> C.CDLL:
     lib.vge_tcl_workspace_bytes.restype = C.c_size_t
     lib.vge_jpeg_entropy_workspace_bytes.restype = C.c_size_t
     lib.vge_jpeg_entropy_decode_workspace_bytes.restype = C.c_size_t
+    lib.vge_ingest_decode_device_workspace_bytes.restype = C.c_size_t
     lib.vge_last_error.restype = C.c_char_p
     lib.vge_version.restype = C.c_char_p
     _lib = lib

@@ -153,7 +153,7 @@ def validate_checkpoint(model: ops.Encoder, store: ops.DeviceFrameStore, windows
 
 def rank_checkpoints(real_meshes_dir: str, real_kp_dir: Optional[str], checkpoints: Sequence, compute: str = "f32x3",
                      seed: int = 1337, batch: int = 2048, clip_len: int = 32, stride: int = 8,
-                     device="cuda") -> List[dict]:
+                     device="cuda", ingest: str = "host") -> List[dict]:
     """Rank checkpoints by the held-out loss.  The data path is BaseExperiment.__init__'s (train.py:117-128):
     NpzVideoDataset over the ten classes, train_test_split(0.8, 1337), stats from the train split, label_dict from
     the sorted classes of the full set.  Stats, both frame stores and the window / label tensors are built once;
@@ -167,12 +167,10 @@ def rank_checkpoints(real_meshes_dir: str, real_kp_dir: Optional[str], checkpoin
     real_ds = NpzVideoDataset(real_meshes_dir, filter_classes=ACTION_CLASSES)
     train_ds, test_ds = train_test_split(real_ds, train_ratio=0.8, seed=1337)
     label_dict = {cls: i for i, cls in enumerate(sorted({it.cls for it in real_ds.items}))}
-    train_store = ops.DeviceFrameStore.from_host(E.load_frame_store(train_ds.items, real_kp_dir, require_kp=False),
-                                                 device)
+    train_store = E.device_frame_store(train_ds.items, real_kp_dir, False, device, ingest)
     stats = E.compute_stats_from_npz(train_ds.items, real_kp_dir, device=device, store=train_store)
     dims_raw, dims_diff = E.infer_dims_from_stats(stats)
-    test_store = ops.DeviceFrameStore.from_host(
-        E.load_frame_store(test_ds.items, real_kp_dir, require_kp=real_kp_dir is not None), device)
+    test_store = E.device_frame_store(test_ds.items, real_kp_dir, real_kp_dir is not None, device, ingest)
     samples = enumerate_test_windows(test_ds, clip_len, stride)
     idx = {it.path: i for i, it in enumerate(test_ds.items)}
     windows = E._window_tensor(samples, idx, device)
@@ -210,6 +208,8 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=1337)
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--out", default="ranking.json")
+    ap.add_argument("--ingest", default="host", choices=["host", "device"],
+                    help="where the npz archives are inflated: host threads (default) or the GPU")
     ap.add_argument("checkpoints", nargs="+", metavar="CKPT")
     a = ap.parse_args(argv)
     if a.kp_layout is not None:
@@ -218,7 +218,7 @@ def main(argv=None):
         from .data import set_keypoint_layout
         set_keypoint_layout(a.kp_layout, a.real_kp)
     ranking = rank_checkpoints(a.real_meshes, a.real_kp, a.checkpoints, compute=a.compute, seed=a.seed,
-                               batch=a.batch, device=a.device)
+                               batch=a.batch, device=a.device, ingest=a.ingest)
     for rank, r in enumerate(ranking, 1):
         if "error" in r:
             print(f"{rank:3d}  {r['checkpoint']}  unsupported: {r['error']}")
