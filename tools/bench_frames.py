@@ -1,7 +1,7 @@
 """Frames per second of vge.frames.load_frames on JPEG frame folders, split into its stages, beside Pillow.
 
     python tools/bench_frames.py [--frames 1024] [--size 256] [--quality 95] [--threads 16] [--folder DIR]
-                                 [--entropy host|device] [--out profiles/jpeg_decode.json]
+                                 [--entropy host|device] [--format jpg|png] [--out profiles/jpeg_decode.json]
 
 Writes its own JPEGs with Pillow (vge.synth.make_frames content, 4:2:0, quality 95: what cv2.imwrite writes) into a
 temporary folder, or reads the *.jpg files of --folder (cycled up to --frames).  Needs a GPU: there is no fallback.
@@ -21,6 +21,15 @@ profiles/jpeg_decode_device.json unless --out says otherwise):
   rounds          mean and max of rounds[]
   e2e_device      load_frames(paths, device, entropy="device") ending in a device synchronise   (host clock)
 The kernel's HBM floor is (coefficient + table + RGB bytes) / 6.3 TB/s (the achievable rate of a float4 copy).
+
+With --format png (written to profiles/png_decode_device.json unless --out says otherwise) the same frames are written
+as PNG files by Pillow at level 6, whose adaptive choice mixes the filter types, and both routes are measured:
+  host_decode     vge_png_decode on --threads host threads into pinned memory            (host clock)
+  plan            vge_png_plan_mem over the files in memory                              (host clock)
+  device_call     vge_png_decode_device: gather + inflate + adler + unfilter             (device events)
+  *_kernel        each of the four kernels alone                                         (device events)
+  e2e_host / e2e_device      load_frames(paths, device, entropy=...) ending in a device synchronise   (host clock)
+  e2e_jpeg_device            the same frames as JPEG files through load_frames(entropy="device")      (host clock)
 """
 from __future__ import annotations
 
@@ -60,8 +69,167 @@ def write_jpegs(folder: Path, n: int, size: int, quality: int):
     return paths
 
 
+def write_pngs(folder: Path, n: int, size: int):
+    """vge.synth.make_frames content as Pillow writes it at level 6: its adaptive choice mixes the five filter types."""
+    from PIL import Image
+    from vge import synth
+    paths = []
+    for v in range((n + 63) // 64):
+        fr = synth.make_frames(1000 + v, min(64, n - 64 * v), h=size, w=size)
+        for f in range(fr.shape[0]):
+            p = folder / f"frame_{64 * v + f:06d}.png"
+            Image.fromarray(fr[f]).save(p, format="PNG", compress_level=6)
+            paths.append(str(p))
+    return paths
+
+
+def bench_png(args) -> int:
+    """--format png: both routes of load_frames on a PNG folder, the device call's kernels one by one, and the JPEG
+    device route on the same frames beside them."""
+    import torch
+    from vge import frames as FR
+    from vge import lib as L
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_frames.py needs a GPU")
+    dev = torch.device("cuda:0")
+    lib = L.load()
+    tmp = tempfile.TemporaryDirectory()
+    (Path(tmp.name) / "png").mkdir()
+    (Path(tmp.name) / "jpg").mkdir()
+    paths = write_pngs(Path(tmp.name) / "png", args.frames, args.size)
+    jpegs = write_jpegs(Path(tmp.name) / "jpg", args.frames, args.size, args.quality)
+    n = len(paths)
+    rows = FR.png_probe(paths, args.threads)
+    assert not rows[:, -1].any()
+    key = tuple(int(x) for x in rows[0, :3])
+    w, h, ct = key
+    filters = {}
+    import zlib
+    for p in paths[:16]:   # which filter types the writer chose
+        data = open(p, "rb").read()
+        raw = zlib.decompress(b"".join(data[a:a + m] for a, m in _idat(data)))
+        for t in raw[::1 + w * 3]:
+            filters[int(t)] = filters.get(int(t), 0) + 1
+
+    def e2e(which, entropy):
+        t = time.perf_counter()
+        fr, kept = FR.load_frames(which, device=dev, threads=args.threads, entropy=entropy)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t
+        assert kept.size == n
+        return dt, fr
+
+    out_h = torch.empty((n, h, w, 3), dtype=torch.uint8, pin_memory=True)
+    status = np.zeros(n, np.int32)
+    arr = (C.c_char_p * n)(*[os.fsencode(p) for p in paths])
+
+    def host_decode():
+        t = time.perf_counter()
+        rc = lib.vge_png_decode(arr, n, args.threads, w, h, ct, out_h.data_ptr(), status.ctypes.data)
+        dt = time.perf_counter() - t
+        assert rc == 0, lib.vge_last_error()
+        return dt
+
+    raw, raw_off, raw_size = FR._read_files(paths, args.threads, pin=True)
+    raw_d = raw.to(dev)
+    descs = (L.PngDesc * n)()
+    n_segs, ws_bytes = C.c_int64(0), C.c_int64(0)
+    plan_st = np.zeros(n, np.int32)
+    seg_cap = int(rows[:, 5].sum())
+    segs = (L.PngSegment * seg_cap)()
+
+    def plan():
+        t = time.perf_counter()
+        rc = lib.vge_png_plan_mem(raw.data_ptr(), int(raw.numel()), raw_off.ctypes.data, raw_size.ctypes.data, n,
+                                  args.threads, w, h, ct, descs, segs, seg_cap, C.byref(n_segs), plan_st.ctypes.data,
+                                  C.byref(ws_bytes))
+        dt = time.perf_counter() - t
+        assert rc == 0, lib.vge_last_error()
+        return dt
+
+    plan()
+    descs_d = torch.frombuffer(descs, dtype=torch.uint8).to(dev)
+    segs_d = torch.frombuffer(segs, dtype=torch.uint8).to(dev)
+    ws = torch.empty(int(ws_bytes.value), dtype=torch.uint8, device=dev)
+    status_d = torch.empty(n, dtype=torch.int32, device=dev)
+    out_d = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev)
+
+    def device_call():
+        L.check(lib.vge_png_decode_device(raw_d.data_ptr(), int(raw_d.numel()), descs_d.data_ptr(), n,
+                                          segs_d.data_ptr(), n_segs.value, n, w, h, ct, ws.data_ptr(), int(ws.numel()),
+                                          out_d.data_ptr(), status_d.data_ptr(), stream.cuda_stream),
+                "vge_png_decode_device")
+
+    def events(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b) * 1e-3
+
+    def stage(mask):   # one kernel of the call alone (a hook of the library for this tool), on the data the others left
+        lib.vge_debug_png_stage_mask(mask)
+        try:
+            return events(device_call)
+        finally:
+            lib.vge_debug_png_stage_mask(15)
+
+    res = {}
+    for _ in range(args.warmup):
+        host_decode(); events(device_call); e2e(paths, "host"); e2e(paths, "device"); e2e(jpegs, "device")
+    res["host_decode_s"] = spread([host_decode() for _ in range(args.repeats)])
+    res["plan_s"] = spread([plan() for _ in range(args.repeats)])
+    res["device_call_s"] = spread([events(device_call) for _ in range(args.repeats)])
+    assert int(status_d.abs().sum()) == 0
+    calls_equal = bool(torch.equal(out_d.cpu(), out_h))
+    for name, mask in (("gather", 1), ("inflate", 2), ("adler", 4)):   # each after a whole call, before the unfilter
+        res[f"{name}_kernel_s"] = spread([stage(mask) for _ in range(args.repeats)])
+    device_call()
+    res["unfilter_kernel_s"] = spread([stage(8) for _ in range(args.repeats)])
+    eh = [e2e(paths, "host") for _ in range(args.repeats)]
+    ed = [e2e(paths, "device") for _ in range(args.repeats)]
+    ej = [e2e(jpegs, "device") for _ in range(args.repeats)]
+    res["e2e_host_s"] = spread([t for t, _ in eh])
+    res["e2e_device_s"] = spread([t for t, _ in ed])
+    res["e2e_jpeg_device_s"] = spread([t for t, _ in ej])
+    report = {
+        "what": "vge.frames.load_frames on a PNG folder, both routes, measured on the GPU by tools/bench_frames.py "
+                "--format png",
+        "device": torch.cuda.get_device_name(0), "frames": n, "width": w, "height": h, "color_type": ct,
+        "threads": args.threads,
+        "source": f"written here by Pillow: vge.synth.make_frames {args.size}x{args.size}, compress_level 6",
+        "filter_types_of_16_files": filters,
+        "png_bytes_per_frame": float(raw_size.mean()), "idat_chunks_per_frame": float(rows[:, 5].mean()),
+        "jpeg_bytes_per_frame": sum(os.path.getsize(p) for p in jpegs) / n,
+        "stages": res,
+        "ms_per_pass": {key[:-2]: 1e3 * v["median"] for key, v in res.items()},
+        "frames_per_s": {key[:-2]: n / v["median"] for key, v in res.items()},
+        "device_equals_host": calls_equal and bool(torch.equal(ed[-1][1], eh[-1][1])),
+    }
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(report, f, indent=1)
+    print(json.dumps(report))
+    tmp.cleanup()
+    return 0
+
+
+def _idat(data: bytes):
+    """(offset, length) of a PNG file's IDAT payloads."""
+    at, out = 8, []
+    while at + 8 <= len(data):
+        m, typ = int.from_bytes(data[at:at + 4], "big"), data[at + 4:at + 8]
+        if typ == b"IDAT":
+            out.append((at + 8, m))
+        at += 12 + m
+    return out
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--format", choices=("jpg", "png"), default="jpg")
     ap.add_argument("--frames", type=int, default=1024)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--quality", type=int, default=95)
@@ -73,6 +241,10 @@ def main(argv=None) -> int:
     ap.add_argument("--entropy", choices=("host", "device"), default="host")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
+    if args.format == "png":
+        if args.out is None:
+            args.out = str(REPO / "profiles" / "png_decode_device.json")
+        return bench_png(args)
     if args.out is None:
         args.out = str(REPO / "profiles" / ("jpeg_decode.json" if args.entropy == "host" else "jpeg_decode_device.json"))
 

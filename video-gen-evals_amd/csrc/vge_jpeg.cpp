@@ -22,56 +22,16 @@
 #include "../../include/vge_frames.h"
 #include "../../include/vge_ingest.h"
 #include "vge_error.h"
+#include "vge_host_files.h"
 #include "vge_jpeg_header.h"
 #include "vge_jpeg_huff_tables.h"
 #include "vge_jpeg_math.h"
 
+using vge::Mapped;
+using vge::parallel_for;
 using vge::set_last_error;
 
 namespace {
-
-struct Mapped {
-  const uint8_t* p = nullptr;
-  size_t n = 0;
-  bool ok = false;
-  explicit Mapped(const char* path) {
-    const int fd = ::open(path, O_RDONLY | O_CLOEXEC);
-    if (fd < 0) return;
-    struct stat st;
-    if (::fstat(fd, &st) == 0 && st.st_size > 0) {
-      void* m = ::mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-      if (m != MAP_FAILED) {
-        p = static_cast<const uint8_t*>(m);
-        n = (size_t)st.st_size;
-        ok = true;
-      }
-    }
-    ::close(fd);
-  }
-  ~Mapped() {
-    if (ok) ::munmap(const_cast<uint8_t*>(p), n);
-  }
-  Mapped(const Mapped&) = delete;
-  Mapped& operator=(const Mapped&) = delete;
-};
-
-template <class Fn>
-void parallel_for(int n, int n_threads, Fn fn) {
-  int T = n_threads > 0 ? n_threads : vge_ingest_default_threads();
-  T = std::max(1, std::min(T, n));
-  if (T == 1) {
-    for (int i = 0; i < n; ++i) fn(i);
-    return;
-  }
-  std::atomic<int> next{0};
-  std::vector<std::thread> pool;
-  pool.reserve((size_t)T);
-  for (int t = 0; t < T; ++t)
-    pool.emplace_back([&]() {
-      for (int i; (i = next.fetch_add(1)) < n;) fn(i);
-    });
-  for (std::thread& th : pool) th.join();
-}
 
 using vge_jpeg::kZigzag;  // vge_jpeg_huff_tables.h
 

@@ -313,9 +313,13 @@ def _save_json(path: Path, data) -> None:
 
 def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root, log_root, actions=None,
                        max_frames: int = 1024, device=None, threads: int = 0, crop=None,
-                       entropy: str = "host") -> Dict[str, Dict[str, list]]:
+                       entropy: str = "host", frame_format: str = "jpg",
+                       jpeg_quality: Optional[int] = None) -> Dict[str, Dict[str, list]]:
     """extract_mesh.py:150-241 and process_video.py:59-94 together, over the frame folders the reference leaves on
     disk: <frames_root>/<action>/<video>/*.jpg, decoded by vge.frames (the pixels cv2.imread gives the reference).
+    frame_format "png" reads <video>/*.png instead: the lossless frames a generator leaves, the array cap.read() would
+    have handed to the reference; with jpeg_quality (the reference's is 95) each pass's frames first go through
+    vge.frames.jpeg_roundtrip on their device, as in extract_videos, and the models see the reference's pixels.
 
     Per action, <log_root>/single/<action>.json and not_single/<action>.json (lists of video names) and
     errors/<action>.json ({video: message}) are rewritten after every video.  A video already in the single or
@@ -326,12 +330,16 @@ def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root
     counts); a pass's videos are decoded in one call and validated before the models see them, and when a pass raises,
     its videos are run again one by one so that one video's failure does not lose the others.
 
-    Outputs: <mesh_root>/<action>/<video>.npz (kept frames only; frame_idx indexes the folder's sorted *.jpg list, so
-    a frame that failed to decode shows as a gap; meta carries action / video / source_path) and
+    Outputs: <mesh_root>/<action>/<video>.npz (kept frames only; frame_idx indexes the folder's sorted list of *.jpg
+    (or *.png) files, so a frame that failed to decode shows as a gap; meta carries action / video / source_path) and
     <kp_root>/<action>/<video>/keypoints.npy.  actions: None (every folder of frames_root), a name or a list of names.
-    entropy: where the frames' Huffman decoding runs, "host" or "device" (vge.frames.load_frames).
+    entropy: where the frames' Huffman decoding (PNG: inflate and unfilter) runs, "host" or "device"
+    (vge.frames.load_frames).
     Returns {action: {"single": [...], "not_single": [...], "errors": [...], "skipped": [...]}} for this run."""
     from . import frames as FR
+    if frame_format not in ("jpg", "png"):
+        raise ValueError(f"frame_format must be 'jpg' or 'png', not {frame_format!r}")
+    ext = "." + frame_format
     frames_root, log_root = Path(frames_root), Path(log_root)
     all_actions = sorted(d.name for d in frames_root.iterdir() if d.is_dir())
     if actions is None:
@@ -382,7 +390,7 @@ def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root
                 print(f"[SKIP] {action}/{video} (already processed)")
                 done["skipped"].append(video)
                 continue
-            todo.append((video, FR.list_frames(action_dir / video)))
+            todo.append((video, FR.list_frames(action_dir / video, ext=ext)))
         for group in _pack_passes([(v, paths, len(paths)) for v, paths in todo], max_frames):
             # decode and validate: one call for the pass; a video that makes it raise is found one by one
             try:
@@ -400,11 +408,12 @@ def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root
                 if isinstance(dec, Exception):
                     fail(video, str(dec))
                 elif not paths:
-                    fail(video, f"no frames (*.jpg) in {action_dir / video}")
+                    fail(video, f"no frames (*{ext}) in {action_dir / video}")
                 elif dec[1].size == 0:
                     fail(video, f"none of the {len(paths)} frames in {action_dir / video} could be decoded")
                 else:
-                    good.append((video, dec[0], np.asarray(dec[1], np.int64)))
+                    fr = dec[0] if jpeg_quality is None else FR.jpeg_roundtrip(dec[0], quality=jpeg_quality)
+                    good.append((video, fr, np.asarray(dec[1], np.int64)))
             if not good:
                 continue
             # frames of one pass are stacked: consecutive videos of one frame size run together
@@ -452,7 +461,8 @@ def _load_state_dict(path: str) -> Dict[str, np.ndarray]:
 def main(argv=None) -> int:
     """python -m vge.extract: the reference's extract_mesh.py + process_video.py over a tree of frame folders."""
     import argparse
-    ap = argparse.ArgumentParser(description="TokenHMR meshes + DWPose keypoints from <frames-root>/<action>/<video>/*.jpg")
+    ap = argparse.ArgumentParser(
+        description="TokenHMR meshes + DWPose keypoints from <frames-root>/<action>/<video>/*.jpg (or *.png)")
     ap.add_argument("--frames-root", required=True)
     ap.add_argument("--mesh-root", required=True)
     ap.add_argument("--kp-root", required=True)
@@ -467,9 +477,14 @@ def main(argv=None) -> int:
                     help="deterministic random weights of the full-size models (vge.synth), for dry runs")
     ap.add_argument("--max-frames", type=int, default=1024, help="frames per GPU pass")
     ap.add_argument("--device", default="cuda:0")
-    ap.add_argument("--threads", type=int, default=0, help="JPEG entropy-decode threads (0: the ingest default)")
+    ap.add_argument("--threads", type=int, default=0, help="frame decode threads (0: the ingest default)")
     ap.add_argument("--entropy", choices=("host", "device"), default="host",
-                    help="where the frames' Huffman decoding runs (vge.frames.load_frames)")
+                    help="where the frames' Huffman decoding (PNG: inflate and unfilter) runs (vge.frames.load_frames)")
+    ap.add_argument("--frame-format", choices=("jpg", "png"), default="jpg",
+                    help="the frame files each video folder holds")
+    ap.add_argument("--jpeg-quality", type=int, default=None,
+                    help="send the decoded frames through a JPEG round trip of this quality before the models "
+                         "(the reference's cache is 95; meant for PNG frames)")
     args = ap.parse_args(argv)
     from . import synth
     from .dwpose import RTMPOSE_L, YOLOX_L, DwposeExtractor, Wholebody, YoloxDetector
@@ -494,7 +509,8 @@ def main(argv=None) -> int:
                                    RTMPOSE_L, device=dev, max_instances=2 * fc))
     summary = extract_frame_tree(hmr, wb, gdet, args.frames_root, args.mesh_root, args.kp_root, args.log_root,
                                  actions=args.action, max_frames=fc, device=dev, threads=args.threads,
-                                 entropy=args.entropy)
+                                 entropy=args.entropy, frame_format=args.frame_format,
+                                 jpeg_quality=args.jpeg_quality)
     for action, d in summary.items():
         print(f"[DONE] {action}: {len(d['single'])} single, {len(d['not_single'])} not single, "
               f"{len(d['errors'])} errors, {len(d['skipped'])} skipped")

@@ -15,6 +15,10 @@ encode_frames gives the same files in memory; on a GPU tensor it also Huffman-co
 its bytes.  decode_frames is the inverse of encode_frames: files held in memory, on either side, back to frames; for
 files on a GPU, and for load_frames(entropy="device"), Huffman decoding runs on the device too
 (vge_jpeg_entropy_decode_device, csrc/vge_jpeg_dehuff.hip) and what is uploaded is the file bytes.
+
+Folders of PNG frames (include/vge_png.h) take the same calls: a video is JPEG or PNG by its first file's signature;
+entropy "host" inflates and unfilters on host threads (vge_png_decode) and uploads the pixels, entropy "device" uploads
+the file bytes and runs vge_png_decode_device (csrc/vge_png.hip) on them.
 """
 from __future__ import annotations
 
@@ -38,10 +42,19 @@ class UnsupportedJpegError(L.VgeError):
     factors); the message names the kind and the file."""
 
 
-def list_frames(folder: PathLike) -> List[str]:
-    """extract_mesh.py:203-205: sorted(join(dir, f) for f in os.listdir(dir) if f.endswith('.jpg'))."""
+class UnsupportedPngError(L.VgeError):
+    """A PNG of a kind the decoders are not built for (interlaced, not 8 bits per sample, palette); the message names
+    the kind and the file."""
+
+
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+
+
+def list_frames(folder: PathLike, ext: str = ".jpg") -> List[str]:
+    """extract_mesh.py:203-205: sorted(join(dir, f) for f in os.listdir(dir) if f.endswith('.jpg')); ext=".png" lists
+    a folder of PNG frames the same way."""
     folder = os.fspath(folder)
-    return sorted(os.path.join(folder, f) for f in os.listdir(folder) if f.endswith(".jpg"))
+    return sorted(os.path.join(folder, f) for f in os.listdir(folder) if f.endswith(ext))
 
 
 def _paths_array(paths: Sequence[str]):
@@ -192,6 +205,135 @@ def _raise_unsupported(names, statuses) -> None:
                                        f"({L.JPEG_STATUS[int(s)]})")
 
 
+# ---- PNG frames (include/vge_png.h)
+
+def _png_rows(info, n: int) -> np.ndarray:
+    return np.array([[i.width, i.height, i.color_type, i.bit_depth, i.interlace, i.n_idat, i.idat_bytes, i.status]
+                     for i in info[:n]], dtype=np.int64).reshape(-1, 8)
+
+
+def png_probe(paths: Sequence[PathLike], threads: int = 0) -> np.ndarray:
+    """Headers only: int64 [n, 8] rows of (width, height, colour type, bit depth, interlace, IDAT chunks, IDAT bytes,
+    status) (vge_png_probe)."""
+    paths = [os.fspath(p) for p in paths]
+    info = (L.PngInfo * max(len(paths), 1))()
+    if paths:
+        L.load().vge_png_probe(_paths_array(paths), len(paths), int(threads), info)
+    return _png_rows(info, len(paths))
+
+
+def png_probe_mem(data: np.ndarray, offsets: np.ndarray, sizes: np.ndarray, threads: int = 0) -> np.ndarray:
+    """png_probe() for files in host memory: file i is data[offsets[i]:offsets[i] + sizes[i]] (vge_png_probe_mem)."""
+    n = len(offsets)
+    info = (L.PngInfo * max(n, 1))()
+    if n:
+        offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
+        L.load().vge_png_probe_mem(data.ctypes.data, data.size, offsets.ctypes.data, sizes.ctypes.data, n,
+                                   int(threads), info)
+    return _png_rows(info, n)
+
+
+def _raise_unsupported_png(names, statuses) -> None:
+    for p, s in zip(names, statuses):
+        if int(s) in L.PNG_UNSUPPORTED:
+            raise UnsupportedPngError(f"{p}: unsupported PNG: {L.PNG_UNSUPPORTED[int(s)]} ({L.PNG_STATUS[int(s)]})")
+
+
+def _png_decode_group(paths, data, offsets, sizes, key, device, threads: int):
+    """One (width, height, colour type)'s frames on host threads, from paths or (paths None) from files in host memory
+    (data: a uint8 CPU tensor) -> (uint8 [n, H, W, 3] tensor on `device`, int32 status [n]): vge_png_decode /
+    vge_png_decode_mem into pinned memory, then one upload."""
+    import torch
+    lib = L.load()
+    w, h, ct = key
+    n = len(paths) if paths is not None else len(offsets)
+    on_gpu = device.type == "cuda"
+    out = torch.empty((n, h, w, 3), dtype=torch.uint8, pin_memory=on_gpu)
+    status = np.zeros(n, np.int32)
+    if paths is not None:
+        lib.vge_png_decode(_paths_array(paths), n, int(threads), w, h, ct, out.data_ptr(), status.ctypes.data)
+    else:
+        offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
+        lib.vge_png_decode_mem(data.data_ptr(), int(data.numel()), offsets.ctypes.data, sizes.ctypes.data, n,
+                               int(threads), w, h, ct, out.data_ptr(), status.ctypes.data)
+    if on_gpu:
+        with torch.cuda.device(device):
+            out = out.to(device, non_blocking=True)
+    return out, status
+
+
+def _png_decode_group_device(data_h: np.ndarray, data_d, offsets: np.ndarray, sizes: np.ndarray, key, threads: int):
+    """One (width, height, colour type)'s files, their bytes both in host memory (data_h, which only the plan's chunk
+    walk reads) and on the GPU (data_d) -> (uint8 [n, H, W, 3] tensor on that GPU, int32 status [n]):
+    vge_png_plan_mem on the host, one upload of the descriptors and segments, vge_png_decode_device on the current
+    stream; the one host synchronisation is the copy of the statuses at the end."""
+    import torch
+    lib = L.load()
+    dev = data_d.device
+    w, h, ct = key
+    n = len(offsets)
+    offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
+    descs = (L.PngDesc * max(n, 1))()
+    planned = np.zeros(n, np.int32)
+    n_segs, ws_bytes = C.c_int64(0), C.c_int64(0)
+    args = (data_h.ctypes.data, data_h.size, offsets.ctypes.data, sizes.ctypes.data, n, int(threads), w, h, ct, descs)
+    lib.vge_png_plan_mem(*args, None, 0, C.byref(n_segs), planned.ctypes.data, None)   # the segment count
+    segs = (L.PngSegment * max(n_segs.value, 1))()
+    lib.vge_png_plan_mem(*args, segs, n_segs.value, C.byref(n_segs), planned.ctypes.data, C.byref(ws_bytes))
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        descs_d = torch.frombuffer(descs, dtype=torch.uint8).to(dev)
+        segs_d = torch.frombuffer(segs, dtype=torch.uint8).to(dev)
+        ws = torch.empty(int(ws_bytes.value), dtype=torch.uint8, device=dev)
+        status_d = torch.empty(n, dtype=torch.int32, device=dev)
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+        L.check(lib.vge_png_decode_device(data_d.data_ptr(), int(data_d.numel()), descs_d.data_ptr(), n,
+                                          segs_d.data_ptr(), n_segs.value, n, w, h, ct, ws.data_ptr(),
+                                          int(ws.numel()), out.data_ptr(), status_d.data_ptr(), stream.cuda_stream),
+                "vge_png_decode_device")
+        status = status_d.cpu().numpy()
+    return out, np.where(planned != 0, planned, status).astype(np.int32)
+
+
+def _first_good_key(rows: np.ndarray, n_key: int):
+    """The layout of a video: its first readable frame's leading probe columns (the last column is the status)."""
+    good = np.flatnonzero(rows[:, -1] == 0)
+    return tuple(int(x) for x in rows[good[0], :n_key]) if good.size else None
+
+
+def _keep_decoded(names, out, status, status_names, device):
+    """(frames, kept) of one video from its decoded rows and statuses; a failed frame is dropped with a log line."""
+    import torch
+    for p, s in zip(names, status):
+        if s != 0:
+            log.warning("dropping frame %s: %s", p, status_names.get(int(s), int(s)))
+    kept = np.flatnonzero(status == 0)
+    if kept.size != len(names):
+        out = out[torch.as_tensor(kept, device=device)]
+    return out, kept
+
+
+def _decode_frames_png(data, starts, sizes, names, device, threads: int, entropy: str):
+    """decode_frames for PNG files.  The plan walks chunk headers that lie all over a file, so for data on a GPU the
+    file bytes are copied to the host once for it (the pixels never are)."""
+    import torch
+    data_h = data.cpu() if data.device.type == "cuda" else data
+    info = png_probe_mem(data_h.numpy(), starts, sizes, threads)
+    _raise_unsupported_png(names, info[:, -1])
+    key = _first_good_key(info, 3)
+    if key is None:
+        for p in names:
+            log.warning("dropping frame %s: unreadable", p)
+        return torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=device), np.zeros(0, np.int64)
+    if entropy == "device":
+        data_d = data if data.device.type == "cuda" else data.to(device)
+        with torch.cuda.device(device):
+            out, status = _png_decode_group_device(data_h.numpy(), data_d, starts, sizes, key, threads)
+    else:
+        out, status = _png_decode_group(None, data_h, starts, sizes, key, device, threads)
+    return _keep_decoded(names, out, status, L.PNG_STATUS, device)
+
+
 _PROBE_HEAD = 1 << 16   # bytes of a device-resident file copied to the host for its header
 
 
@@ -217,7 +359,9 @@ def decode_frames(data, offsets, device=None, threads: int = 0, entropy: Optiona
     reconstructs on `device` (default: the current GPU when there is one, else the CPU); entropy "device" uploads the
     file bytes instead and decodes them there.
     Raises UnsupportedJpegError for a file of an unsupported kind; a file that does not decode is dropped with a log
-    message."""
+    message.
+    PNG files (the first file's signature decides) take the same arguments: entropy "host" is vge_png_decode_mem,
+    entropy "device" vge_png_plan_mem and vge_png_decode_device; UnsupportedPngError for an unsupported kind."""
     import torch
     if not (isinstance(data, torch.Tensor) and data.dtype == torch.uint8 and data.dim() == 1):
         raise ValueError("data must be a one-dimensional uint8 tensor")
@@ -243,6 +387,8 @@ def decode_frames(data, offsets, device=None, threads: int = 0, entropy: Optiona
         return empty
     if (sizes < 0).any() or off[0] < 0 or off[F] > data.numel():
         raise ValueError("offsets must be non-decreasing and inside data")
+    if data[int(starts[0]):int(starts[0]) + min(int(sizes[0]), 8)].cpu().numpy().tobytes() == PNG_SIGNATURE:
+        return _decode_frames_png(data, starts, sizes, names, device, threads, entropy)
     key = None
     if data_on_gpu:
         for i in range(F):   # the first readable file decides the layout, as in load_videos
@@ -474,14 +620,85 @@ def load_videos(videos: Sequence[Union[PathLike, Sequence[PathLike]]], device=No
     load_frames does.  entropy "host": Huffman decoding on host threads, the coefficients are uploaded.  entropy
     "device" (needs a GPU): host threads only read the raw files into one pinned buffer, the file bytes are uploaded
     once -- a quarter of the coefficients' bytes -- and vge_jpeg_entropy_decode_device decodes them; frames, kept,
-    dropped frames and errors are the same."""
-    import torch
+    dropped frames and errors are the same.
+    A video may also be a folder or list of PNG frames (a folder without *.jpg files gives its *.png files in sorted
+    order).  A video is JPEG or PNG by its first file's signature, and files of the other kind inside it are dropped as
+    unreadable.  PNG videos of one (width, height, colour type) share one call: entropy "host" decodes on host threads
+    into pinned memory and uploads the pixels (vge_png_decode); entropy "device" uploads the file bytes once and
+    inflates and unfilters them there (vge_png_plan_mem, vge_png_decode_device).  UnsupportedPngError names an
+    interlaced, non-8-bit or palette file."""
     device = _resolve_device(device)
     if entropy not in ("host", "device"):
         raise ValueError(f"entropy must be 'host' or 'device', not {entropy!r}")
     if entropy == "device" and device.type != "cuda":
         raise ValueError("entropy='device' needs a GPU")
-    vids = [list_frames(v) if isinstance(v, (str, os.PathLike)) else [os.fspath(p) for p in v] for v in videos]
+    vids = [_list_video(v) if isinstance(v, (str, os.PathLike)) else [os.fspath(p) for p in v] for v in videos]
+    is_png = [_is_png_file(v[0]) if v else False for v in vids]
+    results: List[Optional[Tuple]] = [None] * len(vids)
+    for png, load in ((False, _load_jpeg_videos), (True, _load_png_videos)):
+        which = [vi for vi, k in enumerate(is_png) if k == png]
+        if which:
+            for vi, r in zip(which, load([vids[vi] for vi in which], device, threads, entropy)):
+                results[vi] = r
+    return results
+
+
+def _list_video(folder: PathLike) -> List[str]:
+    """A frame folder's files: its *.jpg, or when it has none its *.png, in sorted order."""
+    return list_frames(folder) or list_frames(folder, ext=".png")
+
+
+def _is_png_file(path: str) -> bool:
+    try:
+        with open(path, "rb") as f:
+            return f.read(8) == PNG_SIGNATURE
+    except OSError:
+        return False
+
+
+def _load_png_videos(vids: List[List[str]], device, threads: int, entropy: str):
+    """load_videos for the PNG videos of a call."""
+    import torch
+    flat = [p for v in vids for p in v]
+    first_of = np.concatenate([[0], np.cumsum([len(v) for v in vids])]).astype(np.int64)
+    if entropy == "device":
+        raw, raw_off, raw_size = _read_files(flat, threads, pin=True)
+        info = png_probe_mem(raw.numpy(), raw_off, raw_size, threads)
+        with torch.cuda.device(device):
+            raw_d = raw.to(device, non_blocking=True)   # the one upload: every group decodes out of this buffer
+    else:
+        info = png_probe(flat, threads)
+    _raise_unsupported_png(flat, info[:, -1])
+    keys = [_first_good_key(info[first_of[vi]:first_of[vi + 1]], 3) for vi in range(len(vids))]
+    groups: dict = {}
+    for vi, key in enumerate(keys):
+        if key is not None:
+            groups.setdefault(key, []).append(vi)
+    results: List[Optional[Tuple]] = [None] * len(vids)
+    for key, members in groups.items():
+        if entropy == "device":
+            idx = np.concatenate([np.arange(first_of[vi], first_of[vi + 1]) for vi in members])
+            with torch.cuda.device(device):
+                out, status = _png_decode_group_device(raw.numpy(), raw_d, raw_off[idx], raw_size[idx], key, threads)
+        else:
+            out, status = _png_decode_group([p for vi in members for p in vids[vi]], None, None, None, key, device,
+                                            threads)
+        o = 0
+        for vi in members:
+            n = len(vids[vi])
+            results[vi] = _keep_decoded(vids[vi], out[o:o + n], status[o:o + n], L.PNG_STATUS, device)
+            o += n
+    for vi, key in enumerate(keys):
+        if key is None:
+            for p in vids[vi]:
+                log.warning("dropping frame %s: unreadable", p)
+            results[vi] = (torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=device), np.zeros(0, np.int64))
+    return results
+
+
+def _load_jpeg_videos(vids: List[List[str]], device, threads: int, entropy: str):
+    """load_videos for the JPEG videos of a call."""
+    import torch
     flat = [p for v in vids for p in v]
     if entropy == "device":
         raw, raw_off, raw_size = _read_files(flat, threads, pin=True)
@@ -536,7 +753,8 @@ def load_videos(videos: Sequence[Union[PathLike, Sequence[PathLike]]], device=No
 def load_frames(paths_or_dir: Union[PathLike, Sequence[PathLike]], device=None, threads: int = 0,
                 entropy: str = "host"):
     """load_frames_from_images (extract_mesh.py:72-82) on the GPU.  paths_or_dir: a frame folder (its *.jpg files in
-    sorted order) or a list of JPEG paths.  Returns (frames, kept): uint8 [F', H, W, 3] RGB on `device` (default: the
+    sorted order; its *.png files when it has no *.jpg) or a list of JPEG paths, or of PNG paths.
+    Returns (frames, kept): uint8 [F', H, W, 3] RGB on `device` (default: the
     current GPU when there is one, else the CPU) and the indices of the frames that decoded.  A frame that fails to
     decode is dropped with a log message, as the reference drops a None from cv2.imread; an unsupported kind of JPEG
     raises UnsupportedJpegError naming the kind and the file.  entropy: where Huffman decoding runs, "host" or "device"

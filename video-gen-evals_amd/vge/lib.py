@@ -52,6 +52,8 @@ EXPORTS = ["vge_featurize", "vge_featurize_layout", "vge_layout_feat_dim", "vge_
            "vge_jpeg_probe_mem", "vge_jpeg_entropy_decode_mem", "vge_jpeg_entropy_decode_workspace_bytes",
            "vge_jpeg_entropy_decode_device", "vge_jpeg_entropy_decode_subsequence_bytes",
            "vge_jpeg_entropy_decode_tile_bytes",
+           "vge_png_probe", "vge_png_probe_mem", "vge_png_decode", "vge_png_decode_mem", "vge_png_plan_mem",
+           "vge_png_decode_device", "vge_png_decode_device_workspace_bytes", "vge_png_decode_device_band_rows",
            "vge_time_gather", "vge_tcl_workspace_bytes", "vge_tcl_loss", "vge_hardneg_loss", "vge_centroid_distance"]
 
 
@@ -106,6 +108,27 @@ JPEG_STATUS = {0: "OK", 1: "ERR_ARG", 2: "ERR_HIP", 7: "ERR_IO", 8: "ERR_SHAPE",
                21: "ERR_ARITHMETIC", 22: "ERR_PRECISION", 23: "ERR_COMPONENTS", 24: "ERR_SAMPLING"}
 JPEG_UNSUPPORTED = {20: "progressive (or another non-baseline process)", 21: "arithmetic-coded", 22: "not 8-bit",
                     23: "neither 1 nor 3 components", 24: "sampling other than 4:4:4 / 4:2:2 / 4:2:0"}
+
+
+class PngInfo(C.Structure):  # include/vge_png.h vge_png_info
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("color_type", C.c_int32), ("bit_depth", C.c_int32),
+                ("interlace", C.c_int32), ("n_idat", C.c_int32), ("idat_bytes", C.c_int64), ("status", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class PngDesc(C.Structure):  # include/vge_png.h vge_png_desc
+    _fields_ = [("file_off", C.c_int64), ("file_bytes", C.c_int64), ("gat_off", C.c_int64), ("gat_bytes", C.c_int64),
+                ("slot_off", C.c_int64), ("raw_bytes", C.c_int64), ("color_type", C.c_int32), ("frame", C.c_int32)]
+
+
+class PngSegment(C.Structure):  # include/vge_png.h vge_png_segment
+    _fields_ = [("src_off", C.c_int64), ("dst_off", C.c_int64), ("bytes", C.c_int64), ("desc", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+PNG_STATUS = {0: "OK", 1: "ERR_ARG", 2: "ERR_HIP", 7: "ERR_IO", 8: "ERR_SHAPE", 30: "ERR_INTERLACED",
+              31: "ERR_BITDEPTH", 32: "ERR_PALETTE"}
+PNG_UNSUPPORTED = {30: "interlaced", 31: "not 8 bits per sample", 32: "palette"}
 
 
 class FrameStoreC(C.Structure):
@@ -189,6 +212,16 @@ def load() -> C.CDLL:
         "vge_jpeg_entropy_decode_device": [vp, C.c_int64, vp, vp, i32, C.POINTER(JpegLayout), vp, vp, vp, vp, vp, vp],
         "vge_jpeg_entropy_decode_subsequence_bytes": [],
         "vge_jpeg_entropy_decode_tile_bytes": [],
+        "vge_png_probe": [C.POINTER(C.c_char_p), i32, i32, C.POINTER(PngInfo)],
+        "vge_png_probe_mem": [vp, C.c_int64, vp, vp, i32, i32, C.POINTER(PngInfo)],
+        "vge_png_decode": [C.POINTER(C.c_char_p), i32, i32, i32, i32, i32, vp, vp],
+        "vge_png_decode_mem": [vp, C.c_int64, vp, vp, i32, i32, i32, i32, i32, vp, vp],
+        "vge_png_plan_mem": [vp, C.c_int64, vp, vp, i32, i32, i32, i32, i32, C.POINTER(PngDesc),
+                             C.POINTER(PngSegment), C.c_int64, i64p, vp, i64p],
+        "vge_png_decode_device": [vp, C.c_int64, vp, i32, vp, C.c_int64, i32, i32, i32, i32, vp, C.c_int64, vp, vp,
+                                  vp],
+        "vge_png_decode_device_workspace_bytes": [C.POINTER(PngDesc), i32],
+        "vge_png_decode_device_band_rows": [],
         "vge_time_gather": [vp, vp, i32, i32, i32, vp, vp],
         "vge_tcl_workspace_bytes": [i32],
         "vge_tcl_loss": [vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, vp, C.c_size_t, vp, vp],
@@ -204,6 +237,7 @@ def load() -> C.CDLL:
     lib.vge_jpeg_entropy_workspace_bytes.restype = C.c_size_t
     lib.vge_jpeg_entropy_decode_workspace_bytes.restype = C.c_size_t
     lib.vge_ingest_decode_device_workspace_bytes.restype = C.c_size_t
+    lib.vge_png_decode_device_workspace_bytes.restype = C.c_size_t
     lib.vge_last_error.restype = C.c_char_p
     lib.vge_version.restype = C.c_char_p
     _lib = lib
