@@ -1,7 +1,7 @@
 """Frames per second of vge.frames.load_frames on JPEG frame folders, split into its stages, beside Pillow.
 
     python tools/bench_frames.py [--frames 1024] [--size 256] [--quality 95] [--threads 16] [--folder DIR]
-                                 [--entropy host|device] [--format jpg|png] [--out profiles/jpeg_decode.json]
+                                 [--entropy host|device] [--format jpg|png|gif] [--out profiles/jpeg_decode.json]
 
 Writes its own JPEGs with Pillow (vge.synth.make_frames content, 4:2:0, quality 95: what cv2.imwrite writes) into a
 temporary folder, or reads the *.jpg files of --folder (cycled up to --frames).  Needs a GPU: there is no fallback.
@@ -30,6 +30,15 @@ as PNG files by Pillow at level 6, whose adaptive choice mixes the filter types,
   *_kernel        each of the four kernels alone                                         (device events)
   e2e_host / e2e_device      load_frames(paths, device, entropy=...) ending in a device synchronise   (host clock)
   e2e_jpeg_device            the same frames as JPEG files through load_frames(entropy="device")      (host clock)
+
+With --format gif (written to profiles/gif_decode_device.json unless --out says otherwise) the same frames are written
+as animated GIFs by Pillow, --gif-files files of --frames / --gif-files frames each (RGB frames, save_all=True: what
+diffusers' export_to_gif does, a local colour table per frame), and both routes are measured:
+  host_decode     vge_gif_decode on --threads host threads into pinned memory            (host clock)
+  plan            vge_gif_plan_mem over the files in memory                              (host clock)
+  device_call     vge_gif_decode_device: gather + LZW + compose                          (device events)
+  *_kernel        each of the three kernels alone                                        (device events)
+  e2e_host / e2e_device      load_videos(files, device, entropy=...) ending in a device synchronise   (host clock)
 """
 from __future__ import annotations
 
@@ -216,6 +225,141 @@ def bench_png(args) -> int:
     return 0
 
 
+def write_gifs(folder: Path, n_files: int, per_file: int, size: int):
+    """vge.synth.make_frames content as Pillow writes animated GIFs from RGB frames (each frame quantised to a local
+    table of its own), the way diffusers' export_to_gif calls it."""
+    from PIL import Image
+    from vge import synth
+    paths = []
+    for v in range(n_files):
+        fr = synth.make_frames(1000 + v, per_file, h=size, w=size)
+        ims = [Image.fromarray(fr[f]) for f in range(per_file)]
+        p = folder / f"clip_{v:04d}.gif"
+        ims[0].save(p, format="GIF", save_all=True, append_images=ims[1:], optimize=False, duration=100, loop=0)
+        paths.append(str(p))
+    return paths
+
+
+def bench_gif(args) -> int:
+    """--format gif: both routes of load_videos on animated GIFs and the device call's kernels one by one."""
+    import torch
+    from vge import frames as FR
+    from vge import lib as L
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_frames.py needs a GPU")
+    dev = torch.device("cuda:0")
+    lib = L.load()
+    tmp = tempfile.TemporaryDirectory()
+    n_files = args.gif_files
+    per_file = max(1, args.frames // n_files)
+    paths = write_gifs(Path(tmp.name), n_files, per_file, args.size)
+    rows = FR.gif_probe(paths, args.threads)
+    assert not rows[:, -1].any()
+    n = int(rows[:, 2].sum())
+    n_blocks = int(rows[:, 4].sum())
+    w, h = int(rows[0, 0]), int(rows[0, 1])
+
+    def e2e(entropy):
+        t = time.perf_counter()
+        out = FR.load_videos(paths, device=dev, threads=args.threads, entropy=entropy)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t
+        assert sum(k.size for _, k in out) == n
+        return dt, torch.cat([f for f, _ in out])
+
+    out_h = torch.empty((n, h, w, 3), dtype=torch.uint8, pin_memory=True)
+    status = np.zeros(n, np.int32)
+    arr = (C.c_char_p * n_files)(*[os.fsencode(p) for p in paths])
+
+    def host_decode():
+        t = time.perf_counter()
+        rc = lib.vge_gif_decode(arr, n_files, args.threads, w, h, n, out_h.data_ptr(), status.ctypes.data, None, None)
+        dt = time.perf_counter() - t
+        assert rc == 0, lib.vge_last_error()
+        return dt
+
+    raw, raw_off, raw_size = FR._read_files(paths, args.threads, pin=True)
+    raw_d = raw.to(dev)
+    descs = (L.GifDesc * n)()
+    segs = (L.GifSegment * n_blocks)()
+    n_descs, n_segs, ws_bytes = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+
+    def plan():
+        t = time.perf_counter()
+        rc = lib.vge_gif_plan_mem(raw.data_ptr(), int(raw.numel()), raw_off.ctypes.data, raw_size.ctypes.data, n_files,
+                                  args.threads, w, h, descs, n, C.byref(n_descs), segs, n_blocks, C.byref(n_segs),
+                                  None, None, C.byref(ws_bytes))
+        dt = time.perf_counter() - t
+        assert rc == 0 and n_descs.value == n, lib.vge_last_error()
+        return dt
+
+    plan()
+    descs_d = torch.frombuffer(descs, dtype=torch.uint8).to(dev)
+    segs_d = torch.frombuffer(segs, dtype=torch.uint8).to(dev)
+    ws = torch.empty(int(ws_bytes.value), dtype=torch.uint8, device=dev)
+    status_d = torch.empty(n, dtype=torch.int32, device=dev)
+    out_d = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev)
+
+    def device_call():
+        L.check(lib.vge_gif_decode_device(raw_d.data_ptr(), int(raw_d.numel()), descs_d.data_ptr(), n,
+                                          segs_d.data_ptr(), n_segs.value, n, n_files, w, h, ws.data_ptr(), int(ws.numel()),
+                                          out_d.data_ptr(), status_d.data_ptr(), stream.cuda_stream),
+                "vge_gif_decode_device")
+
+    def events(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b) * 1e-3
+
+    def stage(mask):   # one kernel of the call alone (a hook of the library for this tool), on the data the others left
+        lib.vge_debug_gif_stage_mask(mask)
+        try:
+            return events(device_call)
+        finally:
+            lib.vge_debug_gif_stage_mask(7)
+
+    res = {}
+    for _ in range(args.warmup):
+        host_decode(); events(device_call); e2e("host"); e2e("device")
+    res["host_decode_s"] = spread([host_decode() for _ in range(args.repeats)])
+    res["plan_s"] = spread([plan() for _ in range(args.repeats)])
+    res["device_call_s"] = spread([events(device_call) for _ in range(args.repeats)])
+    assert int(status_d.abs().sum()) == 0
+    calls_equal = bool(torch.equal(out_d.cpu(), out_h))
+    for name, mask in (("gather", 1), ("lzw", 2), ("compose", 4)):   # each on what a whole call left in the workspace
+        res[f"{name}_kernel_s"] = spread([stage(mask) for _ in range(args.repeats)])
+    eh = [e2e("host") for _ in range(args.repeats)]
+    ed = [e2e("device") for _ in range(args.repeats)]
+    res["e2e_host_s"] = spread([t for t, _ in eh])
+    res["e2e_device_s"] = spread([t for t, _ in ed])
+    report = {
+        "what": "vge.frames.load_videos on animated GIFs, both routes, measured on the GPU by tools/bench_frames.py "
+                "--format gif",
+        "device": torch.cuda.get_device_name(0), "files": n_files, "frames": n, "width": w, "height": h,
+        "threads": args.threads,
+        "source": f"written here by Pillow: vge.synth.make_frames {args.size}x{args.size}, RGB frames, save_all",
+        "gif_bytes_per_frame": float(raw_size.sum()) / n, "sub_blocks_per_frame": n_blocks / n,
+        "lzw_expansion": "chain walk: each lane walks its code's (prefix, suffix) links backwards from LDS",
+        "stages": res,
+        "ms_per_pass": {key[:-2]: 1e3 * v["median"] for key, v in res.items()},
+        "frames_per_s": {key[:-2]: n / v["median"] for key, v in res.items()},
+        "yardstick_host_decode_ms": 1e3 * res["host_decode_s"]["median"],
+        "device_call_ms": 1e3 * res["device_call_s"]["median"],
+        "lzw_share_of_device_call": res["lzw_kernel_s"]["median"] / res["device_call_s"]["median"],
+        "device_equals_host": calls_equal and bool(torch.equal(ed[-1][1], eh[-1][1])),
+    }
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(report, f, indent=1)
+    print(json.dumps(report))
+    tmp.cleanup()
+    return 0
+
+
 def _idat(data: bytes):
     """(offset, length) of a PNG file's IDAT payloads."""
     at, out = 8, []
@@ -229,7 +373,8 @@ def _idat(data: bytes):
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--format", choices=("jpg", "png"), default="jpg")
+    ap.add_argument("--format", choices=("jpg", "png", "gif"), default="jpg")
+    ap.add_argument("--gif-files", type=int, default=32, help="--format gif: files the frames are spread over")
     ap.add_argument("--frames", type=int, default=1024)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--quality", type=int, default=95)
@@ -245,6 +390,10 @@ def main(argv=None) -> int:
         if args.out is None:
             args.out = str(REPO / "profiles" / "png_decode_device.json")
         return bench_png(args)
+    if args.format == "gif":
+        if args.out is None:
+            args.out = str(REPO / "profiles" / "gif_decode_device.json")
+        return bench_gif(args)
     if args.out is None:
         args.out = str(REPO / "profiles" / ("jpeg_decode.json" if args.entropy == "host" else "jpeg_decode_device.json"))
 

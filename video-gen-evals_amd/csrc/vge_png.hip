@@ -3,6 +3,7 @@
 //
 //   gather    one workgroup per segment copies an IDAT payload to its place in the frame's gathered run, so that the
 //             bit reader sees one contiguous zlib stream however the writer cut it (Pillow: every 64 KiB; libpng: 8 KiB).
+//             The kernel is vge_gather.h's, shared with the GIF route.
 //   inflate   one wave per frame: the zlib header, then the shared core (vge_inflate_core.h) through its LDS ring into
 //             the frame's slot of filtered rows -- whole dwords, and at the end the last 1-3 bytes as one masked dword
 //             (slots are padded to a dword).  It reads on past the count as zlib does with one spare output byte, and
@@ -28,6 +29,7 @@
 
 #include "../../include/vge_png.h"
 #include "vge_error.h"
+#include "vge_gather.h"
 #include "vge_inflate_core.h"
 
 namespace {
@@ -36,7 +38,7 @@ using namespace vge_inflate;
 using vge::set_last_error;
 
 constexpr int BAND = WAVE;       // rows per unfilter band: one per lane
-constexpr int WIDE = 256;        // threads of the gather and Adler workgroups
+constexpr int WIDE = vge_gather::WIDE;  // threads of the gather and Adler workgroups
 constexpr uint32_t ADLER_MOD = 65521;
 
 struct Args {
@@ -82,22 +84,13 @@ __device__ inline void fail(const Args& A, int frame, int code) {
   if (threadIdx.x == 0) atomicCAS(&A.status[frame], 0, code);
 }
 
-__global__ __launch_bounds__(WIDE) void gather_kernel(Args A) {
-  if ((int64_t)blockIdx.x >= A.n_segs) return;
-  const vge_png_segment g = A.segs[blockIdx.x];
-  if (g.desc < 0 || g.desc >= A.n_descs) return;  // nobody to report to
-  const vge_png_desc d = A.descs[g.desc];
-  const int chk = check_desc(A, d);
-  if (chk < 0) return;
-  if (chk > 0) return fail(A, d.frame, chk);
-  if (g.bytes < 0 || g.src_off < d.file_off || g.src_off - d.file_off > d.file_bytes ||
-      g.bytes > d.file_bytes - (g.src_off - d.file_off) || g.dst_off < d.gat_off ||
-      g.dst_off - d.gat_off > d.gat_bytes || g.bytes > d.gat_bytes - (g.dst_off - d.gat_off))
-    return fail(A, d.frame, VGE_PNG_ERR_ARG);
-  const uint8_t* src = A.data + g.src_off;
-  uint8_t* dst = A.ws + g.dst_off;
-  for (int64_t k = threadIdx.x; k < g.bytes; k += WIDE) dst[k] = src[k];
-}
+// What the shared gather kernel (vge_gather.h) needs of this route.
+struct Route {
+  using Args = ::Args;
+  static constexpr int ERR_ARG = VGE_PNG_ERR_ARG;
+  static __device__ int check_desc(const Args& A, const vge_png_desc& d) { return ::check_desc(A, d); }
+  static __device__ void fail(const Args& A, int frame, int code) { ::fail(A, frame, code); }
+};
 
 __global__ __launch_bounds__(WAVE) void inflate_kernel(Args A) {
   __shared__ Shared S;
@@ -288,7 +281,8 @@ extern "C" int vge_png_decode_device(const uint8_t* data, int64_t data_bytes, co
   A.height = height;
   A.color_type = color_type;
   const int stages = g_stage_mask;
-  if (n_segs > 0 && (stages & 1)) hipLaunchKernelGGL(gather_kernel, dim3((unsigned)n_segs), dim3(WIDE), 0, s, A);
+  if (n_segs > 0 && (stages & 1))
+    hipLaunchKernelGGL(vge_gather::gather_kernel<Route>, dim3((unsigned)n_segs), dim3(WIDE), 0, s, A);
   if (stages & 2) hipLaunchKernelGGL(inflate_kernel, dim3((unsigned)n_descs), dim3(WAVE), 0, s, A);
   if (stages & 4) hipLaunchKernelGGL(adler_kernel, dim3((unsigned)n_descs), dim3(WIDE), 0, s, A);
   if (stages & 8) hipLaunchKernelGGL(unfilter_kernel, dim3((unsigned)n_descs), dim3(WAVE), 0, s, A);

@@ -320,6 +320,10 @@ def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root
     frame_format "png" reads <video>/*.png instead: the lossless frames a generator leaves, the array cap.read() would
     have handed to the reference; with jpeg_quality (the reference's is 95) each pass's frames first go through
     vge.frames.jpeg_roundtrip on their device, as in extract_videos, and the models see the reference's pixels.
+    frame_format "gif" reads videos that are one animated GIF each, <frames_root>/<action>/<video>.gif (the video name
+    is the stem): the frames are the GIF's composed frames (include/vge_gif.h), frame_idx indexes them, pass packing
+    uses the probe's frame counts and jpeg_quality applies as for PNG.  A GIF's frames from the first undecodable one
+    onward are dropped (they are deltas on it).
 
     Per action, <log_root>/single/<action>.json and not_single/<action>.json (lists of video names) and
     errors/<action>.json ({video: message}) are rewritten after every video.  A video already in the single or
@@ -331,15 +335,17 @@ def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root
     its videos are run again one by one so that one video's failure does not lose the others.
 
     Outputs: <mesh_root>/<action>/<video>.npz (kept frames only; frame_idx indexes the folder's sorted list of *.jpg
-    (or *.png) files, so a frame that failed to decode shows as a gap; meta carries action / video / source_path) and
+    (or *.png) files, or the GIF's frames, so a frame that failed to decode shows as a gap; meta carries action /
+    video / source_path) and
     <kp_root>/<action>/<video>/keypoints.npy.  actions: None (every folder of frames_root), a name or a list of names.
     entropy: where the frames' Huffman decoding (PNG: inflate and unfilter) runs, "host" or "device"
     (vge.frames.load_frames).
     Returns {action: {"single": [...], "not_single": [...], "errors": [...], "skipped": [...]}} for this run."""
     from . import frames as FR
-    if frame_format not in ("jpg", "png"):
-        raise ValueError(f"frame_format must be 'jpg' or 'png', not {frame_format!r}")
+    if frame_format not in ("jpg", "png", "gif"):
+        raise ValueError(f"frame_format must be 'jpg', 'png' or 'gif', not {frame_format!r}")
     ext = "." + frame_format
+    is_gif = frame_format == "gif"
     frames_root, log_root = Path(frames_root), Path(log_root)
     all_actions = sorted(d.name for d in frames_root.iterdir() if d.is_dir())
     if actions is None:
@@ -352,7 +358,13 @@ def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root
     summary: Dict[str, Dict[str, list]] = {}
     for action in actions:
         action_dir = frames_root / action
-        videos = sorted(d.name for d in action_dir.iterdir() if d.is_dir())
+        if is_gif:
+            videos = sorted(p.stem for p in action_dir.iterdir() if p.is_file() and p.suffix == ext)
+        else:
+            videos = sorted(d.name for d in action_dir.iterdir() if d.is_dir())
+
+        def source(video):
+            return action_dir / (video + ext if is_gif else video)
         single_path = log_root / "single" / f"{action}.json"
         not_path = log_root / "not_single" / f"{action}.json"
         err_path = log_root / "errors" / f"{action}.json"
@@ -362,7 +374,7 @@ def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root
         done = summary.setdefault(action, {"single": [], "not_single": [], "errors": [], "skipped": []})
 
         def fail(video, msg):
-            print(f"[WARN] Failed on {action_dir / video}: {msg}")
+            print(f"[WARN] Failed on {source(video)}: {msg}")
             errs[video] = msg
             _save_json(err_path, errs)
             done["errors"].append(video)
@@ -377,7 +389,7 @@ def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root
                 done["not_single"].append(video)
             else:
                 save_video_npz(str(Path(action) / video), _mesh_info(frames_kept[valid], rows), out_root=mesh_root,
-                               meta={"action": action, "video": video, "source_path": str(action_dir / video)})
+                               meta={"action": action, "video": video, "source_path": str(source(video))})
                 singles.append(video)
                 _save_json(single_path, singles)
                 done["single"].append(video)
@@ -390,8 +402,18 @@ def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root
                 print(f"[SKIP] {action}/{video} (already processed)")
                 done["skipped"].append(video)
                 continue
-            todo.append((video, FR.list_frames(action_dir / video, ext=ext)))
-        for group in _pack_passes([(v, paths, len(paths)) for v, paths in todo], max_frames):
+            todo.append((video, str(source(video)) if is_gif else FR.list_frames(action_dir / video, ext=ext)))
+        if is_gif:   # a video is one file: the probe gives its frame count
+            counts = FR.gif_probe([p for _, p in todo], threads)[:, 2] if todo else []
+            entries = []
+            for (v, p), n in zip(todo, counts):
+                if int(n) > 0:
+                    entries.append((v, p, int(n)))
+                else:
+                    fail(v, f"no decodable frame in {p}: not a GIF, truncated, or without an image")
+        else:
+            entries = [(v, paths, len(paths)) for v, paths in todo]
+        for group in _pack_passes(entries, max_frames):
             # decode and validate: one call for the pass; a video that makes it raise is found one by one
             try:
                 decoded = FR.load_videos([paths for _, paths, _ in group], device=device, threads=threads,
@@ -404,9 +426,11 @@ def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root
                     except Exception as e:
                         decoded.append(e)
             good = []
-            for (video, paths, _), dec in zip(group, decoded):
+            for (video, paths, count), dec in zip(group, decoded):
                 if isinstance(dec, Exception):
                     fail(video, str(dec))
+                elif is_gif and dec[1].size == 0:
+                    fail(video, f"none of the {count} frames of {paths} could be decoded")
                 elif not paths:
                     fail(video, f"no frames (*{ext}) in {action_dir / video}")
                 elif dec[1].size == 0:
@@ -462,7 +486,8 @@ def main(argv=None) -> int:
     """python -m vge.extract: the reference's extract_mesh.py + process_video.py over a tree of frame folders."""
     import argparse
     ap = argparse.ArgumentParser(
-        description="TokenHMR meshes + DWPose keypoints from <frames-root>/<action>/<video>/*.jpg (or *.png)")
+        description="TokenHMR meshes + DWPose keypoints from <frames-root>/<action>/<video>/*.jpg (or *.png), or "
+                    "<action>/<video>.gif")
     ap.add_argument("--frames-root", required=True)
     ap.add_argument("--mesh-root", required=True)
     ap.add_argument("--kp-root", required=True)
@@ -480,8 +505,8 @@ def main(argv=None) -> int:
     ap.add_argument("--threads", type=int, default=0, help="frame decode threads (0: the ingest default)")
     ap.add_argument("--entropy", choices=("host", "device"), default="host",
                     help="where the frames' Huffman decoding (PNG: inflate and unfilter) runs (vge.frames.load_frames)")
-    ap.add_argument("--frame-format", choices=("jpg", "png"), default="jpg",
-                    help="the frame files each video folder holds")
+    ap.add_argument("--frame-format", choices=("jpg", "png", "gif"), default="jpg",
+                    help="the frame files each video folder holds; gif: each video is one animated <video>.gif")
     ap.add_argument("--jpeg-quality", type=int, default=None,
                     help="send the decoded frames through a JPEG round trip of this quality before the models "
                          "(the reference's cache is 95; meant for PNG frames)")

@@ -19,6 +19,11 @@ files on a GPU, and for load_frames(entropy="device"), Huffman decoding runs on 
 Folders of PNG frames (include/vge_png.h) take the same calls: a video is JPEG or PNG by its first file's signature;
 entropy "host" inflates and unfilters on host threads (vge_png_decode) and uploads the pixels, entropy "device" uploads
 the file bytes and runs vge_png_decode_device (csrc/vge_png.hip) on them.
+
+An animated GIF (include/vge_gif.h) is a video in one file: load_frames("clip.gif") gives the frames
+PIL.ImageSequence gives after .convert("RGB").  entropy "host" is vge_gif_decode on host threads, entropy "device"
+vge_gif_plan_mem and vge_gif_decode_device (csrc/vge_gif.hip) on the uploaded file bytes; decode_gifs takes files
+packed in host memory.
 """
 from __future__ import annotations
 
@@ -47,7 +52,13 @@ class UnsupportedPngError(L.VgeError):
     the kind and the file."""
 
 
+class UnsupportedGifError(L.VgeError):
+    """A GIF the decoders refuse by name (a frame without any colour table, a frame that reaches outside the logical
+    screen); the message names the kind and the file."""
+
+
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+GIF_SIGNATURES = (b"GIF87a", b"GIF89a")
 
 
 def list_frames(folder: PathLike, ext: str = ".jpg") -> List[str]:
@@ -293,6 +304,196 @@ def _png_decode_group_device(data_h: np.ndarray, data_d, offsets: np.ndarray, si
                 "vge_png_decode_device")
         status = status_d.cpu().numpy()
     return out, np.where(planned != 0, planned, status).astype(np.int32)
+
+
+# ---- GIF videos (include/vge_gif.h)
+
+def _gif_rows(info, n: int) -> np.ndarray:
+    return np.array([[i.width, i.height, i.n_frames, i.lzw_bytes, i.n_blocks, i.status] for i in info[:n]],
+                    dtype=np.int64).reshape(-1, 6)
+
+
+def gif_probe(paths: Sequence[PathLike], threads: int = 0) -> np.ndarray:
+    """Headers and block structure only: int64 [n, 6] rows of (screen width, screen height, frames, LZW bytes, data
+    sub-blocks, status) (vge_gif_probe)."""
+    paths = [os.fspath(p) for p in paths]
+    info = (L.GifInfo * max(len(paths), 1))()
+    if paths:
+        L.load().vge_gif_probe(_paths_array(paths), len(paths), int(threads), info)
+    return _gif_rows(info, len(paths))
+
+
+def gif_probe_mem(data: np.ndarray, offsets: np.ndarray, sizes: np.ndarray, threads: int = 0) -> np.ndarray:
+    """gif_probe() for files in host memory: file i is data[offsets[i]:offsets[i] + sizes[i]] (vge_gif_probe_mem)."""
+    n = len(offsets)
+    info = (L.GifInfo * max(n, 1))()
+    if n:
+        offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
+        L.load().vge_gif_probe_mem(data.ctypes.data, data.size, offsets.ctypes.data, sizes.ctypes.data, n,
+                                   int(threads), info)
+    return _gif_rows(info, n)
+
+
+def _raise_unsupported_gif(names, statuses) -> None:
+    for p, s in zip(names, statuses):
+        if int(s) in L.GIF_UNSUPPORTED:
+            raise UnsupportedGifError(f"{p}: unsupported GIF: {L.GIF_UNSUPPORTED[int(s)]} ({L.GIF_STATUS[int(s)]})")
+
+
+def _gif_decode_group(paths, data, offsets, sizes, screen, n_frames: int, device, threads: int):
+    """The GIF files of one logical screen on host threads, from paths or (paths None) from files in host memory
+    (data: a uint8 CPU tensor) -> (uint8 [n_frames, H, W, 3] tensor on `device`, int32 status [n_frames]):
+    vge_gif_decode / vge_gif_decode_mem into pinned memory, then one upload.  n_frames: the probe's sum."""
+    import torch
+    lib = L.load()
+    w, h = screen
+    on_gpu = device.type == "cuda"
+    out = torch.empty((n_frames, h, w, 3), dtype=torch.uint8, pin_memory=on_gpu)
+    status = np.zeros(n_frames, np.int32)
+    if paths is not None:
+        lib.vge_gif_decode(_paths_array(paths), len(paths), int(threads), w, h, n_frames, out.data_ptr(),
+                           status.ctypes.data, None, None)
+    else:
+        offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
+        lib.vge_gif_decode_mem(data.data_ptr(), int(data.numel()), offsets.ctypes.data, sizes.ctypes.data,
+                               len(offsets), int(threads), w, h, n_frames, out.data_ptr(), status.ctypes.data, None,
+                               None)
+    if on_gpu:
+        with torch.cuda.device(device):
+            out = out.to(device, non_blocking=True)
+    return out, status
+
+
+def _gif_decode_group_device(data_h: np.ndarray, data_d, offsets: np.ndarray, sizes: np.ndarray, screen,
+                             n_frames: int, n_blocks: int, threads: int):
+    """The GIF files of one logical screen, their bytes both in host memory (data_h, which only the plan's block walk
+    reads) and on the GPU (data_d) -> (uint8 [n_frames, H, W, 3] tensor on that GPU, int32 status [n_frames]):
+    vge_gif_plan_mem on the host, one upload of the descriptors and segments, vge_gif_decode_device on the current
+    stream; the one host synchronisation is the copy of the statuses at the end.  n_frames, n_blocks: the probe's sums."""
+    import torch
+    lib = L.load()
+    dev = data_d.device
+    w, h = screen
+    offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
+    descs = (L.GifDesc * max(n_frames, 1))()
+    segs = (L.GifSegment * max(n_blocks, 1))()
+    planned = np.zeros(max(n_frames, 1), np.int32)
+    n_descs, n_segs, ws_bytes = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    lib.vge_gif_plan_mem(data_h.ctypes.data, data_h.size, offsets.ctypes.data, sizes.ctypes.data, len(offsets),
+                         int(threads), w, h, descs, n_frames, C.byref(n_descs), segs, n_blocks, C.byref(n_segs),
+                         planned.ctypes.data, None, C.byref(ws_bytes))
+    if n_descs.value != n_frames:
+        raise L.VgeError("vge_gif_plan_mem: " + lib.vge_last_error().decode(errors="replace"))
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        descs_d = torch.frombuffer(descs, dtype=torch.uint8).to(dev)
+        segs_d = torch.frombuffer(segs, dtype=torch.uint8).to(dev)
+        ws = torch.empty(int(ws_bytes.value), dtype=torch.uint8, device=dev)
+        status_d = torch.empty(n_frames, dtype=torch.int32, device=dev)
+        out = torch.empty((n_frames, h, w, 3), dtype=torch.uint8, device=dev)
+        L.check(lib.vge_gif_decode_device(data_d.data_ptr(), int(data_d.numel()), descs_d.data_ptr(), n_frames,
+                                          segs_d.data_ptr(), n_segs.value, n_frames, len(offsets), w, h, ws.data_ptr(),
+                                          int(ws.numel()), out.data_ptr(), status_d.data_ptr(), stream.cuda_stream),
+                "vge_gif_decode_device")
+        status = status_d.cpu().numpy()
+    planned = planned[:n_frames]
+    return out, np.where(planned != 0, planned, status).astype(np.int32)
+
+
+def _keep_gif_frames(name, out, status, device):
+    """(frames, kept) of one GIF video: the frames in front of the first one that failed."""
+    bad = np.flatnonzero(status != 0)
+    n = int(bad[0]) if bad.size else len(status)
+    if bad.size:
+        log.warning("dropping frames %d.. of %s: %s", n, name, L.GIF_STATUS.get(int(status[n]), int(status[n])))
+    return out[:n], np.arange(n, dtype=np.int64)
+
+
+def _empty_video(device):
+    import torch
+    return torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=device), np.zeros(0, np.int64)
+
+
+def _decode_gif_files(names, paths, raw, raw_off, raw_size, info, device, threads: int, entropy: str):
+    """The GIF videos of a call, from paths (host route) or from their bytes in one host tensor `raw` -> one
+    (frames, kept) per file.  info: their probe rows.  Files of one logical screen share one call."""
+    import torch
+    _raise_unsupported_gif(names, info[:, 5])
+    results: List[Optional[Tuple]] = [None] * len(names)
+    groups: dict = {}
+    for i, row in enumerate(info):
+        if int(row[2]) > 0 and int(row[5]) != 1:   # a file with frames, of a size the decoders take
+            groups.setdefault((int(row[0]), int(row[1])), []).append(i)
+        else:
+            log.warning("no decodable frame in %s: %s", names[i], L.GIF_STATUS.get(int(row[5]), int(row[5])))
+            results[i] = _empty_video(device)
+    raw_d = None
+    if entropy == "device" and groups:
+        with torch.cuda.device(device):
+            raw_d = raw.to(device, non_blocking=True)   # the one upload: every group decodes out of this buffer
+    for screen, members in groups.items():
+        counts = [int(info[i, 2]) for i in members]
+        total, blocks = sum(counts), int(sum(info[i, 4] for i in members))
+        if entropy == "device":
+            with torch.cuda.device(device):
+                out, status = _gif_decode_group_device(raw.numpy(), raw_d, raw_off[members], raw_size[members], screen,
+                                                       total, blocks, threads)
+        elif paths is not None:
+            out, status = _gif_decode_group([paths[i] for i in members], None, None, None, screen, total, device,
+                                            threads)
+        else:
+            out, status = _gif_decode_group(None, raw, raw_off[members], raw_size[members], screen, total, device,
+                                            threads)
+        o = 0
+        for i, n in zip(members, counts):
+            results[i] = _keep_gif_frames(names[i], out[o:o + n], status[o:o + n], device)
+            if results[i][1].size == 0:
+                log.warning("no decodable frame in %s", names[i])
+            o += n
+    return results
+
+
+def _load_gif_videos(paths: List[str], device, threads: int, entropy: str):
+    """load_videos for the GIF videos of a call."""
+    if entropy == "device":
+        raw, raw_off, raw_size = _read_files(paths, threads, pin=True)
+        info = gif_probe_mem(raw.numpy(), raw_off, raw_size, threads)
+        return _decode_gif_files(paths, None, raw, raw_off, raw_size, info, device, threads, entropy)
+    return _decode_gif_files(paths, paths, None, None, None, gif_probe(paths, threads), device, threads, entropy)
+
+
+def decode_gifs(data, offsets, device=None, threads: int = 0, entropy: Optional[str] = None):
+    """GIF videos packed in host memory -- (data, offsets[F + 1]): file i at data[offsets[i]:offsets[i + 1]] of a
+    one-dimensional uint8 CPU tensor -- -> one (frames, kept) per file, as load_videos gives them.  entropy "host" (the
+    default without a GPU) decodes on host threads (vge_gif_decode_mem) and uploads the pixels to `device`; entropy
+    "device" (the default with one) uploads the file bytes and runs vge_gif_plan_mem and vge_gif_decode_device.  The
+    plan walks every sub-block of every file on the host, so a buffer that lives on a GPU is refused, not copied back."""
+    import torch
+    if not (isinstance(data, torch.Tensor) and data.dtype == torch.uint8 and data.dim() == 1):
+        raise ValueError("data must be a one-dimensional uint8 tensor")
+    if data.device.type != "cpu":
+        raise ValueError("decode_gifs needs the file bytes in host memory: the plan walks every data sub-block on "
+                         "the host; pass a CPU tensor (entropy='device' uploads it once)")
+    off = np.ascontiguousarray(offsets.cpu().numpy() if isinstance(offsets, torch.Tensor) else offsets, np.int64)
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError("offsets must be int64 [F + 1]")
+    device = _resolve_device(device)
+    if entropy is None:
+        entropy = "device" if device.type == "cuda" else "host"
+    if entropy not in ("host", "device"):
+        raise ValueError(f"entropy must be 'host' or 'device', not {entropy!r}")
+    if entropy == "device" and device.type != "cuda":
+        raise ValueError("entropy='device' needs a GPU")
+    F = off.size - 1
+    if F == 0:
+        return []
+    starts, sizes = off[:F].copy(), np.diff(off)
+    if (sizes < 0).any() or off[0] < 0 or off[F] > data.numel():
+        raise ValueError("offsets must be non-decreasing and inside data")
+    data = data.contiguous()
+    names = [f"file {i}" for i in range(F)]
+    info = gif_probe_mem(data.numpy(), starts, sizes, threads)
+    return _decode_gif_files(names, None, data, starts, sizes, info, device, threads, entropy)
 
 
 def _first_good_key(rows: np.ndarray, n_key: int):
@@ -626,17 +827,29 @@ def load_videos(videos: Sequence[Union[PathLike, Sequence[PathLike]]], device=No
     unreadable.  PNG videos of one (width, height, colour type) share one call: entropy "host" decodes on host threads
     into pinned memory and uploads the pixels (vge_png_decode); entropy "device" uploads the file bytes once and
     inflates and unfilters them there (vge_png_plan_mem, vge_png_decode_device).  UnsupportedPngError names an
-    interlaced, non-8-bit or palette file."""
+    interlaced, non-8-bit or palette file.
+    An entry that is a path to a regular file whose first six bytes are GIF87a or GIF89a is a GIF video
+    (include/vge_gif.h): its frames are the video's frames and `kept` indexes them.  GIF videos of one logical screen
+    share one call: entropy "host" decodes on host threads into pinned memory and uploads the pixels (vge_gif_decode);
+    entropy "device" uploads the file bytes once and runs vge_gif_plan_mem and vge_gif_decode_device.  A frame that
+    does not decode is dropped with every later frame of its file (they are deltas on it), with a log line;
+    UnsupportedGifError names a file with a frame that has no colour table or that overflows the logical screen."""
     device = _resolve_device(device)
     if entropy not in ("host", "device"):
         raise ValueError(f"entropy must be 'host' or 'device', not {entropy!r}")
     if entropy == "device" and device.type != "cuda":
         raise ValueError("entropy='device' needs a GPU")
-    vids = [_list_video(v) if isinstance(v, (str, os.PathLike)) else [os.fspath(p) for p in v] for v in videos]
+    is_gif = [isinstance(v, (str, os.PathLike)) and _is_gif_file(os.fspath(v)) for v in videos]
+    vids = [[] if g else _list_video(v) if isinstance(v, (str, os.PathLike)) else [os.fspath(p) for p in v]
+            for v, g in zip(videos, is_gif)]
     is_png = [_is_png_file(v[0]) if v else False for v in vids]
     results: List[Optional[Tuple]] = [None] * len(vids)
+    gifs = [vi for vi, g in enumerate(is_gif) if g]
+    if gifs:
+        for vi, r in zip(gifs, _load_gif_videos([os.fspath(videos[vi]) for vi in gifs], device, threads, entropy)):
+            results[vi] = r
     for png, load in ((False, _load_jpeg_videos), (True, _load_png_videos)):
-        which = [vi for vi, k in enumerate(is_png) if k == png]
+        which = [vi for vi, k in enumerate(is_png) if k == png and not is_gif[vi]]
         if which:
             for vi, r in zip(which, load([vids[vi] for vi in which], device, threads, entropy)):
                 results[vi] = r
@@ -646,6 +859,17 @@ def load_videos(videos: Sequence[Union[PathLike, Sequence[PathLike]]], device=No
 def _list_video(folder: PathLike) -> List[str]:
     """A frame folder's files: its *.jpg, or when it has none its *.png, in sorted order."""
     return list_frames(folder) or list_frames(folder, ext=".png")
+
+
+def _is_gif_file(path: str) -> bool:
+    """A path to a regular file whose first six bytes are a GIF signature: a GIF video."""
+    try:
+        if not os.path.isfile(path):
+            return False
+        with open(path, "rb") as f:
+            return f.read(6) in GIF_SIGNATURES
+    except OSError:
+        return False
 
 
 def _is_png_file(path: str) -> bool:
@@ -753,7 +977,8 @@ def _load_jpeg_videos(vids: List[List[str]], device, threads: int, entropy: str)
 def load_frames(paths_or_dir: Union[PathLike, Sequence[PathLike]], device=None, threads: int = 0,
                 entropy: str = "host"):
     """load_frames_from_images (extract_mesh.py:72-82) on the GPU.  paths_or_dir: a frame folder (its *.jpg files in
-    sorted order; its *.png files when it has no *.jpg) or a list of JPEG paths, or of PNG paths.
+    sorted order; its *.png files when it has no *.jpg), a list of JPEG paths, or of PNG paths, or the path of an
+    animated GIF, whose frames are the video's frames.
     Returns (frames, kept): uint8 [F', H, W, 3] RGB on `device` (default: the
     current GPU when there is one, else the CPU) and the indices of the frames that decoded.  A frame that fails to
     decode is dropped with a log message, as the reference drops a None from cv2.imread; an unsupported kind of JPEG

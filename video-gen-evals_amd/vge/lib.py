@@ -54,6 +54,8 @@ EXPORTS = ["vge_featurize", "vge_featurize_layout", "vge_layout_feat_dim", "vge_
            "vge_jpeg_entropy_decode_tile_bytes",
            "vge_png_probe", "vge_png_probe_mem", "vge_png_decode", "vge_png_decode_mem", "vge_png_plan_mem",
            "vge_png_decode_device", "vge_png_decode_device_workspace_bytes", "vge_png_decode_device_band_rows",
+           "vge_gif_probe", "vge_gif_probe_mem", "vge_gif_decode", "vge_gif_decode_mem", "vge_gif_plan_mem",
+           "vge_gif_decode_device", "vge_gif_decode_device_workspace_bytes",
            "vge_time_gather", "vge_tcl_workspace_bytes", "vge_tcl_loss", "vge_hardneg_loss", "vge_centroid_distance"]
 
 
@@ -129,6 +131,27 @@ class PngSegment(C.Structure):  # include/vge_png.h vge_png_segment
 PNG_STATUS = {0: "OK", 1: "ERR_ARG", 2: "ERR_HIP", 7: "ERR_IO", 8: "ERR_SHAPE", 30: "ERR_INTERLACED",
               31: "ERR_BITDEPTH", 32: "ERR_PALETTE"}
 PNG_UNSUPPORTED = {30: "interlaced", 31: "not 8 bits per sample", 32: "palette"}
+
+
+class GifInfo(C.Structure):  # include/vge_gif.h vge_gif_info
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("n_frames", C.c_int32), ("status", C.c_int32),
+                ("lzw_bytes", C.c_int64), ("n_blocks", C.c_int64)]
+
+
+class GifDesc(C.Structure):  # include/vge_gif.h vge_gif_desc
+    _fields_ = [("file_off", C.c_int64), ("file_bytes", C.c_int64), ("gat_off", C.c_int64), ("gat_bytes", C.c_int64),
+                ("slot_off", C.c_int64), ("ct_off", C.c_int64), ("ct_size", C.c_int32), ("file", C.c_int32),
+                ("index", C.c_int32), ("frame", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32),
+                ("h", C.c_int32), ("interlace", C.c_int32), ("min_code_size", C.c_int32), ("transparent", C.c_int32),
+                ("disposal", C.c_int32), ("fill_rgb", C.c_int32), ("first_rgb", C.c_int32),
+                ("plan_status", C.c_int32), ("reserved", C.c_int32)]
+
+
+GifSegment = PngSegment  # include/vge_gif.h vge_gif_segment: the same shape
+
+GIF_STATUS = {0: "OK", 1: "ERR_ARG", 2: "ERR_HIP", 7: "ERR_IO", 8: "ERR_SHAPE", 40: "ERR_NO_PALETTE",
+              41: "ERR_BOUNDS"}
+GIF_UNSUPPORTED = {40: "a frame without any colour table", 41: "a frame that reaches outside the logical screen"}
 
 
 class FrameStoreC(C.Structure):
@@ -222,6 +245,15 @@ def load() -> C.CDLL:
                                   vp],
         "vge_png_decode_device_workspace_bytes": [C.POINTER(PngDesc), i32],
         "vge_png_decode_device_band_rows": [],
+        "vge_gif_probe": [C.POINTER(C.c_char_p), i32, i32, C.POINTER(GifInfo)],
+        "vge_gif_probe_mem": [vp, C.c_int64, vp, vp, i32, i32, C.POINTER(GifInfo)],
+        "vge_gif_decode": [C.POINTER(C.c_char_p), i32, i32, i32, i32, C.c_int64, vp, vp, vp, i64p],
+        "vge_gif_decode_mem": [vp, C.c_int64, vp, vp, i32, i32, i32, i32, C.c_int64, vp, vp, vp, i64p],
+        "vge_gif_plan_mem": [vp, C.c_int64, vp, vp, i32, i32, i32, i32, C.POINTER(GifDesc), C.c_int64, i64p,
+                             C.POINTER(GifSegment), C.c_int64, i64p, vp, vp, i64p],
+        "vge_gif_decode_device": [vp, C.c_int64, vp, i32, vp, C.c_int64, i32, i32, i32, i32, vp, C.c_int64, vp, vp,
+                                  vp],
+        "vge_gif_decode_device_workspace_bytes": [C.POINTER(GifDesc), i32],
         "vge_time_gather": [vp, vp, i32, i32, i32, vp, vp],
         "vge_tcl_workspace_bytes": [i32],
         "vge_tcl_loss": [vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, vp, C.c_size_t, vp, vp],
@@ -238,6 +270,7 @@ def load() -> C.CDLL:
     lib.vge_jpeg_entropy_decode_workspace_bytes.restype = C.c_size_t
     lib.vge_ingest_decode_device_workspace_bytes.restype = C.c_size_t
     lib.vge_png_decode_device_workspace_bytes.restype = C.c_size_t
+    lib.vge_gif_decode_device_workspace_bytes.restype = C.c_size_t
     lib.vge_last_error.restype = C.c_char_p
     lib.vge_version.restype = C.c_char_p
     _lib = lib
