@@ -1,7 +1,7 @@
 """Frames per second of vge.frames.load_frames on JPEG frame folders, split into its stages, beside Pillow.
 
     python tools/bench_frames.py [--frames 1024] [--size 256] [--quality 95] [--threads 16] [--folder DIR]
-                                 [--entropy host|device] [--format jpg|png|gif] [--out profiles/jpeg_decode.json]
+                                 [--entropy host|device] [--format jpg|png|gif|webp] [--out profiles/jpeg_decode.json]
 
 Writes its own JPEGs with Pillow (vge.synth.make_frames content, 4:2:0, quality 95: what cv2.imwrite writes) into a
 temporary folder, or reads the *.jpg files of --folder (cycled up to --frames).  Needs a GPU: there is no fallback.
@@ -39,6 +39,16 @@ diffusers' export_to_gif does, a local colour table per frame), and both routes 
   device_call     vge_gif_decode_device: gather + LZW + compose                          (device events)
   *_kernel        each of the three kernels alone                                        (device events)
   e2e_host / e2e_device      load_videos(files, device, entropy=...) ending in a device synchronise   (host clock)
+
+With --format webp (written to profiles/webp_decode_device.json unless --out says otherwise) the same frames are
+written as lossless animated WebP by Pillow (save_all=True, lossless=True), --gif-files files, and both routes are
+measured:
+  host_decode     vge_webp_decode on --threads host threads into pinned memory           (host clock)
+  plan            vge_webp_plan_mem over the files in memory                             (host clock)
+  device_call     vge_webp_decode_device: entropy + transforms + compose                 (device events)
+  entropy_kernel, entropy_transforms, compose_kernel   the first kernel, the first two, the last alone   (device events)
+  e2e_host / e2e_device      load_videos(files, device, entropy=...) ending in a device synchronise   (host clock)
+The report also holds the largest number of prefix-code groups a frame asked for, beside the arena's capacity.
 """
 from __future__ import annotations
 
@@ -360,6 +370,149 @@ def bench_gif(args) -> int:
     return 0
 
 
+def write_webps(folder: Path, n_files: int, per_file: int, size: int):
+    """vge.synth.make_frames content as Pillow writes lossless animated WebP (save_all=True, lossless=True: what
+    ComfyUI's SaveAnimatedWEBP node calls with its defaults)."""
+    from PIL import Image
+    from vge import synth
+    paths = []
+    for v in range(n_files):
+        fr = synth.make_frames(1000 + v, per_file, h=size, w=size)
+        ims = [Image.fromarray(fr[f]) for f in range(per_file)]
+        p = folder / f"clip_{v:04d}.webp"
+        ims[0].save(p, format="WEBP", save_all=True, append_images=ims[1:], lossless=True, duration=100, loop=0)
+        paths.append(str(p))
+    return paths
+
+
+def bench_webp(args) -> int:
+    """--format webp: both routes of load_videos on lossless animated WebP and the device call's kernels one by one."""
+    import torch
+    from vge import frames as FR
+    from vge import lib as L
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_frames.py needs a GPU")
+    dev = torch.device("cuda:0")
+    lib = L.load()
+    tmp = tempfile.TemporaryDirectory()
+    n_files = args.gif_files
+    per_file = max(1, args.frames // n_files)
+    paths = write_webps(Path(tmp.name), n_files, per_file, args.size)
+    rows = FR.webp_probe(paths, args.threads)
+    assert not rows[:, -1].any()
+    n = int(rows[:, 2].sum())
+    w, h = int(rows[0, 0]), int(rows[0, 1])
+
+    def e2e(entropy):
+        t = time.perf_counter()
+        out = FR.load_videos(paths, device=dev, threads=args.threads, entropy=entropy)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t
+        assert sum(k.size for _, k in out) == n
+        return dt, torch.cat([f for f, _ in out])
+
+    out_h = torch.empty((n, h, w, 3), dtype=torch.uint8, pin_memory=True)
+    status = np.zeros(n, np.int32)
+    arr = (C.c_char_p * n_files)(*[os.fsencode(p) for p in paths])
+
+    def host_decode():
+        t = time.perf_counter()
+        rc = lib.vge_webp_decode(arr, n_files, args.threads, w, h, n, out_h.data_ptr(), status.ctypes.data, None, None)
+        dt = time.perf_counter() - t
+        assert rc == 0, lib.vge_last_error()
+        return dt
+
+    raw, raw_off, raw_size = FR._read_files(paths, args.threads, pin=True)
+    raw_d = raw.to(dev)
+    descs = (L.WebpDesc * n)()
+    n_descs, ws_bytes = C.c_int64(0), C.c_int64(0)
+
+    def plan():
+        t = time.perf_counter()
+        rc = lib.vge_webp_plan_mem(raw.data_ptr(), int(raw.numel()), raw_off.ctypes.data, raw_size.ctypes.data, n_files,
+                                   args.threads, w, h, descs, n, C.byref(n_descs), None, None, C.byref(ws_bytes))
+        dt = time.perf_counter() - t
+        assert rc == 0 and n_descs.value == n, lib.vge_last_error()
+        return dt
+
+    plan()
+    # the largest number of prefix-code groups any frame asks for (the table arena holds VGE_WEBP_MAX_GROUPS)
+    feats = lib.vge_debug_webp_features
+    feats.argtypes, feats.restype = [C.c_void_p, C.c_int64, C.c_void_p], C.c_int
+    most_groups, word = 0, np.zeros(4, np.uint64)
+    for i in range(n_files):
+        assert feats(raw.data_ptr() + int(raw_off[i]), int(raw_size[i]), word.ctypes.data) == 0
+        most_groups = max(most_groups, int(word[3]))
+    descs_d = torch.frombuffer(descs, dtype=torch.uint8).to(dev)
+    ws = torch.empty(int(ws_bytes.value), dtype=torch.uint8, device=dev)
+    status_d = torch.empty(n, dtype=torch.int32, device=dev)
+    out_d = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev)
+
+    def device_call():
+        L.check(lib.vge_webp_decode_device(raw_d.data_ptr(), int(raw_d.numel()), descs_d.data_ptr(), n, n, n_files, w, h,
+                                           ws.data_ptr(), int(ws.numel()), out_d.data_ptr(), status_d.data_ptr(),
+                                           stream.cuda_stream), "vge_webp_decode_device")
+
+    def events(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b) * 1e-3
+
+    def stage(mask):   # one kernel of the call alone (a hook of the library for this tool), on the data the others left
+        lib.vge_debug_webp_stage_mask(mask)
+        try:
+            return events(device_call)
+        finally:
+            lib.vge_debug_webp_stage_mask(7)
+
+    res = {}
+    for _ in range(args.warmup):
+        host_decode(); events(device_call); e2e("host"); e2e("device")
+    res["host_decode_s"] = spread([host_decode() for _ in range(args.repeats)])
+    res["plan_s"] = spread([plan() for _ in range(args.repeats)])
+    res["device_call_s"] = spread([events(device_call) for _ in range(args.repeats)])
+    assert int(status_d.abs().sum()) == 0
+    calls_equal = bool(torch.equal(out_d.cpu(), out_h))
+    # entropy alone rewrites the coded planes; the transforms then run on fresh input once more before compose is timed
+    res["entropy_kernel_s"] = spread([stage(1) for _ in range(args.repeats)])
+    res["entropy_transforms_s"] = spread([stage(3) for _ in range(args.repeats)])
+    res["compose_kernel_s"] = spread([stage(4) for _ in range(args.repeats)])
+    eh = [e2e("host") for _ in range(args.repeats)]
+    ed = [e2e("device") for _ in range(args.repeats)]
+    res["e2e_host_s"] = spread([t for t, _ in eh])
+    res["e2e_device_s"] = spread([t for t, _ in ed])
+    report = {
+        "what": "vge.frames.load_videos on lossless animated WebP, both routes, measured on the GPU by "
+                "tools/bench_frames.py --format webp",
+        "device": torch.cuda.get_device_name(0), "files": n_files, "frames": n, "width": w, "height": h,
+        "threads": args.threads,
+        "source": f"written here by Pillow: vge.synth.make_frames {args.size}x{args.size}, RGB frames, save_all, "
+                  "lossless",
+        "webp_bytes_per_frame": float(raw_size.sum()) / n,
+        "workspace_bytes_per_frame": int(ws_bytes.value) / n,
+        "group_capacity": L.WEBP_MAX_GROUPS, "most_groups_in_a_frame": most_groups,
+        "entropy_kernel": "one wave per frame, the stream walked by one lane (the shared decoder of "
+                          "csrc/vge_webp_vp8l.h); transforms and compose are parallel",
+        "stages": res,
+        "ms_per_pass": {key[:-2]: 1e3 * v["median"] for key, v in res.items()},
+        "frames_per_s": {key[:-2]: n / v["median"] for key, v in res.items()},
+        "yardstick_host_decode_ms": 1e3 * res["host_decode_s"]["median"],
+        "device_call_ms": 1e3 * res["device_call_s"]["median"],
+        "entropy_share_of_device_call": res["entropy_kernel_s"]["median"] / res["device_call_s"]["median"],
+        "device_equals_host": calls_equal and bool(torch.equal(ed[-1][1], eh[-1][1])),
+    }
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(report, f, indent=1)
+    print(json.dumps(report))
+    tmp.cleanup()
+    return 0
+
+
 def _idat(data: bytes):
     """(offset, length) of a PNG file's IDAT payloads."""
     at, out = 8, []
@@ -373,8 +526,9 @@ def _idat(data: bytes):
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--format", choices=("jpg", "png", "gif"), default="jpg")
-    ap.add_argument("--gif-files", type=int, default=32, help="--format gif: files the frames are spread over")
+    ap.add_argument("--format", choices=("jpg", "png", "gif", "webp"), default="jpg")
+    ap.add_argument("--gif-files", type=int, default=32,
+                    help="--format gif / webp: files the frames are spread over")
     ap.add_argument("--frames", type=int, default=1024)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--quality", type=int, default=95)
@@ -394,6 +548,10 @@ def main(argv=None) -> int:
         if args.out is None:
             args.out = str(REPO / "profiles" / "gif_decode_device.json")
         return bench_gif(args)
+    if args.format == "webp":
+        if args.out is None:
+            args.out = str(REPO / "profiles" / "webp_decode_device.json")
+        return bench_webp(args)
     if args.out is None:
         args.out = str(REPO / "profiles" / ("jpeg_decode.json" if args.entropy == "host" else "jpeg_decode_device.json"))
 

@@ -323,7 +323,8 @@ def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root
     frame_format "gif" reads videos that are one animated GIF each, <frames_root>/<action>/<video>.gif (the video name
     is the stem): the frames are the GIF's composed frames (include/vge_gif.h), frame_idx indexes them, pass packing
     uses the probe's frame counts and jpeg_quality applies as for PNG.  A GIF's frames from the first undecodable one
-    onward are dropped (they are deltas on it).
+    onward are dropped (they are deltas on it).  frame_format "webp" reads <action>/<video>.webp, one lossless WebP
+    file per video (include/vge_webp.h), in exactly the same way.
 
     Per action, <log_root>/single/<action>.json and not_single/<action>.json (lists of video names) and
     errors/<action>.json ({video: message}) are rewritten after every video.  A video already in the single or
@@ -342,10 +343,11 @@ def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root
     (vge.frames.load_frames).
     Returns {action: {"single": [...], "not_single": [...], "errors": [...], "skipped": [...]}} for this run."""
     from . import frames as FR
-    if frame_format not in ("jpg", "png", "gif"):
-        raise ValueError(f"frame_format must be 'jpg', 'png' or 'gif', not {frame_format!r}")
+    if frame_format not in ("jpg", "png", "gif", "webp"):
+        raise ValueError(f"frame_format must be 'jpg', 'png', 'gif' or 'webp', not {frame_format!r}")
     ext = "." + frame_format
-    is_gif = frame_format == "gif"
+    is_gif = frame_format in ("gif", "webp")   # a video is one file
+    probe_file = FR.webp_probe if frame_format == "webp" else FR.gif_probe
     frames_root, log_root = Path(frames_root), Path(log_root)
     all_actions = sorted(d.name for d in frames_root.iterdir() if d.is_dir())
     if actions is None:
@@ -404,13 +406,13 @@ def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root
                 continue
             todo.append((video, str(source(video)) if is_gif else FR.list_frames(action_dir / video, ext=ext)))
         if is_gif:   # a video is one file: the probe gives its frame count
-            counts = FR.gif_probe([p for _, p in todo], threads)[:, 2] if todo else []
+            counts = probe_file([p for _, p in todo], threads)[:, 2] if todo else []
             entries = []
             for (v, p), n in zip(todo, counts):
                 if int(n) > 0:
                     entries.append((v, p, int(n)))
                 else:
-                    fail(v, f"no decodable frame in {p}: not a GIF, truncated, or without an image")
+                    fail(v, f"no decodable frame in {p}: not a {frame_format.upper()}, truncated, or without an image")
         else:
             entries = [(v, paths, len(paths)) for v, paths in todo]
         for group in _pack_passes(entries, max_frames):
@@ -505,8 +507,9 @@ def main(argv=None) -> int:
     ap.add_argument("--threads", type=int, default=0, help="frame decode threads (0: the ingest default)")
     ap.add_argument("--entropy", choices=("host", "device"), default="host",
                     help="where the frames' Huffman decoding (PNG: inflate and unfilter) runs (vge.frames.load_frames)")
-    ap.add_argument("--frame-format", choices=("jpg", "png", "gif"), default="jpg",
-                    help="the frame files each video folder holds; gif: each video is one animated <video>.gif")
+    ap.add_argument("--frame-format", choices=("jpg", "png", "gif", "webp"), default="jpg",
+                    help="the frame files each video folder holds; gif / webp: each video is one animated <video>.gif "
+                         "or lossless <video>.webp")
     ap.add_argument("--jpeg-quality", type=int, default=None,
                     help="send the decoded frames through a JPEG round trip of this quality before the models "
                          "(the reference's cache is 95; meant for PNG frames)")

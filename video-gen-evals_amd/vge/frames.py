@@ -24,6 +24,10 @@ An animated GIF (include/vge_gif.h) is a video in one file: load_frames("clip.gi
 PIL.ImageSequence gives after .convert("RGB").  entropy "host" is vge_gif_decode on host threads, entropy "device"
 vge_gif_plan_mem and vge_gif_decode_device (csrc/vge_gif.hip) on the uploaded file bytes; decode_gifs takes files
 packed in host memory.
+
+A lossless WebP file (include/vge_webp.h) is a video in one file in the same way (load_frames("clip.webp"),
+decode_webps; vge_webp_decode on host threads, or vge_webp_plan_mem and vge_webp_decode_device, csrc/vge_webp.hip, on
+the uploaded file bytes), and a folder or list of still .webp files is a video of one frame per file.
 """
 from __future__ import annotations
 
@@ -50,6 +54,12 @@ class UnsupportedJpegError(L.VgeError):
 class UnsupportedPngError(L.VgeError):
     """A PNG of a kind the decoders are not built for (interlaced, not 8 bits per sample, palette); the message names
     the kind and the file."""
+
+
+class UnsupportedWebpError(L.VgeError):
+    """A WebP the decoders refuse by name (a lossy VP8 / ALPH frame, a frame outside the canvas or of another size
+    than its VP8L header, more prefix-code groups than the table arena holds); the message names the kind and the
+    file."""
 
 
 class UnsupportedGifError(L.VgeError):
@@ -496,6 +506,217 @@ def decode_gifs(data, offsets, device=None, threads: int = 0, entropy: Optional[
     return _decode_gif_files(names, None, data, starts, sizes, info, device, threads, entropy)
 
 
+# ---- lossless WebP videos and frames (include/vge_webp.h)
+
+def _webp_rows(info, n: int) -> np.ndarray:
+    return np.array([[i.width, i.height, i.n_frames, i.vp8l_bytes, i.n_chunks, i.status] for i in info[:n]],
+                    dtype=np.int64).reshape(-1, 6)
+
+
+def webp_probe(paths: Sequence[PathLike], threads: int = 0) -> np.ndarray:
+    """Headers and chunk structure only: int64 [n, 6] rows of (canvas width, canvas height, frames, VP8L payload
+    bytes, chunks, status) (vge_webp_probe)."""
+    paths = [os.fspath(p) for p in paths]
+    info = (L.WebpInfo * max(len(paths), 1))()
+    if paths:
+        L.load().vge_webp_probe(_paths_array(paths), len(paths), int(threads), info)
+    return _webp_rows(info, len(paths))
+
+
+def webp_probe_mem(data: np.ndarray, offsets: np.ndarray, sizes: np.ndarray, threads: int = 0) -> np.ndarray:
+    """webp_probe() for files in host memory: file i is data[offsets[i]:offsets[i] + sizes[i]] (vge_webp_probe_mem)."""
+    n = len(offsets)
+    info = (L.WebpInfo * max(n, 1))()
+    if n:
+        offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
+        L.load().vge_webp_probe_mem(data.ctypes.data, data.size, offsets.ctypes.data, sizes.ctypes.data, n,
+                                    int(threads), info)
+    return _webp_rows(info, n)
+
+
+def _raise_unsupported_webp(names, statuses) -> None:
+    for p, s in zip(names, statuses):
+        if int(s) in L.WEBP_UNSUPPORTED:
+            raise UnsupportedWebpError(
+                f"{p}: unsupported WebP: {L.WEBP_UNSUPPORTED[int(s)]} ({L.WEBP_STATUS[int(s)]})")
+
+
+def _webp_decode_group(paths, data, offsets, sizes, canvas, n_frames: int, device, threads: int):
+    """The WebP files of one canvas on host threads, from paths or (paths None) from files in host memory (data: a
+    uint8 CPU tensor) -> (uint8 [n_frames, H, W, 3] tensor on `device`, int32 status [n_frames]): vge_webp_decode /
+    vge_webp_decode_mem into pinned memory, then one upload.  n_frames: the probe's sum."""
+    import torch
+    lib = L.load()
+    w, h = canvas
+    on_gpu = device.type == "cuda"
+    out = torch.empty((n_frames, h, w, 3), dtype=torch.uint8, pin_memory=on_gpu)
+    status = np.zeros(n_frames, np.int32)
+    if paths is not None:
+        lib.vge_webp_decode(_paths_array(paths), len(paths), int(threads), w, h, n_frames, out.data_ptr(),
+                            status.ctypes.data, None, None)
+    else:
+        offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
+        lib.vge_webp_decode_mem(data.data_ptr(), int(data.numel()), offsets.ctypes.data, sizes.ctypes.data,
+                                len(offsets), int(threads), w, h, n_frames, out.data_ptr(), status.ctypes.data, None,
+                                None)
+    if on_gpu:
+        with torch.cuda.device(device):
+            out = out.to(device, non_blocking=True)
+    return out, status
+
+
+def _webp_decode_group_device(data_h: np.ndarray, data_d, offsets: np.ndarray, sizes: np.ndarray, canvas,
+                              n_frames: int, threads: int):
+    """The WebP files of one canvas, their bytes both in host memory (data_h, which only the plan's chunk walk reads)
+    and on the GPU (data_d) -> (uint8 [n_frames, H, W, 3] tensor on that GPU, int32 status [n_frames]):
+    vge_webp_plan_mem on the host, one upload of the descriptors, vge_webp_decode_device on the current stream; the
+    one host synchronisation is the copy of the statuses at the end.  n_frames: the probe's sum."""
+    import torch
+    lib = L.load()
+    dev = data_d.device
+    w, h = canvas
+    offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
+    descs = (L.WebpDesc * max(n_frames, 1))()
+    planned = np.zeros(max(n_frames, 1), np.int32)
+    n_descs, ws_bytes = C.c_int64(0), C.c_int64(0)
+    lib.vge_webp_plan_mem(data_h.ctypes.data, data_h.size, offsets.ctypes.data, sizes.ctypes.data, len(offsets),
+                          int(threads), w, h, descs, n_frames, C.byref(n_descs), planned.ctypes.data, None,
+                          C.byref(ws_bytes))
+    if n_descs.value != n_frames:
+        raise L.VgeError("vge_webp_plan_mem: " + lib.vge_last_error().decode(errors="replace"))
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        descs_d = torch.frombuffer(descs, dtype=torch.uint8).to(dev)
+        ws = torch.empty(int(ws_bytes.value), dtype=torch.uint8, device=dev)
+        status_d = torch.empty(n_frames, dtype=torch.int32, device=dev)
+        out = torch.empty((n_frames, h, w, 3), dtype=torch.uint8, device=dev)
+        L.check(lib.vge_webp_decode_device(data_d.data_ptr(), int(data_d.numel()), descs_d.data_ptr(), n_frames,
+                                           n_frames, len(offsets), w, h, ws.data_ptr(), int(ws.numel()),
+                                           out.data_ptr(), status_d.data_ptr(), stream.cuda_stream),
+                "vge_webp_decode_device")
+        status = status_d.cpu().numpy()
+    planned = planned[:n_frames]
+    return out, np.where(planned != 0, planned, status).astype(np.int32)
+
+
+def _keep_webp_frames(name, out, status, device):
+    """(frames, kept) of one WebP video: the frames in front of the first one that failed."""
+    bad = np.flatnonzero(status != 0)
+    n = int(bad[0]) if bad.size else len(status)
+    if bad.size:
+        if int(status[n]) in L.WEBP_UNSUPPORTED:   # what only the decoders see: the group capacity
+            _raise_unsupported_webp([name], [status[n]])
+        log.warning("dropping frames %d.. of %s: %s", n, name, L.WEBP_STATUS.get(int(status[n]), int(status[n])))
+    return out[:n], np.arange(n, dtype=np.int64)
+
+
+def _decode_webp_files(names, paths, raw, raw_off, raw_size, info, device, threads: int, entropy: str):
+    """The WebP files of a call, from paths (host route) or from their bytes in one host tensor `raw` -> one
+    (frames, kept) per file.  info: their probe rows.  Files of one canvas share one call."""
+    import torch
+    _raise_unsupported_webp(names, info[:, 5])
+    results: List[Optional[Tuple]] = [None] * len(names)
+    groups: dict = {}
+    for i, row in enumerate(info):
+        if int(row[2]) > 0 and int(row[5]) != 1 and int(row[0]) > 0 and int(row[1]) > 0:
+            groups.setdefault((int(row[0]), int(row[1])), []).append(i)
+        else:
+            log.warning("no decodable frame in %s: %s", names[i], L.WEBP_STATUS.get(int(row[5]), int(row[5])))
+            results[i] = _empty_video(device)
+    raw_d = None
+    if entropy == "device" and groups:
+        with torch.cuda.device(device):
+            raw_d = raw.to(device, non_blocking=True)   # the one upload: every group decodes out of this buffer
+    for canvas, members in groups.items():
+        counts = [int(info[i, 2]) for i in members]
+        total = sum(counts)
+        if entropy == "device":
+            with torch.cuda.device(device):
+                out, status = _webp_decode_group_device(raw.numpy(), raw_d, raw_off[members], raw_size[members],
+                                                        canvas, total, threads)
+        elif paths is not None:
+            out, status = _webp_decode_group([paths[i] for i in members], None, None, None, canvas, total, device,
+                                             threads)
+        else:
+            out, status = _webp_decode_group(None, raw, raw_off[members], raw_size[members], canvas, total, device,
+                                             threads)
+        o = 0
+        for i, n in zip(members, counts):
+            results[i] = _keep_webp_frames(names[i], out[o:o + n], status[o:o + n], device)
+            if results[i][1].size == 0:
+                log.warning("no decodable frame in %s", names[i])
+            o += n
+    return results
+
+
+def _load_webp_files(paths: List[str], device, threads: int, entropy: str):
+    """One (frames, kept) per WebP file of a call."""
+    if entropy == "device":
+        raw, raw_off, raw_size = _read_files(paths, threads, pin=True)
+        info = webp_probe_mem(raw.numpy(), raw_off, raw_size, threads)
+        return _decode_webp_files(paths, None, raw, raw_off, raw_size, info, device, threads, entropy)
+    return _decode_webp_files(paths, paths, None, None, None, webp_probe(paths, threads), device, threads, entropy)
+
+
+def _load_webp_still_videos(vids: List[List[str]], device, threads: int, entropy: str):
+    """load_videos for the videos that are folders or lists of still WebP frames: every file is one frame, and all
+    frames of a video have one size (a file of another size is refused with a ValueError that names it)."""
+    import torch
+    flat = [p for v in vids for p in v]
+    per_file = _load_webp_files(flat, device, threads, entropy)
+    results, o = [], 0
+    for v in vids:
+        frames, kept, size = [], [], None
+        for k, p in enumerate(v):
+            fr = per_file[o + k][0]
+            if fr.shape[0] != 1:
+                log.warning("dropping frame %s: %s", p, "unreadable" if fr.shape[0] == 0 else "an animation")
+                continue
+            if size is not None and tuple(fr.shape[1:3]) != size:
+                raise ValueError(f"{p}: a frame of {fr.shape[2]} x {fr.shape[1]} in a video of {size[1]} x {size[0]}: "
+                                 "the still WebP frames of one video must have one size")
+            size = tuple(fr.shape[1:3])
+            frames.append(fr)
+            kept.append(k)
+        o += len(v)
+        results.append((torch.cat(frames), np.asarray(kept, np.int64)) if frames else _empty_video(device))
+    return results
+
+
+def decode_webps(data, offsets, device=None, threads: int = 0, entropy: Optional[str] = None):
+    """WebP files packed in host memory -- (data, offsets[F + 1]): file i at data[offsets[i]:offsets[i + 1]] of a
+    one-dimensional uint8 CPU tensor -- -> one (frames, kept) per file, as load_videos gives them.  entropy "host" (the
+    default without a GPU) decodes on host threads (vge_webp_decode_mem) and uploads the pixels to `device`; entropy
+    "device" (the default with one) uploads the file bytes and runs vge_webp_plan_mem and vge_webp_decode_device.  The
+    plan walks every chunk of every file on the host, so a buffer that lives on a GPU is refused, not copied back."""
+    import torch
+    if not (isinstance(data, torch.Tensor) and data.dtype == torch.uint8 and data.dim() == 1):
+        raise ValueError("data must be a one-dimensional uint8 tensor")
+    if data.device.type != "cpu":
+        raise ValueError("decode_webps needs the file bytes in host memory: the plan walks every chunk on the host; "
+                         "pass a CPU tensor (entropy='device' uploads it once)")
+    off = np.ascontiguousarray(offsets.cpu().numpy() if isinstance(offsets, torch.Tensor) else offsets, np.int64)
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError("offsets must be int64 [F + 1]")
+    device = _resolve_device(device)
+    if entropy is None:
+        entropy = "device" if device.type == "cuda" else "host"
+    if entropy not in ("host", "device"):
+        raise ValueError(f"entropy must be 'host' or 'device', not {entropy!r}")
+    if entropy == "device" and device.type != "cuda":
+        raise ValueError("entropy='device' needs a GPU")
+    F = off.size - 1
+    if F == 0:
+        return []
+    starts, sizes = off[:F].copy(), np.diff(off)
+    if (sizes < 0).any() or off[0] < 0 or off[F] > data.numel():
+        raise ValueError("offsets must be non-decreasing and inside data")
+    data = data.contiguous()
+    names = [f"file {i}" for i in range(F)]
+    info = webp_probe_mem(data.numpy(), starts, sizes, threads)
+    return _decode_webp_files(names, None, data, starts, sizes, info, device, threads, entropy)
+
+
 def _first_good_key(rows: np.ndarray, n_key: int):
     """The layout of a video: its first readable frame's leading probe columns (the last column is the status)."""
     good = np.flatnonzero(rows[:, -1] == 0)
@@ -833,23 +1054,41 @@ def load_videos(videos: Sequence[Union[PathLike, Sequence[PathLike]]], device=No
     share one call: entropy "host" decodes on host threads into pinned memory and uploads the pixels (vge_gif_decode);
     entropy "device" uploads the file bytes once and runs vge_gif_plan_mem and vge_gif_decode_device.  A frame that
     does not decode is dropped with every later frame of its file (they are deltas on it), with a log line;
-    UnsupportedGifError names a file with a frame that has no colour table or that overflows the logical screen."""
+    UnsupportedGifError names a file with a frame that has no colour table or that overflows the logical screen.
+    An entry that is a path to a regular file with the RIFF....WEBP signature is a lossless WebP video
+    (include/vge_webp.h), handled as a GIF video is: vge_webp_decode on host threads, or vge_webp_plan_mem and
+    vge_webp_decode_device on the uploaded file bytes.  A folder without *.jpg and *.png files gives its *.webp files,
+    and a list whose first file is a WebP is a list of still WebP frames: every file is one frame, and all must have
+    one size.  UnsupportedWebpError names a file with a lossy frame, a frame outside its canvas or more prefix-code
+    groups than the decoders hold."""
     device = _resolve_device(device)
     if entropy not in ("host", "device"):
         raise ValueError(f"entropy must be 'host' or 'device', not {entropy!r}")
     if entropy == "device" and device.type != "cuda":
         raise ValueError("entropy='device' needs a GPU")
-    is_gif = [isinstance(v, (str, os.PathLike)) and _is_gif_file(os.fspath(v)) for v in videos]
-    vids = [[] if g else _list_video(v) if isinstance(v, (str, os.PathLike)) else [os.fspath(p) for p in v]
-            for v, g in zip(videos, is_gif)]
+    is_webp = [isinstance(v, (str, os.PathLike)) and _is_webp_file(os.fspath(v)) for v in videos]
+    is_gif = [isinstance(v, (str, os.PathLike)) and not wp and _is_gif_file(os.fspath(v))
+              for v, wp in zip(videos, is_webp)]
+    vids = [[] if g or wp else _list_video(v) if isinstance(v, (str, os.PathLike)) else [os.fspath(p) for p in v]
+            for v, g, wp in zip(videos, is_gif, is_webp)]
     is_png = [_is_png_file(v[0]) if v else False for v in vids]
+    is_stills = [bool(v) and _is_webp_file(v[0]) for v in vids]
     results: List[Optional[Tuple]] = [None] * len(vids)
     gifs = [vi for vi, g in enumerate(is_gif) if g]
     if gifs:
         for vi, r in zip(gifs, _load_gif_videos([os.fspath(videos[vi]) for vi in gifs], device, threads, entropy)):
             results[vi] = r
+    webps = [vi for vi, wp in enumerate(is_webp) if wp]
+    if webps:
+        for vi, r in zip(webps, _load_webp_files([os.fspath(videos[vi]) for vi in webps], device, threads, entropy)):
+            results[vi] = r
+    stills = [vi for vi, k in enumerate(is_stills) if k]
+    if stills:
+        for vi, r in zip(stills, _load_webp_still_videos([vids[vi] for vi in stills], device, threads, entropy)):
+            results[vi] = r
     for png, load in ((False, _load_jpeg_videos), (True, _load_png_videos)):
-        which = [vi for vi, k in enumerate(is_png) if k == png and not is_gif[vi]]
+        which = [vi for vi, k in enumerate(is_png)
+                 if k == png and not is_gif[vi] and not is_webp[vi] and not is_stills[vi]]
         if which:
             for vi, r in zip(which, load([vids[vi] for vi in which], device, threads, entropy)):
                 results[vi] = r
@@ -857,8 +1096,21 @@ def load_videos(videos: Sequence[Union[PathLike, Sequence[PathLike]]], device=No
 
 
 def _list_video(folder: PathLike) -> List[str]:
-    """A frame folder's files: its *.jpg, or when it has none its *.png, in sorted order."""
-    return list_frames(folder) or list_frames(folder, ext=".png")
+    """A frame folder's files: its *.jpg, or when it has none its *.png, or when it has neither its *.webp, in sorted
+    order."""
+    return list_frames(folder) or list_frames(folder, ext=".png") or list_frames(folder, ext=".webp")
+
+
+def _is_webp_file(path: str) -> bool:
+    """A path to a regular file that begins RIFF....WEBP: a WebP video or still."""
+    try:
+        if not os.path.isfile(path):
+            return False
+        with open(path, "rb") as f:
+            head = f.read(12)
+        return len(head) == 12 and head[:4] == b"RIFF" and head[8:] == b"WEBP"
+    except OSError:
+        return False
 
 
 def _is_gif_file(path: str) -> bool:
@@ -978,7 +1230,8 @@ def load_frames(paths_or_dir: Union[PathLike, Sequence[PathLike]], device=None, 
                 entropy: str = "host"):
     """load_frames_from_images (extract_mesh.py:72-82) on the GPU.  paths_or_dir: a frame folder (its *.jpg files in
     sorted order; its *.png files when it has no *.jpg), a list of JPEG paths, or of PNG paths, or the path of an
-    animated GIF, whose frames are the video's frames.
+    animated GIF or of a lossless WebP file, whose frames are the video's frames, or a folder or list of still WebP
+    frames.
     Returns (frames, kept): uint8 [F', H, W, 3] RGB on `device` (default: the
     current GPU when there is one, else the CPU) and the indices of the frames that decoded.  A frame that fails to
     decode is dropped with a log message, as the reference drops a None from cv2.imread; an unsupported kind of JPEG

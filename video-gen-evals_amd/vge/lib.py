@@ -56,6 +56,8 @@ EXPORTS = ["vge_featurize", "vge_featurize_layout", "vge_layout_feat_dim", "vge_
            "vge_png_decode_device", "vge_png_decode_device_workspace_bytes", "vge_png_decode_device_band_rows",
            "vge_gif_probe", "vge_gif_probe_mem", "vge_gif_decode", "vge_gif_decode_mem", "vge_gif_plan_mem",
            "vge_gif_decode_device", "vge_gif_decode_device_workspace_bytes",
+           "vge_webp_probe", "vge_webp_probe_mem", "vge_webp_decode", "vge_webp_decode_mem", "vge_webp_plan_mem",
+           "vge_webp_decode_device", "vge_webp_decode_device_workspace_bytes", "vge_webp_slot_bytes",
            "vge_time_gather", "vge_tcl_workspace_bytes", "vge_tcl_loss", "vge_hardneg_loss", "vge_centroid_distance"]
 
 
@@ -152,6 +154,26 @@ GifSegment = PngSegment  # include/vge_gif.h vge_gif_segment: the same shape
 GIF_STATUS = {0: "OK", 1: "ERR_ARG", 2: "ERR_HIP", 7: "ERR_IO", 8: "ERR_SHAPE", 40: "ERR_NO_PALETTE",
               41: "ERR_BOUNDS"}
 GIF_UNSUPPORTED = {40: "a frame without any colour table", 41: "a frame that reaches outside the logical screen"}
+
+
+class WebpInfo(C.Structure):  # include/vge_webp.h vge_webp_info
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("n_frames", C.c_int32), ("status", C.c_int32),
+                ("vp8l_bytes", C.c_int64), ("n_chunks", C.c_int64)]
+
+
+class WebpDesc(C.Structure):  # include/vge_webp.h vge_webp_desc
+    _fields_ = [("file_off", C.c_int64), ("file_bytes", C.c_int64), ("pay_off", C.c_int64), ("pay_bytes", C.c_int64),
+                ("slot_off", C.c_int64), ("file", C.c_int32), ("index", C.c_int32), ("frame", C.c_int32),
+                ("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("blend", C.c_int32),
+                ("dispose", C.c_int32), ("key", C.c_int32), ("plan_status", C.c_int32), ("reserved", C.c_int32)]
+
+
+WEBP_STATUS = {0: "OK", 1: "ERR_ARG", 2: "ERR_HIP", 7: "ERR_IO", 8: "ERR_SHAPE", 50: "ERR_LOSSY", 51: "ERR_BOUNDS",
+               52: "ERR_GROUPS"}
+WEBP_UNSUPPORTED = {50: "a lossy (VP8 / ALPH) frame",
+                    51: "a frame outside the canvas, or of another size than its VP8L header",
+                    52: "more prefix-code groups than the table arena holds"}
+WEBP_MAX_GROUPS = 256   # include/vge_webp.h VGE_WEBP_MAX_GROUPS
 
 
 class FrameStoreC(C.Structure):
@@ -254,6 +276,15 @@ def load() -> C.CDLL:
         "vge_gif_decode_device": [vp, C.c_int64, vp, i32, vp, C.c_int64, i32, i32, i32, i32, vp, C.c_int64, vp, vp,
                                   vp],
         "vge_gif_decode_device_workspace_bytes": [C.POINTER(GifDesc), i32],
+        "vge_webp_probe": [C.POINTER(C.c_char_p), i32, i32, C.POINTER(WebpInfo)],
+        "vge_webp_probe_mem": [vp, C.c_int64, vp, vp, i32, i32, C.POINTER(WebpInfo)],
+        "vge_webp_decode": [C.POINTER(C.c_char_p), i32, i32, i32, i32, C.c_int64, vp, vp, vp, i64p],
+        "vge_webp_decode_mem": [vp, C.c_int64, vp, vp, i32, i32, i32, i32, C.c_int64, vp, vp, vp, i64p],
+        "vge_webp_plan_mem": [vp, C.c_int64, vp, vp, i32, i32, i32, i32, C.POINTER(WebpDesc), C.c_int64, i64p, vp, vp,
+                              i64p],
+        "vge_webp_decode_device": [vp, C.c_int64, vp, i32, i32, i32, i32, i32, vp, C.c_int64, vp, vp, vp],
+        "vge_webp_decode_device_workspace_bytes": [C.POINTER(WebpDesc), i32],
+        "vge_webp_slot_bytes": [i32, i32],
         "vge_time_gather": [vp, vp, i32, i32, i32, vp, vp],
         "vge_tcl_workspace_bytes": [i32],
         "vge_tcl_loss": [vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, vp, C.c_size_t, vp, vp],
@@ -271,6 +302,8 @@ def load() -> C.CDLL:
     lib.vge_ingest_decode_device_workspace_bytes.restype = C.c_size_t
     lib.vge_png_decode_device_workspace_bytes.restype = C.c_size_t
     lib.vge_gif_decode_device_workspace_bytes.restype = C.c_size_t
+    lib.vge_webp_decode_device_workspace_bytes.restype = C.c_size_t
+    lib.vge_webp_slot_bytes.restype = C.c_int64
     lib.vge_last_error.restype = C.c_char_p
     lib.vge_version.restype = C.c_char_p
     _lib = lib
