@@ -26,6 +26,21 @@
  * vge_frcnn_shapes / vge_frcnn_reserve / vge_frcnn_detect before any launch: a frame whose short edge rounds to 0
  * pixels under the max_size cap (aspect ratio above ~2 max_size, e.g. 1 x 667 at max_size 333), and a chunk whose
  * row or thread counts would pass 2^31.
+ *
+ * The non-GEMM kernels are also pinned one at a time, through the vge_op_* entries at the end of this header, on
+ * crafted inputs (tests/test_frcnn_ops.py; the cases and the property each one carries: tests/frcnn_op_cases.py,
+ * checked under the oracle alone by tests/test_frcnn_op_cases.py):
+ *   vge_op_frcnn_preprocess   resized bytes == the oracle's PIL resample; the bf16 tensor bit for bit against
+ *                             bf16((v - mean) / std) in numpy float32, BGR, +0 in channels 3..7 and in the padding
+ *   vge_op_frcnn_pool_s2      == torch max_pool2d of the bf16 values (K 3 and 1, odd and even sizes)
+ *   vge_op_frcnn_stem_pool    float64 conv 7x7 / 2 + bias + ReLU, one bf16 rounding, max_pool2d(3, 2, 1): 2^-7 |ref| + 1e-4
+ *   vge_debug_gconv3          torch conv2d(groups) in f32, 2^-7 |ref| + 1e-4, at 1, 8, 9 and 17 images per call
+ *   vge_op_rpn_proposals      oracle proposals(): counts and scores bit-equal in order (ties at the top-k cut, across
+ *                             levels, IoU within 4 ulp of the threshold, NaN / inf logits and deltas, no valid box)
+ *   vge_op_roi_align          oracle box_features(): 2^-7 |ref| + max(1e-6, 2^-20 sum |w v| / count), the three kernels
+ *                             (vge_debug_set_roi_direct 0 / 1 / 2) at every level boundary, 13 / 14 samples per bin,
+ *                             samples outside the map, empty slots
+ *   vge_op_det_post           oracle inference() + postprocess(): counts, classes, order, persons equal; scores 2e-6
  */
 #ifndef VGE_FRCNN_H
 #define VGE_FRCNN_H
@@ -96,6 +111,44 @@ int vge_frcnn_detect(vge_frcnn* m, const uint8_t* frames, int n_frames, int H, i
  * (grouped convolutions counted at their grouped size). */
 int vge_frcnn_profile_begin(vge_frcnn* m, int max_calls);
 int vge_frcnn_profile_read(vge_frcnn* m, double* stage_ms, int* n_calls, double* flops_per_call);
+
+/* ---- The detector's non-GEMM kernels one at a time (tests, tools).  Each entry checks its arguments (VGE_ERR_ARG,
+ * vge_last_error names the entry and the rule, no GPU work) and then calls the launcher vge_frcnn_detect calls.
+ * Device pointers unless stated; an entry that packs weights, builds tables or needs scratch allocates them, runs on
+ * `stream` and waits for it before returning. */
+
+/* DefaultPredictor's preprocessing of n frames uint8 [n][H][W][3] RGB: resized (optional) uint8 [n][nh][nw][3], out
+ * bf16 [n][hp][wp][8] = (B, G, R) normalised, channels 3..7 and the padding +0; (nh, nw) = ResizeShortestEdge(min_size,
+ * max_size), (hp, wp) = those rounded up to 32 (vge_frcnn_shapes out[0..3]). */
+int vge_op_frcnn_preprocess(const uint8_t* frames, int n, int H, int W, int min_size, int max_size, uint8_t* resized,
+                            void* out, vge_stream_t stream);
+/* max_pool2d(K, stride 2, pad K / 2) of x bf16 [n][H][W][C] -> y [n][(H - 1) / 2 + 1][(W - 1) / 2 + 1][C]; K 3 (after
+ * the stem) or 1 (P6), C a multiple of 8. */
+int vge_op_frcnn_pool_s2(const void* x, void* y, int n, int H, int W, int C, int K, vge_stream_t stream);
+/* The fused stem: in bf16 [n][hp][wp][8], w HOST f32 [64][3][7][7] and b HOST f32 [64] (FrozenBN already folded;
+ * packed as vge_frcnn_create packs them) -> out bf16 [n][hp / 4][wp / 4][64]; hp, wp multiples of 32. */
+int vge_op_frcnn_stem_pool(const void* in, const float* w, const float* b, void* out, int n, int hp, int wp,
+                           vge_stream_t stream);
+/* find_top_rpn_proposals: levels = HOST array of 5 device pointers f32 [n][h_l][w_l][16] (vge_frcnn_taps.rpn), level_hw
+ * = HOST int [10] (h_0, w_0, ...); level l has stride 4 << l and anchors of size 32 << l.  -> props f32
+ * [n][post_topk][5], n_prop int32 [n].  Optional (NULL = internal): sel and kept f32 [n][5][1024][8] (per level: the
+ * top-k entries x1 y1 x2 y2 logit valid, in key order; the boxes NMS kept, x1 y1 x2 y2 logit), kcount int32 [n][5]. */
+int vge_op_rpn_proposals(const float* const* levels, const int* level_hw, int n, int pre_topk, int post_topk,
+                         float nms_thresh, int img_h, int img_w, float* props, int32_t* n_prop, float* sel, float* kept,
+                         int32_t* kcount, vge_stream_t stream);
+/* ROIPooler: levels = HOST array of 4 device pointers bf16 [n][h_l][w_l][256] (P2..P5), level_hw = HOST int [8];
+ * props f32 [n][P][5], n_prop int32 [n] (each <= P) -> out bf16 [n][P][49][256], slots from n_prop[f] on +0.  The
+ * kernel is the one vge_debug_set_roi_direct selects. */
+int vge_op_roi_align(const void* const* levels, const int* level_hw, const float* props, const int32_t* n_prop, int n,
+                     int P, void* out, vge_stream_t stream);
+/* FastRCNNOutputLayers.inference + detector_postprocess + the gate count: head f32 [n * P][ld] (logits K + 1 | deltas
+ * 4 K), props f32 [n][P][5], n_prop int32 [n] (each <= P); img = the resized image, out = the frame.  vge_frcnn_create's
+ * rules hold: score_thresh in [0.2, 1), K in [1, 127], det_per_img and P <= 1024.  Outputs as in vge_frcnn_taps
+ * (pre_dets, n_pre) and vge_frcnn_detect (dets, n_dets, person, n_person); all optional but n_person. */
+int vge_op_det_post(const float* head, int ld, int P, int K, int det_per_img, const float* props, const int32_t* n_prop,
+                    int n, int img_h, int img_w, int out_h, int out_w, float score_thresh, float nms_thresh,
+                    float gate_thresh, float* pre_dets, int32_t* n_pre, float* dets, int32_t* n_dets, float* person,
+                    int32_t* n_person, vge_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -19,11 +19,13 @@ so its published inference path is restated here:
                                  max_pool2d(P5, 1, 2)
   RPN                            StandardRPNHead (3x3 conv + ReLU, 1x1 objectness (3) and deltas (12)), anchors of
                                  sizes 32..512 x ratios (0.5, 1, 2), offset 0; per level top-1000 logits, decode
-                                 (weights 1, clamp log(1000/16)), clip, nonempty, batched_nms 0.7 over levels, top 1000
+                                 (weights 1, clamp log(1000/16)), finite boxes and logits only, clip, nonempty,
+                                 batched_nms 0.7 over levels, top 1000
   ROIPooler                      ROIAlignV2 7x7 (aligned, sampling_ratio 0 = adaptive), level = floor(4 + log2(sqrt(area)
                                  / 224 + 1e-8)) clamped to P2..P5
   FastRCNNConvFCHead / outputs   flatten -> fc1 1024 + ReLU -> fc2 1024 + ReLU -> cls_score (81) / bbox_pred (320);
-                                 softmax, per-class decode (10, 10, 5, 5), clip, score > 0.25, batched_nms 0.5, top 100
+                                 softmax, per-class decode (10, 10, 5, 5), rows with a non-finite box or probability
+                                 dropped, clip, score > 0.25, batched_nms 0.5, top 100
   detector_postprocess           boxes scaled to the input frame size, clipped, nonempty
 
 Conventions where the upstream result depends on the platform: ties between equal scores keep the lower index (stable
@@ -189,6 +191,19 @@ def nonempty(b: torch.Tensor, thr: float = 0.0) -> torch.Tensor:
     return ((b[:, 2] - b[:, 0]) > thr) & ((b[:, 3] - b[:, 1]) > thr)
 
 
+def pair_iou(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """torchvision devIoU of boxes a [..., 4] and b [..., 4] (broadcast), float32, every operation rounded on its own:
+    inter / ((area_a + area_b) - inter)."""
+    area_a = (a[..., 2] - a[..., 0]) * (a[..., 3] - a[..., 1])
+    area_b = (b[..., 2] - b[..., 0]) * (b[..., 3] - b[..., 1])
+    left = torch.maximum(a[..., 0], b[..., 0])
+    right = torch.minimum(a[..., 2], b[..., 2])
+    top = torch.maximum(a[..., 1], b[..., 1])
+    bottom = torch.minimum(a[..., 3], b[..., 3])
+    inter = torch.clamp(right - left, min=0) * torch.clamp(bottom - top, min=0)
+    return inter / ((area_a + area_b) - inter)
+
+
 def nms(boxes: torch.Tensor, scores: torch.Tensor, thr: float) -> torch.Tensor:
     """torchvision nms: stable descending sort, greedy suppression of later boxes with IoU > thr; kept indices in
     score order."""
@@ -197,14 +212,7 @@ def nms(boxes: torch.Tensor, scores: torch.Tensor, thr: float) -> torch.Tensor:
         return torch.zeros(0, dtype=torch.int64)
     order = torch.sort(scores, descending=True, stable=True)[1]
     b = boxes[order]
-    x1, y1, x2, y2 = b[:, 0], b[:, 1], b[:, 2], b[:, 3]
-    area = (x2 - x1) * (y2 - y1)
-    left = torch.maximum(x1[:, None], x1[None, :])
-    right = torch.minimum(x2[:, None], x2[None, :])
-    top = torch.maximum(y1[:, None], y1[None, :])
-    bottom = torch.minimum(y2[:, None], y2[None, :])
-    inter = torch.clamp(right - left, min=0) * torch.clamp(bottom - top, min=0)
-    iou = inter / ((area[:, None] + area[None, :]) - inter)
+    iou = pair_iou(b[:, None, :], b[None, :, :])
     sup = (iou > thr).numpy()
     removed = np.zeros(n, bool)
     keep = []
@@ -226,7 +234,9 @@ def batched_nms(boxes: torch.Tensor, scores: torch.Tensor, idxs: torch.Tensor, t
 
 
 def topk_stable(x: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
-    """The k largest values, ties by the lower index (libvge's rule; torch.topk leaves it unspecified)."""
+    """The k largest values, ties by the lower index (libvge's rule; torch.topk leaves it unspecified).  NaN orders as
+    torch.sort(descending=True, stable=True) orders it: every NaN (either sign, any payload) first, among themselves by
+    index; -0 and +0 are equal."""
     v, i = torch.sort(x, descending=True, stable=True)
     return v[:k], i[:k]
 
@@ -385,6 +395,9 @@ class OracleFrcnn:
             sc.append(v)
             lv.append(torch.full((k,), l, dtype=torch.int64))
         boxes, scores, lvl = torch.cat(bx), torch.cat(sc), torch.cat(lv)
+        # find_top_rpn_proposals' valid_mask: after the per-level top-k (a non-finite entry still took its slot)
+        fin = torch.isfinite(boxes).all(dim=1) & torch.isfinite(scores)
+        boxes, scores, lvl = boxes[fin], scores[fin], lvl[fin]
         boxes = clip_boxes(boxes, image_size[0], image_size[1])
         keep = nonempty(boxes)
         boxes, scores, lvl = boxes[keep], scores[keep], lvl[keep]
@@ -421,6 +434,9 @@ class OracleFrcnn:
         e = torch.exp(cls_logits - mx)
         probs = e / e.sum(dim=1, keepdim=True)
         boxes = apply_deltas(deltas, proposals, (10.0, 10.0, 5.0, 5.0))
+        # fast_rcnn_inference_single_image's valid_mask: rows whose K boxes and K + 1 probabilities are all finite
+        fin = torch.isfinite(boxes).all(dim=1) & torch.isfinite(probs).all(dim=1)
+        boxes, probs = boxes[fin], probs[fin]
         scores = probs[:, :-1]
         K = scores.shape[1]
         boxes = clip_boxes(boxes.reshape(-1, 4), image_size[0], image_size[1]).view(-1, K, 4)

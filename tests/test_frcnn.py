@@ -109,32 +109,61 @@ def test_grouped_conv_kernel_vs_torch(gw, stride, C, H, W):
     two MFMAs per tap).  The kernel rounds its f32 sums to bf16 once.  The output tile is picked per shape
     (gc_pick_tile): the detector's 200 / 100 / 50-wide maps at both strides take tiles whose 16-pixel groups run across
     rows (5 x 25, 6 x 10), the small shapes whole-image tiles, 51 x 47 a partial last group."""
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
+    _gconv_check(gw, stride, C, H, W, 2)
+
+
+def _gconv_run(x, w, b, gw, stride):
+    """vge_debug_gconv3 on x bf16 [n, H, W, C] (host) -> bf16 [n, Ho, Wo, C] (host), over a NaN pre-fill"""
     import ctypes as C_
-    import torch.nn.functional as F
     from vge import lib as L
     so = L.load()
-    g = torch.Generator().manual_seed(gw * 7 + stride)
-    x = torch.randn((2, H, W, C), generator=g).to(torch.bfloat16)
-    w = (torch.randn((C, gw, 3, 3), generator=g) / (3.0 * gw ** 0.5)).float()
-    b = (0.1 * torch.randn(C, generator=g)).float()
+    n, H, W, C = x.shape
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     xd = x.to(DEV)
-    out = torch.full((2, Ho, Wo, C), float("nan"), dtype=torch.bfloat16, device=DEV)
+    out = torch.full((n, Ho, Wo, C), float("nan"), dtype=torch.bfloat16, device=DEV)
     torch.cuda.synchronize()
     st = torch.cuda.current_stream().cuda_stream
-    rc = so.vge_debug_gconv3(C_.c_void_p(xd.data_ptr()), 2, H, W, C, gw, stride, C_.c_void_p(w.data_ptr()),
+    rc = so.vge_debug_gconv3(C_.c_void_p(xd.data_ptr()), n, H, W, C, gw, stride, C_.c_void_p(w.data_ptr()),
                              C_.c_void_p(b.data_ptr()), C_.c_void_p(out.data_ptr()), C_.c_void_p(st))
     assert rc == 0, L.load().vge_last_error()
+    return out.cpu()
+
+
+def _gconv_check(gw, stride, C, H, W, n):
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import torch.nn.functional as F
+    g = torch.Generator().manual_seed(gw * 7 + stride)
+    x = torch.randn((n, H, W, C), generator=g).to(torch.bfloat16)
+    w = (torch.randn((C, gw, 3, 3), generator=g) / (3.0 * gw ** 0.5)).float()
+    b = (0.1 * torch.randn(C, generator=g)).float()
+    out = _gconv_run(x, w, b, gw, stride)
     ref = F.conv2d(x.float().permute(0, 3, 1, 2), w.to(torch.bfloat16).float(), b, stride=stride, padding=1,
                    groups=C // gw).relu().permute(0, 2, 3, 1)
-    got = out.float().cpu()
+    got = out.float()
     assert torch.isfinite(got).all()
     err = (got - ref).abs()
     bound = 2.0 ** -7 * ref.abs() + 1e-4          # one bf16 rounding of the output (+ f32 summation order)
-    print(f"gw {gw} stride {stride}: max |d| {err.max():.2e}, max |ref| {ref.abs().max():.2e}")
+    print(f"gw {gw} stride {stride} n {n}: max |d| {err.max():.2e}, max |ref| {ref.abs().max():.2e}, "
+          f"worst error / bound {float((err / bound).max()):.3f}")
     assert bool((err <= bound).all()), float((err - bound).max())
+    return x, w, b, out
+
+
+@pytest.mark.parametrize("n", [1, 8, 9, 17])
+@pytest.mark.parametrize("gw,stride,C,H,W", [(8, 1, 256, 20, 37), (16, 2, 512, 21, 18), (32, 1, 1024, 13, 11),
+                                             (64, 1, 2048, 9, 10), (32, 2, 1024, 14, 13), (64, 2, 2048, 7, 6),
+                                             (8, 2, 256, 15, 16), (16, 1, 512, 10, 33)])
+def test_grouped_conv_image_groups(gw, stride, C, H, W, n):
+    """The same bound at 1, 8, 9 and 17 images per call, one small shape per kernel template (group widths 8 / 16, 32
+    and 64, each at stride 1 and 2): a workgroup of gconv3_kernel loops over up to GC_NI = 8 images with the next
+    image's loads in flight, so 8 is one full group, 9 and 17 end in a group of one, 1 is a group of one alone.  Image
+    i of the 17-image call equals the same image run alone, bit for bit."""
+    x, w, b, out = _gconv_check(gw, stride, C, H, W, n)
+    if n == 17:
+        for i in range(n):
+            one = _gconv_run(x[i:i + 1].contiguous(), w, b, gw, stride)
+            assert torch.equal(one[0].view(torch.int16), out[i].view(torch.int16)), f"image {i} differs when run alone"
 
 
 def test_chunk_cap_and_128_frame_chunk_matches_64(run):

@@ -91,6 +91,18 @@ void pil_coeffs(int in, int out, std::vector<int>& bounds, std::vector<int>& kk,
 
 std::string I(int i) { return std::to_string(i); }
 
+// the PIL coefficient tables of both axes on the device, as launch_frcnn_resize_h / _v_norm read them (H x W frames
+// resized to nh x nw): vge_frcnn_reserve and vge_op_frcnn_preprocess
+struct ResizeTables {
+  int *xb = nullptr, *xk = nullptr, *yb = nullptr, *yk = nullptr, ksx = 0, ksy = 0;
+  bool upload_for(DevAllocs& d, int H, int W, int nh, int nw) {
+    std::vector<int> b, k;
+    if (pil_coeffs(W, nw, b, k, ksx), !upload(d, b, &xb) || !upload(d, k, &xk)) return false;
+    if (pil_coeffs(H, nh, b, k, ksy), !upload(d, b, &yb) || !upload(d, k, &yk)) return false;
+    return true;
+  }
+};
+
 }  // namespace
 
 struct vge_frcnn {
@@ -248,6 +260,19 @@ void load_all(FLoader& ld, const vge_frcnn_config& c) {
   }
 }
 
+// what det_post_kernel is built for: vge_frcnn_create's rule for these fields, and vge_op_det_post's
+bool det_post_ok(int K, int det_per_img, float score_thresh, float nms_thresh, std::string& why) {
+  if (K < 1 || K + 1 > 128) return why = "num_classes must be in [1, 127]", false;
+  if (det_per_img < 1 || det_per_img > vge::FR_MAXK) return why = "det_per_img must be in [1, 1024]", false;
+  // det_post_kernel keeps at most 4 candidate classes per proposal (vge_frcnn_kernels.hip, FR_MAXCAND = 4,096 slots):
+  // exact when no proposal can have 5 classes above the threshold, i.e. 5 x score_thresh >= 1 (softmax sums to 1);
+  // the reference's gate runs at 0.25 (mesh_generator.py:71)
+  if (!(score_thresh >= 0.2f && score_thresh < 1.f))
+    return why = "score_thresh must be in [0.2, 1): at most 4 classes per proposal pass it (det_post_kernel)", false;
+  if (!(nms_thresh > 0.f && nms_thresh <= 1.f)) return why = "NMS thresholds must be in (0, 1]", false;
+  return true;
+}
+
 bool cfg_ok(const vge_frcnn_config& c, std::string& why) {
   int nb[4];
   if (c.min_size <= 0 || c.max_size < c.min_size) return why = "min_size / max_size", false;
@@ -259,16 +284,9 @@ bool cfg_ok(const vge_frcnn_config& c, std::string& why) {
   if (c.fpn_ch != 256) return why = "fpn_ch must be 256", false;
   if (c.rpn_pre_topk < 1 || c.rpn_pre_topk > vge::FR_MAXK || c.rpn_post_topk < 1 || c.rpn_post_topk > vge::FR_MAXK)
     return why = "rpn top-k must be in [1, 1024]", false;
-  if (c.num_classes < 1 || c.num_classes + 1 > 128) return why = "num_classes must be in [1, 127]", false;
-  if (c.det_per_img < 1 || c.det_per_img > vge::FR_MAXK) return why = "det_per_img must be in [1, 1024]", false;
   if (!pow2(c.fc_dim) || c.fc_dim < 64) return why = "fc_dim must be a power of two >= 64", false;
-  // det_post_kernel keeps at most 4 candidate classes per proposal (vge_frcnn_kernels.hip, FR_MAXCAND = 4,096 slots):
-  // exact when no proposal can have 5 classes above the threshold, i.e. 5 x score_thresh >= 1 (softmax sums to 1);
-  // the reference's gate runs at 0.25 (mesh_generator.py:71)
-  if (!(c.score_thresh >= 0.2f && c.score_thresh < 1.f))
-    return why = "score_thresh must be in [0.2, 1): at most 4 classes per proposal pass it (det_post_kernel)", false;
-  if (!(c.nms_thresh > 0.f && c.nms_thresh <= 1.f) || !(c.rpn_nms > 0.f && c.rpn_nms <= 1.f))
-    return why = "NMS thresholds must be in (0, 1]", false;
+  if (!det_post_ok(c.num_classes, c.det_per_img, c.score_thresh, c.nms_thresh, why)) return false;
+  if (!(c.rpn_nms > 0.f && c.rpn_nms <= 1.f)) return why = "NMS thresholds must be in (0, 1]", false;
   return true;
 }
 
@@ -447,11 +465,14 @@ int vge_frcnn_reserve(vge_frcnn* m, int chunk, int H, int W) {
   RC(m->ws.reserve("vge_frcnn_reserve", bufs));
   for (const Alias& a : al)
     if (a.bytes <= a.over_bytes) *a.p = *a.over;
-  std::vector<int> b, k;
-  if (pil_coeffs(W, m->nw, b, k, m->ksx), !upload(m->ws.dev, b, &m->xb) || !upload(m->ws.dev, k, &m->xk))
-    return fail(VGE_ERR_NOMEM, "vge_frcnn_reserve: upload failed");
-  if (pil_coeffs(H, m->nh, b, k, m->ksy), !upload(m->ws.dev, b, &m->yb) || !upload(m->ws.dev, k, &m->yk))
-    return fail(VGE_ERR_NOMEM, "vge_frcnn_reserve: upload failed");
+  ResizeTables rt;
+  if (!rt.upload_for(m->ws.dev, H, W, m->nh, m->nw)) return fail(VGE_ERR_NOMEM, "vge_frcnn_reserve: upload failed");
+  m->xb = rt.xb;
+  m->xk = rt.xk;
+  m->yb = rt.yb;
+  m->yk = rt.yk;
+  m->ksx = rt.ksx;
+  m->ksy = rt.ksy;
   m->chunk = chunk;
   m->rH = H;
   m->rW = W;
@@ -691,6 +712,162 @@ int vge_debug_gconv3(const void* x, int n, int H, int W, int C, int gw, int stri
   HIPCHK(hipStreamSynchronize(s));
   return VGE_OK;
 }
+
+// ---- the non-GEMM kernels one at a time (include/vge_frcnn.h): the arguments are checked, then the launcher
+// vge_frcnn_detect calls runs; an entry that allocates (tables, packed weights, scratch) waits for the stream before
+// it frees them
+#define OP_REFUSE(cond, msg) \
+  if (cond) return fail(VGE_ERR_ARG, std::string(OP) + ": " + (msg))
+
+int vge_op_frcnn_preprocess(const uint8_t* frames, int n, int H, int W, int min_size, int max_size, uint8_t* resized,
+                            void* out, vge_stream_t stream) {
+  static const char* OP = "vge_op_frcnn_preprocess";
+  OP_REFUSE(n <= 0 || H <= 0 || W <= 0, "n, H, W must be positive");
+  OP_REFUSE(min_size <= 0 || max_size < min_size, "min_size must be positive and max_size >= min_size");
+  int nh, nw;
+  output_shape(H, W, min_size, max_size, nh, nw);
+  OP_REFUSE(nh < 1 || nw < 1, "an axis of the resized frame rounds to 0 pixels");
+  const int hp = rup(nh, 32), wp = rup(nw, 32);
+  OP_REFUSE((size_t)n * std::max((size_t)hp * wp, (size_t)H * nw) >= (1ull << 31), "n x pixels must stay under 2^31");
+  OP_REFUSE(!frames || !out, "null pointer");
+  DevAllocs dev;
+  ResizeTables rt;
+  uint8_t* tmp = static_cast<uint8_t*>(dev.dmalloc((size_t)n * H * nw * 3));
+  if (!tmp || !rt.upload_for(dev, H, W, nh, nw)) return fail(VGE_ERR_NOMEM, std::string(OP) + ": allocation failed");
+  hipStream_t s = S(stream);
+  HIPCHK(vge::launch_frcnn_resize_h(frames, n, H, W, nw, rt.xb, rt.xk, rt.ksx, tmp, s));
+  HIPCHK(vge::launch_frcnn_resize_v_norm(tmp, n, H, nw, nh, hp, wp, rt.yb, rt.yk, rt.ksy, resized, out, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return VGE_OK;
+}
+
+int vge_op_frcnn_pool_s2(const void* x, void* y, int n, int H, int W, int C, int K, vge_stream_t stream) {
+  static const char* OP = "vge_op_frcnn_pool_s2";
+  OP_REFUSE(K != 1 && K != 3, "K must be 1 (P6) or 3 (after the stem)");
+  OP_REFUSE(C <= 0 || C % 8, "C must be a positive multiple of 8");
+  OP_REFUSE(n <= 0 || H <= 0 || W <= 0, "n, H, W must be positive");
+  OP_REFUSE((size_t)n * H * W * (C / 8) >= (1ull << 31), "n x H x W x C / 8 must stay under 2^31");
+  OP_REFUSE(!x || !y, "null pointer");
+  HIPCHK(vge::launch_frcnn_pool_s2(x, y, n, H, W, C, K, S(stream)));
+  return VGE_OK;
+}
+
+int vge_op_frcnn_stem_pool(const void* in, const float* w, const float* b, void* out, int n, int hp, int wp,
+                           vge_stream_t stream) {
+  static const char* OP = "vge_op_frcnn_stem_pool";
+  OP_REFUSE(n <= 0 || hp <= 0 || wp <= 0, "n, hp, wp must be positive");
+  OP_REFUSE(hp % 32 || wp % 32, "hp, wp must be multiples of 32 (the detector's padding)");
+  OP_REFUSE((size_t)n * hp * wp >= (1ull << 31), "n x hp x wp must stay under 2^31");
+  OP_REFUSE(!in || !w || !b || !out, "null pointer");
+  DevAllocs dev;
+  ConvW L;
+  if (!pack_conv(dev, w, b, 64, 3, 8, 7, 7, L)) return fail(VGE_ERR_NOMEM, std::string(OP) + ": upload failed");
+  hipStream_t s = S(stream);
+  HIPCHK(vge::launch_frcnn_stem_pool(in, L.w, L.Kp, L.b, out, n, hp, wp, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return VGE_OK;
+}
+
+int vge_op_rpn_proposals(const float* const* levels, const int* level_hw, int n, int pre_topk, int post_topk,
+                         float nms_thresh, int img_h, int img_w, float* props, int32_t* n_prop, float* sel, float* kept,
+                         int32_t* kcount, vge_stream_t stream) {
+  static const char* OP = "vge_op_rpn_proposals";
+  OP_REFUSE(n <= 0 || n > 4096, "n must be in [1, 4096]");
+  OP_REFUSE(pre_topk < 1 || pre_topk > vge::FR_MAXK || post_topk < 1 || post_topk > vge::FR_MAXK,
+            "pre_topk, post_topk must be in [1, 1024]");
+  OP_REFUSE(!(nms_thresh > 0.f && nms_thresh <= 1.f), "nms_thresh must be in (0, 1]");
+  OP_REFUSE(img_h <= 0 || img_w <= 0, "img_h, img_w must be positive");
+  OP_REFUSE(!levels || !level_hw, "null levels / level_hw array");
+  vge::RpnLevels rl{};
+  for (int l = 0; l < 5; ++l) {
+    const int h = level_hw[2 * l], w = level_hw[2 * l + 1];
+    OP_REFUSE(h <= 0 || w <= 0 || (size_t)h * w > (1u << 24), "every level needs 1 <= h x w <= 2^24");
+    rl.l[l].out = levels[l];
+    rl.l[l].h = h;
+    rl.l[l].w = w;
+    rl.l[l].stride = 4 << l;
+    rl.l[l].k = std::min(pre_topk, h * w * 3);
+  }
+  OP_REFUSE(!levels[0] || !levels[1] || !levels[2] || !levels[3] || !levels[4] || !props || !n_prop, "null pointer");
+  DevAllocs dev;
+  const size_t per = (size_t)n * 5 * vge::FR_MAXK * vge::FR_SEL * 4;
+  if (!sel) sel = static_cast<float*>(dev.dmalloc(per));
+  if (!kept) kept = static_cast<float*>(dev.dmalloc(per));
+  if (!kcount) kcount = static_cast<int32_t*>(dev.dmalloc((size_t)n * 5 * 4));
+  float* sel_max = static_cast<float*>(dev.dmalloc((size_t)n * 5 * 4));
+  if (!sel || !kept || !kcount || !sel_max) return fail(VGE_ERR_NOMEM, std::string(OP) + ": allocation failed");
+  hipStream_t s = S(stream);
+  HIPCHK(vge::launch_rpn_select(rl, n, (float)img_h, (float)img_w, sel, sel_max, s));
+  HIPCHK(vge::launch_rpn_nms(rl, sel, sel_max, n, nms_thresh, kept, kcount, s));
+  HIPCHK(vge::launch_rpn_merge(kept, kcount, n, post_topk, props, n_prop, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return VGE_OK;
+}
+
+int vge_op_roi_align(const void* const* levels, const int* level_hw, const float* props, const int32_t* n_prop, int n,
+                     int P, void* out, vge_stream_t stream) {
+  static const char* OP = "vge_op_roi_align";
+  OP_REFUSE(n <= 0 || n > 4096, "n must be in [1, 4096]");
+  OP_REFUSE(P < 1 || P > vge::FR_MAXK, "P must be in [1, 1024]");
+  OP_REFUSE(!levels || !level_hw, "null levels / level_hw array");
+  vge::RoiLevels ro{};
+  for (int l = 0; l < 4; ++l) {
+    const int h = level_hw[2 * l], w = level_hw[2 * l + 1];
+    // one frame's level is one buffer record range of h x w x 512 bytes (roi_align_sep_kernel)
+    OP_REFUSE(h <= 0 || w <= 0 || (size_t)h * w * 512 >= (1ull << 31), "every level needs 1 <= h x w < 2^22");
+    ro.p[l] = levels[l];
+    ro.h[l] = h;
+    ro.w[l] = w;
+  }
+  OP_REFUSE(!levels[0] || !levels[1] || !levels[2] || !levels[3] || !props || !n_prop || !out, "null pointer");
+  HIPCHK(vge::launch_roi_align(ro, props, n_prop, n, P, out, S(stream)));
+  return VGE_OK;
+}
+
+int vge_op_det_post(const float* head, int ld, int P, int K, int det_per_img, const float* props, const int32_t* n_prop,
+                    int n, int img_h, int img_w, int out_h, int out_w, float score_thresh, float nms_thresh,
+                    float gate_thresh, float* pre_dets, int32_t* n_pre, float* dets, int32_t* n_dets, float* person,
+                    int32_t* n_person, vge_stream_t stream) {
+  static const char* OP = "vge_op_det_post";
+  std::string why;
+  OP_REFUSE(!det_post_ok(K, det_per_img, score_thresh, nms_thresh, why), why);
+  OP_REFUSE(P < 1 || P > vge::FR_MAXK, "P must be in [1, 1024]");
+  OP_REFUSE(ld < 5 * K + 1, "ld must be >= 5 K + 1 (logits K + 1 | deltas 4 K)");
+  OP_REFUSE(n <= 0 || n > 4096, "n must be in [1, 4096]");
+  OP_REFUSE(img_h <= 0 || img_w <= 0 || out_h <= 0 || out_w <= 0, "image and frame sizes must be positive");
+  OP_REFUSE(!head || !props || !n_prop || !n_person, "null pointer");
+  DevAllocs dev;
+  vge::DetPostArgs da{};
+  da.scratch = static_cast<float*>(dev.dmalloc(vge::det_post_scratch_bytes(n)));
+  if (!da.scratch) return fail(VGE_ERR_NOMEM, std::string(OP) + ": allocation failed");
+  da.head = head;
+  da.ld = ld;
+  da.P = P;
+  da.K = K;
+  da.det_per_img = det_per_img;
+  da.props = props;
+  da.n_prop = n_prop;
+  da.img_h = (float)img_h;
+  da.img_w = (float)img_w;
+  da.sx = (float)((double)out_w / img_w);  // as vge_frcnn_detect forms them
+  da.sy = (float)((double)out_h / img_h);
+  da.out_h = (float)out_h;
+  da.out_w = (float)out_w;
+  da.score_thresh = score_thresh;
+  da.nms_thresh = nms_thresh;
+  da.gate_thresh = gate_thresh;
+  da.pre_dets = pre_dets;
+  da.n_pre = n_pre;
+  da.dets = dets;
+  da.n_dets = n_dets;
+  da.person = person;
+  da.n_person = n_person;
+  hipStream_t s = S(stream);
+  HIPCHK(vge::launch_det_post(da, n, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return VGE_OK;
+}
+#undef OP_REFUSE
 
 }  // extern "C"
 

@@ -7,7 +7,8 @@
 //       multiple of 32 (ImageList size_divisibility)
 //   frcnn_pool_s2_kernel<K>   max_pool2d(3, 2, 1) after the stem, max_pool2d(1, 2, 0) for P6 (LastLevelMaxPool)
 //   rpn_select_kernel         find_top_rpn_proposals, one workgroup per (frame, level): the top-k objectness logits by
-//       an 8-bit radix select on order-preserving keys (ties: lower anchor index), a bitonic sort of the k winners,
+//       an 8-bit radix select on order-preserving keys (ties: lower anchor index; NaN first and -0 = +0, as
+//       torch.sort orders them), a bitonic sort of the k winners,
 //       anchor + Box2BoxTransform decode, clip, nonempty, and the level's largest kept coordinate
 //   rpn_nms_kernel            batched_nms(0.7) per (frame, level): torchvision's coordinate trick (boxes + level x
 //       (max + 1)), the IoU > thr upper triangle as 64-bit ballot words in LDS, the greedy scan by one wave (bit scan
@@ -37,8 +38,12 @@ typedef unsigned long long u64;
 
 constexpr float SCALE_CLAMP = 4.135166556742356f;  // log(1000 / 16), Box2BoxTransform
 
-__device__ __forceinline__ unsigned okey(float f) {  // order-preserving unsigned key of a float
+// order-preserving unsigned key of a float, in torch.sort's order: every NaN (either sign, any payload) one key above
+// +inf, and -0 the key of +0 (equal values: the index decides)
+__device__ __forceinline__ unsigned okey(float f) {
   const unsigned u = __float_as_uint(f);
+  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0xFFFFFFFFu;
+  if (u == 0x80000000u) return 0x80000000u;
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ int clip8(int v) {

@@ -78,6 +78,13 @@ _SIG = {
     "vge_frcnn_detect": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, C.POINTER(FrcnnTapsC), _vp],
     "vge_frcnn_profile_begin": [_vp, _i32],
     "vge_frcnn_profile_read": [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double)],
+    "vge_op_frcnn_preprocess": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
+    "vge_op_frcnn_pool_s2": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
+    "vge_op_frcnn_stem_pool": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp],
+    "vge_op_rpn_proposals": [_vp, _vp, _i32, _i32, _i32, C.c_float, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "vge_op_roi_align": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
+    "vge_op_det_post": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.c_float, C.c_float,
+                        C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 
 
@@ -217,3 +224,84 @@ class FrcnnDetector(L.NativeModel):
 
     def profile_read(self):
         return self._profile_read(("backbone_gemm", "head_gemm", "other"), n_flops=2)
+
+
+# Thin wrappers of include/vge_frcnn.h's vge_op_*: the detector's non-GEMM kernels one at a time, on device tensors the
+# caller owns (an output may be pre-filled to show what the kernel writes); weights are host float32 arrays.
+def _op(name: str, *args) -> None:
+    L.check(getattr(_sig(L.load()), name)(*args), name)
+
+
+def _host_f32(a) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float32))
+
+
+def _level_args(levels, n_levels: int):
+    """-> (host array of device pointers, host int array h_0, w_0, ...) of [n, h, w, C] level tensors"""
+    if len(levels) != n_levels:
+        raise L.VgeError(f"{n_levels} level tensors expected")
+    ptrs = (C.c_void_p * n_levels)(*[_ptr(t) for t in levels])
+    hw = (C.c_int * (2 * n_levels))(*[int(v) for t in levels for v in t.shape[1:3]])
+    return ptrs, hw
+
+
+def preprocess(frames: torch.Tensor, min_size: int, max_size: int, out: torch.Tensor,
+               resized: Optional[torch.Tensor] = None) -> None:
+    """frames uint8 [n, H, W, 3] RGB -> out bf16 [n, hp, wp, 8] (normalised BGR, zero channels and padding), resized
+    uint8 [n, nh, nw, 3] (oracle.frcnn.output_shape gives nh, nw; hp, wp round them up to 32)."""
+    n, H, W = (int(v) for v in frames.shape[:3])
+    _op("vge_op_frcnn_preprocess", _ptr(frames), n, H, W, int(min_size), int(max_size), _ptr(resized), _ptr(out),
+        _stream(frames.device))
+
+
+def pool_s2(x: torch.Tensor, out: torch.Tensor, K: int) -> None:
+    """max_pool2d(K, 2, K // 2) of x bf16 [n, H, W, C] -> out [n, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C]."""
+    n, H, W, Cc = (int(v) for v in x.shape)
+    _op("vge_op_frcnn_pool_s2", _ptr(x), _ptr(out), n, H, W, Cc, int(K), _stream(x.device))
+
+
+def stem_pool(x: torch.Tensor, w, b, out: torch.Tensor) -> None:
+    """The fused stem conv 7x7 / 2 + ReLU + max_pool2d(3, 2, 1): x bf16 [n, hp, wp, 8], w host f32 [64, 3, 7, 7], b host
+    f32 [64] -> out bf16 [n, hp // 4, wp // 4, 64]."""
+    n, hp, wp = (int(v) for v in x.shape[:3])
+    w, b = _host_f32(w), _host_f32(b)
+    if w.shape != (64, 3, 7, 7) or b.shape != (64,):
+        raise L.VgeError("stem weights must be [64, 3, 7, 7] and [64]")
+    _op("vge_op_frcnn_stem_pool", _ptr(x), w.ctypes.data, b.ctypes.data, _ptr(out), n, hp, wp, _stream(x.device))
+
+
+def rpn_proposals(levels, pre_topk: int, post_topk: int, nms_thresh: float, image_size, props: torch.Tensor,
+                  n_prop: torch.Tensor, sel: Optional[torch.Tensor] = None, kept: Optional[torch.Tensor] = None,
+                  kcount: Optional[torch.Tensor] = None) -> None:
+    """levels: five f32 [n, h_l, w_l, 16] RPN head outputs; image_size = (h, w) of the resized image -> props f32
+    [n, post_topk, 5], n_prop int32 [n]; optional sel / kept f32 [n, 5, 1024, 8], kcount int32 [n, 5]."""
+    ptrs, hw = _level_args(levels, 5)
+    _op("vge_op_rpn_proposals", ptrs, hw, int(levels[0].shape[0]), int(pre_topk), int(post_topk), float(nms_thresh),
+        int(image_size[0]), int(image_size[1]), _ptr(props), _ptr(n_prop), _ptr(sel), _ptr(kept), _ptr(kcount),
+        _stream(props.device))
+
+
+def roi_align(levels, props: torch.Tensor, n_prop: torch.Tensor, out: torch.Tensor) -> None:
+    """levels: four bf16 [n, h_l, w_l, 256] (P2..P5); props f32 [n, P, 5], n_prop int32 [n] -> out bf16 [n, P, 49, 256]."""
+    ptrs, hw = _level_args(levels, 4)
+    _op("vge_op_roi_align", ptrs, hw, _ptr(props), _ptr(n_prop), int(props.shape[0]), int(props.shape[1]), _ptr(out),
+        _stream(props.device))
+
+
+def det_post(head: torch.Tensor, props: torch.Tensor, n_prop: torch.Tensor, K: int, det_per_img: int, image_size,
+             frame_hw, score_thresh: float, nms_thresh: float, gate_thresh: float) -> Dict[str, torch.Tensor]:
+    """head f32 [n, P, ld] (logits K + 1 | deltas 4 K), props f32 [n, P, 5], n_prop int32 [n] -> pre_dets
+    [n, det_per_img, 6] / n_pre (resized pixels), dets / n_dets (frame pixels), person [n, 2, 5], n_person, pre-filled
+    with NaN / -1."""
+    n, P, ld = (int(v) for v in head.shape)
+    dev = head.device
+    nan = float("nan")
+    o = {"pre_dets": torch.full((n, det_per_img, 6), nan, device=dev), "dets": torch.full((n, det_per_img, 6), nan, device=dev),
+         "person": torch.full((n, 2, 5), nan, device=dev)}
+    for k in ("n_pre", "n_dets", "n_person"):
+        o[k] = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    _op("vge_op_det_post", _ptr(head), ld, P, int(K), int(det_per_img), _ptr(props), _ptr(n_prop), n,
+        int(image_size[0]), int(image_size[1]), int(frame_hw[0]), int(frame_hw[1]), float(score_thresh),
+        float(nms_thresh), float(gate_thresh), _ptr(o["pre_dets"]), _ptr(o["n_pre"]), _ptr(o["dets"]),
+        _ptr(o["n_dets"]), _ptr(o["person"]), _ptr(o["n_person"]), _stream(dev))
+    return o

@@ -43,6 +43,8 @@ EXPORTS = ["vge_featurize", "vge_featurize_layout", "vge_layout_feat_dim", "vge_
            "vge_yolox_profile_begin", "vge_yolox_profile_read",
            "vge_frcnn_create", "vge_frcnn_reserve", "vge_frcnn_destroy", "vge_frcnn_shapes", "vge_frcnn_detect",
            "vge_frcnn_profile_begin", "vge_frcnn_profile_read",
+           "vge_op_frcnn_preprocess", "vge_op_frcnn_pool_s2", "vge_op_frcnn_stem_pool", "vge_op_rpn_proposals",
+           "vge_op_roi_align", "vge_op_det_post",
            "vge_jpeg_probe", "vge_jpeg_make_layout", "vge_jpeg_entropy_decode", "vge_jpeg_reconstruct",
            "vge_jpeg_reconstruct_host",
            "vge_jpeg_quant_tables", "vge_jpeg_forward", "vge_jpeg_forward_host", "vge_jpeg_entropy_encode",
