@@ -1,7 +1,7 @@
 """Frames per second of vge.frames.load_frames on JPEG frame folders, split into its stages, beside Pillow.
 
     python tools/bench_frames.py [--frames 1024] [--size 256] [--quality 95] [--threads 16] [--folder DIR]
-                                 [--entropy host|device] [--format jpg|png|gif|webp] [--out profiles/jpeg_decode.json]
+                                 [--entropy host|device] [--format jpg|png|gif|webp|apng] [--out profiles/jpeg_decode.json]
 
 Writes its own JPEGs with Pillow (vge.synth.make_frames content, 4:2:0, quality 95: what cv2.imwrite writes) into a
 temporary folder, or reads the *.jpg files of --folder (cycled up to --frames).  Needs a GPU: there is no fallback.
@@ -49,6 +49,16 @@ measured:
   entropy_kernel, entropy_transforms, compose_kernel   the first kernel, the first two, the last alone   (device events)
   e2e_host / e2e_device      load_videos(files, device, entropy=...) ending in a device synchronise   (host clock)
 The report also holds the largest number of prefix-code groups a frame asked for, beside the arena's capacity.
+
+With --format apng (written to profiles/apng_decode_device.json unless --out says otherwise) animated PNGs are written
+by Pillow (save_all=True), --gif-files files, in two kinds of content -- "deltas": RGB frames that differ in a moving
+square, which Pillow crops to the rectangle that changed; "rgba": whole RGBA frames blended OVER -- and both routes are
+measured for each kind:
+  host_decode     vge_apng_decode on --threads host threads into pinned memory           (host clock)
+  plan            vge_apng_plan_mem over the files in memory                             (host clock)
+  device_call     vge_apng_decode_device: gather + inflate + adler + unfilter + compose  (device events)
+  gather_kernel, inflate_kernel, adler_kernel, inflate_unfilter_kernel, compose_kernel   (device events)
+  e2e_host / e2e_device      load_videos(files, device, entropy=...) ending in a device synchronise   (host clock)
 """
 from __future__ import annotations
 
@@ -513,6 +523,171 @@ def bench_webp(args) -> int:
     return 0
 
 
+def write_apngs(folder: Path, n_files: int, per_file: int, size: int, kind: str):
+    """Animated PNGs as Pillow writes them (save_all=True).  kind "deltas": RGB frames that repeat the clip's first
+    vge.synth.make_frames frame with a square moving over it, so that Pillow crops every frame to the rectangle that
+    changed; kind "rgba": vge.synth.make_frames frames with an alpha channel of their own, which change everywhere, so
+    that every frame is a whole RGBA picture, blended OVER the one before."""
+    from PIL import Image
+    from vge import synth
+    paths = []
+    y, x = np.mgrid[0:size, 0:size]
+    for v in range(n_files):
+        fr = synth.make_frames(1000 + v, per_file, h=size, w=size)
+        if kind == "deltas":
+            ims = []
+            for f in range(per_file):
+                a = fr[0].copy()
+                q = size // 4
+                ox, oy = (7 * f + 3 * v) % (size - q), (5 * f + v) % (size - q)
+                a[oy:oy + q, ox:ox + q] = fr[f][oy:oy + q, ox:ox + q][::-1]
+                ims.append(Image.fromarray(a))
+            kw = {}
+        else:
+            alpha = ((3 * x + 5 * y) % 256).astype(np.uint8)
+            ims = [Image.fromarray(np.dstack([fr[f], np.roll(alpha, 11 * f, axis=1)]), "RGBA") for f in range(per_file)]
+            kw = dict(blend=1)
+        p = folder / f"{kind}_{v:04d}.png"
+        ims[0].save(p, format="PNG", save_all=True, append_images=ims[1:], duration=100, loop=0, **kw)
+        paths.append(str(p))
+    return paths
+
+
+def bench_apng(args) -> int:
+    """--format apng: both routes of load_videos on animated PNGs of two kinds of content and the device call's kernels
+    one by one."""
+    import torch
+    from vge import frames as FR
+    from vge import lib as L
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_frames.py needs a GPU")
+    dev = torch.device("cuda:0")
+    lib = L.load()
+    n_files = args.gif_files
+    per_file = max(1, args.frames // n_files)
+
+    def events(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b) * 1e-3
+
+    def one_kind(kind):
+        tmp = tempfile.TemporaryDirectory()
+        paths = write_apngs(Path(tmp.name), n_files, per_file, args.size, kind)
+        rows = FR.apng_probe(paths, args.threads)
+        assert not rows[:, -1].any()
+        n, n_chunks = int(rows[:, 5].sum()), int(rows[:, 7].sum())
+        w, h, ct = int(rows[0, 0]), int(rows[0, 1]), int(rows[0, 2])
+
+        def e2e(entropy):
+            t = time.perf_counter()
+            out = FR.load_videos(paths, device=dev, threads=args.threads, entropy=entropy)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t
+            assert sum(k.size for _, k in out) == n
+            return dt, torch.cat([f for f, _ in out])
+
+        out_h = torch.empty((n, h, w, 3), dtype=torch.uint8, pin_memory=True)
+        status = np.zeros(n, np.int32)
+        arr = (C.c_char_p * n_files)(*[os.fsencode(p) for p in paths])
+
+        def host_decode():
+            t = time.perf_counter()
+            rc = lib.vge_apng_decode(arr, n_files, args.threads, w, h, ct, n, out_h.data_ptr(), status.ctypes.data, None,
+                                     None)
+            dt = time.perf_counter() - t
+            assert rc == 0, lib.vge_last_error()
+            return dt
+
+        raw, raw_off, raw_size = FR._read_files(paths, args.threads, pin=True)
+        raw_d = raw.to(dev)
+        descs = (L.ApngDesc * n)()
+        segs = (L.ApngSegment * n_chunks)()
+        n_descs, n_segs, ws_bytes = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+
+        def plan():
+            t = time.perf_counter()
+            rc = lib.vge_apng_plan_mem(raw.data_ptr(), int(raw.numel()), raw_off.ctypes.data, raw_size.ctypes.data,
+                                       n_files, args.threads, w, h, ct, descs, n, C.byref(n_descs), segs, n_chunks,
+                                       C.byref(n_segs), None, None, C.byref(ws_bytes))
+            dt = time.perf_counter() - t
+            assert rc == 0 and n_descs.value == n, lib.vge_last_error()
+            return dt
+
+        plan()
+        descs_d = torch.frombuffer(descs, dtype=torch.uint8).to(dev)
+        segs_d = torch.frombuffer(segs, dtype=torch.uint8).to(dev)
+        ws = torch.empty(int(ws_bytes.value), dtype=torch.uint8, device=dev)
+        status_d = torch.empty(n, dtype=torch.int32, device=dev)
+        out_d = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev)
+
+        def device_call():
+            L.check(lib.vge_apng_decode_device(raw_d.data_ptr(), int(raw_d.numel()), descs_d.data_ptr(), n,
+                                               segs_d.data_ptr(), n_segs.value, n, n_files, w, h, ct, ws.data_ptr(),
+                                               int(ws.numel()), out_d.data_ptr(), status_d.data_ptr(),
+                                               stream.cuda_stream), "vge_apng_decode_device")
+
+        def stage(mask):   # one kernel of the call alone (a hook of the library for this tool)
+            lib.vge_debug_apng_stage_mask(mask)
+            try:
+                return events(device_call)
+            finally:
+                lib.vge_debug_apng_stage_mask(31)
+
+        res = {}
+        for _ in range(args.warmup):
+            host_decode(); events(device_call); e2e("host"); e2e("device")
+        res["host_decode_s"] = spread([host_decode() for _ in range(args.repeats)])
+        res["plan_s"] = spread([plan() for _ in range(args.repeats)])
+        res["device_call_s"] = spread([events(device_call) for _ in range(args.repeats)])
+        assert int(status_d.abs().sum()) == 0
+        calls_equal = bool(torch.equal(out_d.cpu(), out_h))
+        # gather, inflate and adler run on what the call before left; unfilter rewrites its slot in place, so it is
+        # timed together with the inflate that fills it, and compose on the pixels a whole call left
+        for name, mask in (("gather", 1), ("inflate", 2), ("adler", 4), ("inflate_unfilter", 2 | 8), ("compose", 16)):
+            if name == "compose":
+                events(device_call)
+            res[f"{name}_kernel_s"] = spread([stage(mask) for _ in range(args.repeats)])
+        eh = [e2e("host") for _ in range(args.repeats)]
+        ed = [e2e("device") for _ in range(args.repeats)]
+        res["e2e_host_s"] = spread([t for t, _ in eh])
+        res["e2e_device_s"] = spread([t for t, _ in ed])
+        rect = np.array([[descs[k].w, descs[k].h] for k in range(n)])
+        tmp.cleanup()
+        return {
+            "files": n_files, "frames": n, "width": w, "height": h, "color_type": ct,
+            "apng_bytes_per_frame": float(raw_size.sum()) / n, "chunks_per_frame": n_chunks / n,
+            "mean_rectangle": [float(rect[:, 0].mean()), float(rect[:, 1].mean())],
+            "stages": res,
+            "ms_per_pass": {key[:-2]: 1e3 * v["median"] for key, v in res.items()},
+            "frames_per_s": {key[:-2]: n / v["median"] for key, v in res.items()},
+            "yardstick_host_decode_ms": 1e3 * res["host_decode_s"]["median"],
+            "device_call_ms": 1e3 * res["device_call_s"]["median"],
+            "device_call_over_host_decode": res["device_call_s"]["median"] / res["host_decode_s"]["median"],
+            "e2e_device_over_e2e_host": res["e2e_device_s"]["median"] / res["e2e_host_s"]["median"],
+            "device_equals_host": calls_equal and bool(torch.equal(ed[-1][1], eh[-1][1])),
+        }
+
+    report = {
+        "what": "vge.frames.load_videos on animated PNGs, both routes, measured on the GPU by tools/bench_frames.py "
+                "--format apng",
+        "device": torch.cuda.get_device_name(0), "threads": args.threads,
+        "source": f"written here by Pillow (save_all): vge.synth.make_frames {args.size}x{args.size}; deltas: RGB, a "
+                  "moving square over a fixed frame, cropped by Pillow; rgba: whole RGBA frames blended OVER",
+        "deltas": one_kind("deltas"),
+        "rgba": one_kind("rgba"),
+    }
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(report, f, indent=1)
+    print(json.dumps(report))
+    return 0
+
+
 def _idat(data: bytes):
     """(offset, length) of a PNG file's IDAT payloads."""
     at, out = 8, []
@@ -526,9 +701,9 @@ def _idat(data: bytes):
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--format", choices=("jpg", "png", "gif", "webp"), default="jpg")
+    ap.add_argument("--format", choices=("jpg", "png", "gif", "webp", "apng"), default="jpg")
     ap.add_argument("--gif-files", type=int, default=32,
-                    help="--format gif / webp: files the frames are spread over")
+                    help="--format gif / webp / apng: files the frames are spread over")
     ap.add_argument("--frames", type=int, default=1024)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--quality", type=int, default=95)
@@ -552,6 +727,10 @@ def main(argv=None) -> int:
         if args.out is None:
             args.out = str(REPO / "profiles" / "webp_decode_device.json")
         return bench_webp(args)
+    if args.format == "apng":
+        if args.out is None:
+            args.out = str(REPO / "profiles" / "apng_decode_device.json")
+        return bench_apng(args)
     if args.out is None:
         args.out = str(REPO / "profiles" / ("jpeg_decode.json" if args.entropy == "host" else "jpeg_decode_device.json"))
 

@@ -1,6 +1,6 @@
 // The gather kernel of the device decoders that read a stream cut into pieces (vge_png.hip: IDAT chunks; vge_gif.hip:
-// data sub-blocks): one workgroup per segment copies a payload to its place in the frame's gathered run of the
-// workspace, so that the bit reader sees one contiguous stream however the writer cut it.
+// data sub-blocks; vge_apng.hip: IDAT and fdAT chunks): one workgroup per segment copies a payload to its place in the
+// frame's gathered run of the workspace, so that the bit reader sees one contiguous stream however the writer cut it.
 //
 // Route supplies the call's argument struct and its descriptor check:
 //   Route::Args          with data, descs, segs, n_segs, n_descs, ws; descriptors with file_off, file_bytes, gat_off,

@@ -1,7 +1,6 @@
 // The host half of the PNG frame front end (include/vge_png.h): the chunk parser, the probe, the host decoder (zlib's
-// inflate and a plain C++ unfilter, one frame per thread) and the plan of the device route.  Plain C++ and zlib: no HIP.
-#include <zlib.h>
-
+// inflate and a plain C++ unfilter, vge_png_host.h, one frame per thread) and the plan of the device route.  Plain C++
+// and zlib: no HIP.
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
@@ -12,10 +11,15 @@
 #include "../../include/vge_png.h"
 #include "vge_error.h"
 #include "vge_host_files.h"
+#include "vge_png_host.h"
 
 using vge::Mapped;
 using vge::parallel_for;
 using vge::set_last_error;
+using vge_png_host::bytes_per_pixel;
+using vge_png_host::Chunk;
+using vge_png_host::inflate_chunks;
+using vge_png_host::unfilter;
 
 namespace {
 
@@ -35,12 +39,6 @@ const char* status_name(int st) {
 inline uint32_t be32(const uint8_t* p) {
   return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3];
 }
-
-struct Chunk {
-  size_t off, len;  // payload inside the file
-};
-
-inline int bytes_per_pixel(int color_type) { return color_type == 0 ? 1 : color_type == 2 ? 3 : color_type == 4 ? 2 : 4; }
 
 // The chunk walk: signature, IHDR, then every chunk up to the end of the one run of IDATs.  idat (may be NULL) receives
 // the payload ranges, empty chunks included.  A chunk that runs past the file before the IDAT run has ended is a
@@ -95,38 +93,6 @@ int check_layout(const vge_png_info& info, int width, int height, int color_type
   return info.width == width && info.height == height && info.color_type == color_type ? VGE_PNG_OK : VGE_PNG_ERR_SHAPE;
 }
 
-inline int paeth(int a, int b, int c) {
-  const int pa = std::abs(b - c), pb = std::abs(a - c), pc = std::abs(a + b - 2 * c);
-  return pa <= pb && pa <= pc ? a : pb <= pc ? b : c;
-}
-
-// Filtered rows -> RGB rows; false: a filter byte above 4.  raw is reconstructed in place.
-bool unfilter(uint8_t* raw, int width, int height, int color_type, uint8_t* rgb) {
-  const int bpp = bytes_per_pixel(color_type);
-  const size_t rowb = (size_t)width * bpp, stride = 1 + rowb;
-  for (int y = 0; y < height; ++y)
-    if (raw[y * stride] > 4) return false;
-  for (int y = 0; y < height; ++y) {
-    uint8_t* cur = raw + y * stride + 1;
-    const uint8_t* up = y ? cur - stride : nullptr;
-    const int ft = cur[-1];
-    for (size_t i = 0; i < rowb; ++i) {
-      const int a = i >= (size_t)bpp ? cur[i - bpp] : 0, b = up ? up[i] : 0, c = up && i >= (size_t)bpp ? up[i - bpp] : 0;
-      const int pred = ft == 0 ? 0 : ft == 1 ? a : ft == 2 ? b : ft == 3 ? (a + b) >> 1 : paeth(a, b, c);
-      cur[i] = (uint8_t)(cur[i] + pred);
-    }
-    uint8_t* out = rgb + (size_t)y * width * 3;
-    for (int x = 0; x < width; ++x) {
-      const uint8_t* px = cur + (size_t)x * bpp;
-      const bool grey = bpp < 3;
-      out[3 * x] = px[0];
-      out[3 * x + 1] = px[grey ? 0 : 1];
-      out[3 * x + 2] = px[grey ? 0 : 2];
-    }
-  }
-  return true;
-}
-
 int decode_one(const uint8_t* p, size_t n, int width, int height, int color_type, uint8_t* rgb) {
   vge_png_info info;
   std::vector<Chunk> idat;
@@ -134,33 +100,8 @@ int decode_one(const uint8_t* p, size_t n, int width, int height, int color_type
   if (st == VGE_PNG_OK) st = check_layout(info, width, height, color_type);
   if (st != VGE_PNG_OK) return st;
   const size_t count = (size_t)height * (1 + (size_t)width * bytes_per_pixel(color_type));
-  std::vector<uint8_t> raw(count + 1);  // one spare byte: zlib reads on through the end of the stream and its trailer
-  z_stream zs;
-  memset(&zs, 0, sizeof(zs));
-  if (inflateInit(&zs) != Z_OK) return VGE_PNG_ERR_IO;
-  zs.next_out = raw.data();
-  size_t out_left = raw.size();
-  bool bad = false, done = false;
-  for (const Chunk& c : idat) {
-    size_t in_left = c.len;
-    const uint8_t* in = p + c.off;
-    while (in_left > 0 && !bad && !done) {
-      const uInt ai = (uInt)std::min<size_t>(in_left, 1u << 30), ao = (uInt)std::min<size_t>(out_left, 1u << 30);
-      zs.next_in = const_cast<Bytef*>(in);
-      zs.avail_in = ai;
-      zs.avail_out = ao;
-      const int r = inflate(&zs, Z_NO_FLUSH);
-      in += ai - zs.avail_in;
-      in_left -= ai - zs.avail_in;
-      out_left -= ao - zs.avail_out;
-      if (r == Z_STREAM_END || out_left == 0) done = true;
-      else if (r != Z_OK && r != Z_BUF_ERROR) bad = true;  // Z_DATA_ERROR, Z_NEED_DICT (FDICT), Z_MEM_ERROR
-      else if (r == Z_BUF_ERROR && zs.avail_in == ai) bad = true;  // no progress: cannot happen with room on both sides
-    }
-    if (bad || done) break;
-  }
-  inflateEnd(&zs);
-  if (bad || raw.size() - out_left < count) return VGE_PNG_ERR_IO;
+  std::vector<uint8_t> raw;
+  if (!inflate_chunks(p, idat, count, raw)) return VGE_PNG_ERR_IO;
   return unfilter(raw.data(), width, height, color_type, rgb) ? VGE_PNG_OK : VGE_PNG_ERR_IO;
 }
 

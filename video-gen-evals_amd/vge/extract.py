@@ -324,7 +324,9 @@ def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root
     is the stem): the frames are the GIF's composed frames (include/vge_gif.h), frame_idx indexes them, pass packing
     uses the probe's frame counts and jpeg_quality applies as for PNG.  A GIF's frames from the first undecodable one
     onward are dropped (they are deltas on it).  frame_format "webp" reads <action>/<video>.webp, one lossless WebP
-    file per video (include/vge_webp.h), in exactly the same way.
+    file per video (include/vge_webp.h), in exactly the same way, and frame_format "apng" reads <action>/<video>.png
+    and <action>/<video>.apng, one animated PNG per video (include/vge_apng.h); when both files exist the .apng is
+    used, and a line says so.
 
     Per action, <log_root>/single/<action>.json and not_single/<action>.json (lists of video names) and
     errors/<action>.json ({video: message}) are rewritten after every video.  A video already in the single or
@@ -343,11 +345,13 @@ def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root
     (vge.frames.load_frames).
     Returns {action: {"single": [...], "not_single": [...], "errors": [...], "skipped": [...]}} for this run."""
     from . import frames as FR
-    if frame_format not in ("jpg", "png", "gif", "webp"):
-        raise ValueError(f"frame_format must be 'jpg', 'png', 'gif' or 'webp', not {frame_format!r}")
+    if frame_format not in ("jpg", "png", "gif", "webp", "apng"):
+        raise ValueError(f"frame_format must be 'jpg', 'png', 'gif', 'webp' or 'apng', not {frame_format!r}")
     ext = "." + frame_format
-    is_gif = frame_format in ("gif", "webp")   # a video is one file
-    probe_file = FR.webp_probe if frame_format == "webp" else FR.gif_probe
+    is_gif = frame_format in ("gif", "webp", "apng")   # a video is one file
+    exts = (".png", ".apng") if frame_format == "apng" else (ext,)   # the later suffix wins when both files exist
+    probe_file = {"webp": FR.webp_probe, "apng": FR.apng_probe}.get(frame_format, FR.gif_probe)
+    count_col = 5 if frame_format == "apng" else 2   # the probe row's frame count
     frames_root, log_root = Path(frames_root), Path(log_root)
     all_actions = sorted(d.name for d in frames_root.iterdir() if d.is_dir())
     if actions is None:
@@ -361,12 +365,19 @@ def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root
     for action in actions:
         action_dir = frames_root / action
         if is_gif:
-            videos = sorted(p.stem for p in action_dir.iterdir() if p.is_file() and p.suffix == ext)
+            files = [p for p in action_dir.iterdir() if p.is_file() and p.suffix in exts]
+            videos = sorted({p.stem for p in files})
+            for v in videos:
+                if sum(p.stem == v for p in files) > 1:
+                    print(f"[WARN] {action}/{v}: both {v}{exts[0]} and {v}{exts[-1]} exist, using {v}{exts[-1]}")
         else:
             videos = sorted(d.name for d in action_dir.iterdir() if d.is_dir())
 
         def source(video):
-            return action_dir / (video + ext if is_gif else video)
+            if not is_gif:
+                return action_dir / video
+            found = [e for e in exts if (action_dir / (video + e)).is_file()]
+            return action_dir / (video + (found[-1] if found else exts[0]))
         single_path = log_root / "single" / f"{action}.json"
         not_path = log_root / "not_single" / f"{action}.json"
         err_path = log_root / "errors" / f"{action}.json"
@@ -406,7 +417,7 @@ def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root
                 continue
             todo.append((video, str(source(video)) if is_gif else FR.list_frames(action_dir / video, ext=ext)))
         if is_gif:   # a video is one file: the probe gives its frame count
-            counts = probe_file([p for _, p in todo], threads)[:, 2] if todo else []
+            counts = probe_file([p for _, p in todo], threads)[:, count_col] if todo else []
             entries = []
             for (v, p), n in zip(todo, counts):
                 if int(n) > 0:
@@ -507,9 +518,9 @@ def main(argv=None) -> int:
     ap.add_argument("--threads", type=int, default=0, help="frame decode threads (0: the ingest default)")
     ap.add_argument("--entropy", choices=("host", "device"), default="host",
                     help="where the frames' Huffman decoding (PNG: inflate and unfilter) runs (vge.frames.load_frames)")
-    ap.add_argument("--frame-format", choices=("jpg", "png", "gif", "webp"), default="jpg",
-                    help="the frame files each video folder holds; gif / webp: each video is one animated <video>.gif "
-                         "or lossless <video>.webp")
+    ap.add_argument("--frame-format", choices=("jpg", "png", "gif", "webp", "apng"), default="jpg",
+                    help="the frame files each video folder holds; gif / webp / apng: each video is one animated "
+                         "<video>.gif, lossless <video>.webp or animated <video>.png / <video>.apng")
     ap.add_argument("--jpeg-quality", type=int, default=None,
                     help="send the decoded frames through a JPEG round trip of this quality before the models "
                          "(the reference's cache is 95; meant for PNG frames)")

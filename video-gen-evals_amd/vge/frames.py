@@ -28,6 +28,10 @@ packed in host memory.
 A lossless WebP file (include/vge_webp.h) is a video in one file in the same way (load_frames("clip.webp"),
 decode_webps; vge_webp_decode on host threads, or vge_webp_plan_mem and vge_webp_decode_device, csrc/vge_webp.hip, on
 the uploaded file bytes), and a folder or list of still .webp files is a video of one frame per file.
+
+An animated PNG (include/vge_apng.h) given as the path of one file is a video in the same way (load_frames("clip.png"),
+decode_apngs; vge_apng_decode on host threads, or vge_apng_plan_mem and vge_apng_decode_device, csrc/vge_apng.hip, on
+the uploaded file bytes): the frames are what PIL.ImageSequence gives after .convert("RGB").
 """
 from __future__ import annotations
 
@@ -717,6 +721,189 @@ def decode_webps(data, offsets, device=None, threads: int = 0, entropy: Optional
     return _decode_webp_files(names, None, data, starts, sizes, info, device, threads, entropy)
 
 
+# ---- APNG videos (include/vge_apng.h)
+
+def _apng_rows(info, n: int) -> np.ndarray:
+    return np.array([[i.width, i.height, i.color_type, i.bit_depth, i.interlace, i.n_frames, i.default_image,
+                      i.n_chunks, i.data_bytes, i.status] for i in info[:n]], dtype=np.int64).reshape(-1, 10)
+
+
+def apng_probe(paths: Sequence[PathLike], threads: int = 0) -> np.ndarray:
+    """Chunk headers only: int64 [n, 10] rows of (canvas width, canvas height, colour type, bit depth, interlace,
+    frames, whether frame 0 is a default image outside the animation, non-empty IDAT / fdAT payloads, their bytes,
+    status) (vge_apng_probe).  A PNG that is not animated is a video of one frame."""
+    paths = [os.fspath(p) for p in paths]
+    info = (L.ApngInfo * max(len(paths), 1))()
+    if paths:
+        L.load().vge_apng_probe(_paths_array(paths), len(paths), int(threads), info)
+    return _apng_rows(info, len(paths))
+
+
+def apng_probe_mem(data: np.ndarray, offsets: np.ndarray, sizes: np.ndarray, threads: int = 0) -> np.ndarray:
+    """apng_probe() for files in host memory: file i is data[offsets[i]:offsets[i] + sizes[i]] (vge_apng_probe_mem)."""
+    n = len(offsets)
+    info = (L.ApngInfo * max(n, 1))()
+    if n:
+        offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
+        L.load().vge_apng_probe_mem(data.ctypes.data, data.size, offsets.ctypes.data, sizes.ctypes.data, n,
+                                    int(threads), info)
+    return _apng_rows(info, n)
+
+
+def _apng_decode_group(paths, data, offsets, sizes, key, n_frames: int, device, threads: int):
+    """The APNG files of one (canvas width, canvas height, colour type) on host threads, from paths or (paths None)
+    from files in host memory (data: a uint8 CPU tensor) -> (uint8 [n_frames, H, W, 3] tensor on `device`, int32
+    status [n_frames]): vge_apng_decode / vge_apng_decode_mem into pinned memory, then one upload.  n_frames: the
+    probe's sum."""
+    import torch
+    lib = L.load()
+    w, h, ct = key
+    on_gpu = device.type == "cuda"
+    out = torch.empty((n_frames, h, w, 3), dtype=torch.uint8, pin_memory=on_gpu)
+    status = np.zeros(n_frames, np.int32)
+    if paths is not None:
+        lib.vge_apng_decode(_paths_array(paths), len(paths), int(threads), w, h, ct, n_frames, out.data_ptr(),
+                            status.ctypes.data, None, None)
+    else:
+        offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
+        lib.vge_apng_decode_mem(data.data_ptr(), int(data.numel()), offsets.ctypes.data, sizes.ctypes.data,
+                                len(offsets), int(threads), w, h, ct, n_frames, out.data_ptr(), status.ctypes.data,
+                                None, None)
+    if on_gpu:
+        with torch.cuda.device(device):
+            out = out.to(device, non_blocking=True)
+    return out, status
+
+
+def _apng_decode_group_device(data_h: np.ndarray, data_d, offsets: np.ndarray, sizes: np.ndarray, key, n_frames: int,
+                              n_chunks: int, threads: int):
+    """The APNG files of one (canvas width, canvas height, colour type), their bytes both in host memory (data_h, which
+    only the plan's chunk walk reads) and on the GPU (data_d) -> (uint8 [n_frames, H, W, 3] tensor on that GPU, int32
+    status [n_frames]): vge_apng_plan_mem on the host, one upload of the descriptors and segments,
+    vge_apng_decode_device on the current stream; the one host synchronisation is the copy of the statuses at the end.
+    n_frames, n_chunks: the probe's sums."""
+    import torch
+    lib = L.load()
+    dev = data_d.device
+    w, h, ct = key
+    offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
+    descs = (L.ApngDesc * max(n_frames, 1))()
+    segs = (L.ApngSegment * max(n_chunks, 1))()
+    planned = np.zeros(max(n_frames, 1), np.int32)
+    n_descs, n_segs, ws_bytes = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    lib.vge_apng_plan_mem(data_h.ctypes.data, data_h.size, offsets.ctypes.data, sizes.ctypes.data, len(offsets),
+                          int(threads), w, h, ct, descs, n_frames, C.byref(n_descs), segs, n_chunks, C.byref(n_segs),
+                          planned.ctypes.data, None, C.byref(ws_bytes))
+    if n_descs.value != n_frames:
+        raise L.VgeError("vge_apng_plan_mem: " + lib.vge_last_error().decode(errors="replace"))
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        descs_d = torch.frombuffer(descs, dtype=torch.uint8).to(dev)
+        segs_d = torch.frombuffer(segs, dtype=torch.uint8).to(dev)
+        ws = torch.empty(int(ws_bytes.value), dtype=torch.uint8, device=dev)
+        status_d = torch.empty(n_frames, dtype=torch.int32, device=dev)
+        out = torch.empty((n_frames, h, w, 3), dtype=torch.uint8, device=dev)
+        L.check(lib.vge_apng_decode_device(data_d.data_ptr(), int(data_d.numel()), descs_d.data_ptr(), n_frames,
+                                           segs_d.data_ptr(), n_segs.value, n_frames, len(offsets), w, h, ct,
+                                           ws.data_ptr(), int(ws.numel()), out.data_ptr(), status_d.data_ptr(),
+                                           stream.cuda_stream),
+                "vge_apng_decode_device")
+        status = status_d.cpu().numpy()
+    planned = planned[:n_frames]
+    return out, np.where(planned != 0, planned, status).astype(np.int32)
+
+
+def _keep_apng_frames(name, out, status, device):
+    """(frames, kept) of one APNG video: the frames in front of the first one that failed."""
+    bad = np.flatnonzero(status != 0)
+    n = int(bad[0]) if bad.size else len(status)
+    if bad.size:
+        log.warning("dropping frames %d.. of %s: %s", n, name, L.APNG_STATUS.get(int(status[n]), int(status[n])))
+    return out[:n], np.arange(n, dtype=np.int64)
+
+
+def _decode_apng_files(names, paths, raw, raw_off, raw_size, info, device, threads: int, entropy: str):
+    """The APNG videos of a call, from paths (host route) or from their bytes in one host tensor `raw` -> one
+    (frames, kept) per file.  info: their probe rows.  Files of one canvas and colour type share one call."""
+    import torch
+    _raise_unsupported_png(names, info[:, -1])
+    results: List[Optional[Tuple]] = [None] * len(names)
+    groups: dict = {}
+    for i, row in enumerate(info):
+        if int(row[5]) > 0 and int(row[-1]) != 1:   # a file with frames, of a size the decoders take
+            groups.setdefault((int(row[0]), int(row[1]), int(row[2])), []).append(i)
+        else:
+            log.warning("no decodable frame in %s: %s", names[i], L.APNG_STATUS.get(int(row[-1]), int(row[-1])))
+            results[i] = _empty_video(device)
+    raw_d = None
+    if entropy == "device" and groups:
+        with torch.cuda.device(device):
+            raw_d = raw.to(device, non_blocking=True)   # the one upload: every group decodes out of this buffer
+    for key, members in groups.items():
+        counts = [int(info[i, 5]) for i in members]
+        total, chunks = sum(counts), int(sum(info[i, 7] for i in members))
+        if entropy == "device":
+            with torch.cuda.device(device):
+                out, status = _apng_decode_group_device(raw.numpy(), raw_d, raw_off[members], raw_size[members], key,
+                                                        total, chunks, threads)
+        elif paths is not None:
+            out, status = _apng_decode_group([paths[i] for i in members], None, None, None, key, total, device,
+                                             threads)
+        else:
+            out, status = _apng_decode_group(None, raw, raw_off[members], raw_size[members], key, total, device,
+                                             threads)
+        o = 0
+        for i, n in zip(members, counts):
+            results[i] = _keep_apng_frames(names[i], out[o:o + n], status[o:o + n], device)
+            if results[i][1].size == 0:
+                log.warning("no decodable frame in %s", names[i])
+            o += n
+    return results
+
+
+def _load_apng_videos(paths: List[str], device, threads: int, entropy: str):
+    """load_videos for the APNG videos of a call."""
+    if entropy == "device":
+        raw, raw_off, raw_size = _read_files(paths, threads, pin=True)
+        info = apng_probe_mem(raw.numpy(), raw_off, raw_size, threads)
+        return _decode_apng_files(paths, None, raw, raw_off, raw_size, info, device, threads, entropy)
+    return _decode_apng_files(paths, paths, None, None, None, apng_probe(paths, threads), device, threads, entropy)
+
+
+def decode_apngs(data, offsets, device=None, threads: int = 0, entropy: Optional[str] = None):
+    """APNG videos packed in host memory -- (data, offsets[F + 1]): file i at data[offsets[i]:offsets[i + 1]] of a
+    one-dimensional uint8 CPU tensor -- -> one (frames, kept) per file, as load_videos gives them.  entropy "host" (the
+    default without a GPU) decodes on host threads (vge_apng_decode_mem) and uploads the pixels to `device`; entropy
+    "device" (the default with one) uploads the file bytes and runs vge_apng_plan_mem and vge_apng_decode_device.  The
+    plan walks every chunk of every file on the host, so a buffer that lives on a GPU is refused, not copied back."""
+    import torch
+    if not (isinstance(data, torch.Tensor) and data.dtype == torch.uint8 and data.dim() == 1):
+        raise ValueError("data must be a one-dimensional uint8 tensor")
+    if data.device.type != "cpu":
+        raise ValueError("decode_apngs needs the file bytes in host memory: the plan walks every chunk on the host; "
+                         "pass a CPU tensor (entropy='device' uploads it once)")
+    off = np.ascontiguousarray(offsets.cpu().numpy() if isinstance(offsets, torch.Tensor) else offsets, np.int64)
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError("offsets must be int64 [F + 1]")
+    device = _resolve_device(device)
+    if entropy is None:
+        entropy = "device" if device.type == "cuda" else "host"
+    if entropy not in ("host", "device"):
+        raise ValueError(f"entropy must be 'host' or 'device', not {entropy!r}")
+    if entropy == "device" and device.type != "cuda":
+        raise ValueError("entropy='device' needs a GPU")
+    F = off.size - 1
+    if F == 0:
+        return []
+    starts, sizes = off[:F].copy(), np.diff(off)
+    if (sizes < 0).any() or off[0] < 0 or off[F] > data.numel():
+        raise ValueError("offsets must be non-decreasing and inside data")
+    data = data.contiguous()
+    names = [f"file {i}" for i in range(F)]
+    info = apng_probe_mem(data.numpy(), starts, sizes, threads)
+    return _decode_apng_files(names, None, data, starts, sizes, info, device, threads, entropy)
+
+
 def _first_good_key(rows: np.ndarray, n_key: int):
     """The layout of a video: its first readable frame's leading probe columns (the last column is the status)."""
     good = np.flatnonzero(rows[:, -1] == 0)
@@ -1060,7 +1247,12 @@ def load_videos(videos: Sequence[Union[PathLike, Sequence[PathLike]]], device=No
     vge_webp_decode_device on the uploaded file bytes.  A folder without *.jpg and *.png files gives its *.webp files,
     and a list whose first file is a WebP is a list of still WebP frames: every file is one frame, and all must have
     one size.  UnsupportedWebpError names a file with a lossy frame, a frame outside its canvas or more prefix-code
-    groups than the decoders hold."""
+    groups than the decoders hold.
+    An entry that is a path to a regular file with the PNG signature is an APNG video (include/vge_apng.h), handled as a
+    GIF video is: vge_apng_decode on host threads, or vge_apng_plan_mem and vge_apng_decode_device on the uploaded file
+    bytes; APNG videos of one (canvas, colour type) share one call, and a PNG file that is not animated is a video of
+    one frame.  UnsupportedPngError names an interlaced, non-8-bit or palette file.  Inside a folder or a list, a PNG
+    file stays one still frame (its IDAT picture), animated or not."""
     device = _resolve_device(device)
     if entropy not in ("host", "device"):
         raise ValueError(f"entropy must be 'host' or 'device', not {entropy!r}")
@@ -1069,11 +1261,18 @@ def load_videos(videos: Sequence[Union[PathLike, Sequence[PathLike]]], device=No
     is_webp = [isinstance(v, (str, os.PathLike)) and _is_webp_file(os.fspath(v)) for v in videos]
     is_gif = [isinstance(v, (str, os.PathLike)) and not wp and _is_gif_file(os.fspath(v))
               for v, wp in zip(videos, is_webp)]
-    vids = [[] if g or wp else _list_video(v) if isinstance(v, (str, os.PathLike)) else [os.fspath(p) for p in v]
-            for v, g, wp in zip(videos, is_gif, is_webp)]
+    is_apng = [isinstance(v, (str, os.PathLike)) and not wp and not g and _is_apng_file(os.fspath(v))
+               for v, wp, g in zip(videos, is_webp, is_gif)]
+    one_file = [g or wp or a for g, wp, a in zip(is_gif, is_webp, is_apng)]   # a video in one file: no frame list
+    vids = [[] if one else _list_video(v) if isinstance(v, (str, os.PathLike)) else [os.fspath(p) for p in v]
+            for v, one in zip(videos, one_file)]
     is_png = [_is_png_file(v[0]) if v else False for v in vids]
     is_stills = [bool(v) and _is_webp_file(v[0]) for v in vids]
     results: List[Optional[Tuple]] = [None] * len(vids)
+    apngs = [vi for vi, a in enumerate(is_apng) if a]
+    if apngs:
+        for vi, r in zip(apngs, _load_apng_videos([os.fspath(videos[vi]) for vi in apngs], device, threads, entropy)):
+            results[vi] = r
     gifs = [vi for vi, g in enumerate(is_gif) if g]
     if gifs:
         for vi, r in zip(gifs, _load_gif_videos([os.fspath(videos[vi]) for vi in gifs], device, threads, entropy)):
@@ -1087,8 +1286,7 @@ def load_videos(videos: Sequence[Union[PathLike, Sequence[PathLike]]], device=No
         for vi, r in zip(stills, _load_webp_still_videos([vids[vi] for vi in stills], device, threads, entropy)):
             results[vi] = r
     for png, load in ((False, _load_jpeg_videos), (True, _load_png_videos)):
-        which = [vi for vi, k in enumerate(is_png)
-                 if k == png and not is_gif[vi] and not is_webp[vi] and not is_stills[vi]]
+        which = [vi for vi, k in enumerate(is_png) if k == png and not one_file[vi] and not is_stills[vi]]
         if which:
             for vi, r in zip(which, load([vids[vi] for vi in which], device, threads, entropy)):
                 results[vi] = r
@@ -1120,6 +1318,14 @@ def _is_gif_file(path: str) -> bool:
             return False
         with open(path, "rb") as f:
             return f.read(6) in GIF_SIGNATURES
+    except OSError:
+        return False
+
+
+def _is_apng_file(path: str) -> bool:
+    """A path to a regular file with the PNG signature: an APNG video (a still PNG is a video of one frame)."""
+    try:
+        return os.path.isfile(path) and _is_png_file(path)
     except OSError:
         return False
 
@@ -1230,8 +1436,8 @@ def load_frames(paths_or_dir: Union[PathLike, Sequence[PathLike]], device=None, 
                 entropy: str = "host"):
     """load_frames_from_images (extract_mesh.py:72-82) on the GPU.  paths_or_dir: a frame folder (its *.jpg files in
     sorted order; its *.png files when it has no *.jpg), a list of JPEG paths, or of PNG paths, or the path of an
-    animated GIF or of a lossless WebP file, whose frames are the video's frames, or a folder or list of still WebP
-    frames.
+    animated GIF, of a lossless WebP file or of an animated PNG, whose frames are the video's frames, or a folder or
+    list of still WebP frames.
     Returns (frames, kept): uint8 [F', H, W, 3] RGB on `device` (default: the
     current GPU when there is one, else the CPU) and the indices of the frames that decoded.  A frame that fails to
     decode is dropped with a log message, as the reference drops a None from cv2.imread; an unsupported kind of JPEG

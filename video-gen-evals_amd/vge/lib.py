@@ -60,6 +60,8 @@ EXPORTS = ["vge_featurize", "vge_featurize_layout", "vge_layout_feat_dim", "vge_
            "vge_gif_decode_device", "vge_gif_decode_device_workspace_bytes",
            "vge_webp_probe", "vge_webp_probe_mem", "vge_webp_decode", "vge_webp_decode_mem", "vge_webp_plan_mem",
            "vge_webp_decode_device", "vge_webp_decode_device_workspace_bytes", "vge_webp_slot_bytes",
+           "vge_apng_probe", "vge_apng_probe_mem", "vge_apng_decode", "vge_apng_decode_mem", "vge_apng_plan_mem",
+           "vge_apng_decode_device", "vge_apng_decode_device_workspace_bytes",
            "vge_time_gather", "vge_tcl_workspace_bytes", "vge_tcl_loss", "vge_hardneg_loss", "vge_centroid_distance"]
 
 
@@ -178,6 +180,27 @@ WEBP_UNSUPPORTED = {50: "a lossy (VP8 / ALPH) frame",
 WEBP_MAX_GROUPS = 256   # include/vge_webp.h VGE_WEBP_MAX_GROUPS
 
 
+class ApngInfo(C.Structure):  # include/vge_apng.h vge_apng_info
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("color_type", C.c_int32), ("bit_depth", C.c_int32),
+                ("interlace", C.c_int32), ("n_frames", C.c_int32), ("default_image", C.c_int32), ("status", C.c_int32),
+                ("n_chunks", C.c_int64), ("data_bytes", C.c_int64)]
+
+
+class ApngDesc(C.Structure):  # include/vge_apng.h vge_apng_desc
+    _fields_ = [("file_off", C.c_int64), ("file_bytes", C.c_int64), ("gat_off", C.c_int64), ("gat_bytes", C.c_int64),
+                ("slot_off", C.c_int64), ("raw_bytes", C.c_int64), ("file", C.c_int32), ("index", C.c_int32),
+                ("frame", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32),
+                ("color_type", C.c_int32), ("dispose_op", C.c_int32), ("blend_op", C.c_int32), ("trns", C.c_int32),
+                ("plan_status", C.c_int32)]
+
+
+ApngSegment = PngSegment  # include/vge_apng.h vge_apng_segment: the same shape
+
+APNG_STATUS = {0: "OK", 1: "ERR_ARG", 2: "ERR_HIP", 7: "ERR_IO", 8: "ERR_SHAPE", 30: "ERR_INTERLACED",
+               31: "ERR_BITDEPTH", 32: "ERR_PALETTE", 60: "ERR_BOUNDS"}
+APNG_UNSUPPORTED = PNG_UNSUPPORTED   # the kinds the still path refuses by name, in the same words
+
+
 class FrameStoreC(C.Structure):
     _fields_ = [("pose", C.c_void_p), ("gori", C.c_void_p), ("betas", C.c_void_p), ("vit", C.c_void_p),
                 ("kp", C.c_void_p), ("videos", C.c_void_p), ("n_videos", C.c_int)]
@@ -278,6 +301,15 @@ def load() -> C.CDLL:
         "vge_gif_decode_device": [vp, C.c_int64, vp, i32, vp, C.c_int64, i32, i32, i32, i32, vp, C.c_int64, vp, vp,
                                   vp],
         "vge_gif_decode_device_workspace_bytes": [C.POINTER(GifDesc), i32],
+        "vge_apng_probe": [C.POINTER(C.c_char_p), i32, i32, C.POINTER(ApngInfo)],
+        "vge_apng_probe_mem": [vp, C.c_int64, vp, vp, i32, i32, C.POINTER(ApngInfo)],
+        "vge_apng_decode": [C.POINTER(C.c_char_p), i32, i32, i32, i32, i32, C.c_int64, vp, vp, vp, i64p],
+        "vge_apng_decode_mem": [vp, C.c_int64, vp, vp, i32, i32, i32, i32, i32, C.c_int64, vp, vp, vp, i64p],
+        "vge_apng_plan_mem": [vp, C.c_int64, vp, vp, i32, i32, i32, i32, i32, C.POINTER(ApngDesc), C.c_int64, i64p,
+                              C.POINTER(ApngSegment), C.c_int64, i64p, vp, vp, i64p],
+        "vge_apng_decode_device": [vp, C.c_int64, vp, i32, vp, C.c_int64, i32, i32, i32, i32, i32, vp, C.c_int64, vp,
+                                   vp, vp],
+        "vge_apng_decode_device_workspace_bytes": [C.POINTER(ApngDesc), i32],
         "vge_webp_probe": [C.POINTER(C.c_char_p), i32, i32, C.POINTER(WebpInfo)],
         "vge_webp_probe_mem": [vp, C.c_int64, vp, vp, i32, i32, C.POINTER(WebpInfo)],
         "vge_webp_decode": [C.POINTER(C.c_char_p), i32, i32, i32, i32, C.c_int64, vp, vp, vp, i64p],
@@ -305,6 +337,7 @@ def load() -> C.CDLL:
     lib.vge_png_decode_device_workspace_bytes.restype = C.c_size_t
     lib.vge_gif_decode_device_workspace_bytes.restype = C.c_size_t
     lib.vge_webp_decode_device_workspace_bytes.restype = C.c_size_t
+    lib.vge_apng_decode_device_workspace_bytes.restype = C.c_size_t
     lib.vge_webp_slot_bytes.restype = C.c_int64
     lib.vge_last_error.restype = C.c_char_p
     lib.vge_version.restype = C.c_char_p
