@@ -85,30 +85,122 @@ def spread(xs):
     return {"median": statistics.median(xs), "min": min(xs), "max": max(xs), "n": len(xs)}
 
 
-def write_jpegs(folder: Path, n: int, size: int, quality: int):
+def gpu():
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_frames.py needs a GPU")
+    return torch.device("cuda:0")
+
+
+def events(fn, inner=1):
+    """Seconds per call of fn between two device events, over `inner` calls."""
+    import torch
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(inner):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1e-3 / inner
+
+
+def clocked(lib, call, also=lambda: True):
+    """Host seconds of one C call that has to return 0 (and leave `also` true)."""
+    t = time.perf_counter()
+    rc = call()
+    dt = time.perf_counter() - t
+    assert rc == 0 and also(), lib.vge_last_error()
+    return dt
+
+
+def staged(set_mask, mask, whole, device_call):
+    """One kernel of the device call alone (a hook of the library for this tool), on the data the others left."""
+    set_mask(mask)
+    try:
+        return events(device_call)
+    finally:
+        set_mask(whole)
+
+
+def e2e(videos, n, dev, threads, entropy):
+    """load_videos ending in a device synchronise -> (host seconds, every frame); all n frames have to decode."""
+    import torch
+    from vge import frames as FR
+    t = time.perf_counter()
+    out = FR.load_videos(videos, device=dev, threads=threads, entropy=entropy)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t
+    assert sum(k.size for _, k in out) == n
+    return dt, torch.cat([f for f, _ in out])
+
+
+def measure_calls(args, host_decode, plan, device_call, warm_e2e):
+    """Warm up everything, then the three stages every format has -> res."""
+    for _ in range(args.warmup):
+        host_decode(); events(device_call); warm_e2e()
+    return {"host_decode_s": spread([host_decode() for _ in range(args.repeats)]),
+            "plan_s": spread([plan() for _ in range(args.repeats)]),
+            "device_call_s": spread([events(device_call) for _ in range(args.repeats)])}
+
+
+def measure_e2e(args, res, videos, n, dev, more=()):
+    """The host route, then the device route, then `more` (name, videos, entropy) of load_videos into res -> whether
+    the two routes gave the same frames."""
+    import torch
+    runs = [("e2e_host", videos, "host"), ("e2e_device", videos, "device"), *more]
+    took = [[e2e(v, n, dev, args.threads, entropy) for _ in range(args.repeats)] for _, v, entropy in runs]
+    for (name, _, _), r in zip(runs, took):
+        res[f"{name}_s"] = spread([t for t, _ in r])
+    return bool(torch.equal(took[1][-1][1], took[0][-1][1]))
+
+
+def rates(res, n):
+    return {"stages": res, "ms_per_pass": {key[:-2]: 1e3 * v["median"] for key, v in res.items()},
+            "frames_per_s": {key[:-2]: n / v["median"] for key, v in res.items()}}
+
+
+def write_report(args, report) -> int:
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(report, f, indent=1)
+    print(json.dumps(report))
+    return 0
+
+
+def write_frames(folder: Path, n: int, size: int, ext: str, **save):
+    """vge.synth.make_frames content, one file per frame, as Pillow saves it."""
     from PIL import Image
     from vge import synth
     paths = []
     for v in range((n + 63) // 64):
         fr = synth.make_frames(1000 + v, min(64, n - 64 * v), h=size, w=size)
         for f in range(fr.shape[0]):
-            p = folder / f"frame_{64 * v + f:06d}.jpg"
-            Image.fromarray(fr[f]).save(p, format="JPEG", quality=quality, subsampling=2)
+            p = folder / f"frame_{64 * v + f:06d}{ext}"
+            Image.fromarray(fr[f]).save(p, **save)
             paths.append(str(p))
     return paths
 
 
+def write_jpegs(folder: Path, n: int, size: int, quality: int):
+    return write_frames(folder, n, size, ".jpg", format="JPEG", quality=quality, subsampling=2)
+
+
 def write_pngs(folder: Path, n: int, size: int):
-    """vge.synth.make_frames content as Pillow writes it at level 6: its adaptive choice mixes the five filter types."""
+    """Pillow at level 6: its adaptive choice mixes the five filter types."""
+    return write_frames(folder, n, size, ".png", format="PNG", compress_level=6)
+
+
+def write_clips(folder: Path, n_files: int, per_file: int, size: int, ext: str, **save):
+    """vge.synth.make_frames content, one animated file per clip, as Pillow saves RGB frames with save_all=True."""
     from PIL import Image
     from vge import synth
     paths = []
-    for v in range((n + 63) // 64):
-        fr = synth.make_frames(1000 + v, min(64, n - 64 * v), h=size, w=size)
-        for f in range(fr.shape[0]):
-            p = folder / f"frame_{64 * v + f:06d}.png"
-            Image.fromarray(fr[f]).save(p, format="PNG", compress_level=6)
-            paths.append(str(p))
+    for v in range(n_files):
+        fr = synth.make_frames(1000 + v, per_file, h=size, w=size)
+        ims = [Image.fromarray(fr[f]) for f in range(per_file)]
+        p = folder / f"clip_{v:04d}{ext}"
+        ims[0].save(p, save_all=True, append_images=ims[1:], duration=100, loop=0, **save)
+        paths.append(str(p))
     return paths
 
 
@@ -116,11 +208,10 @@ def bench_png(args) -> int:
     """--format png: both routes of load_frames on a PNG folder, the device call's kernels one by one, and the JPEG
     device route on the same frames beside them."""
     import torch
+    import zlib
     from vge import frames as FR
     from vge import lib as L
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_frames.py needs a GPU")
-    dev = torch.device("cuda:0")
+    dev = gpu()
     lib = L.load()
     tmp = tempfile.TemporaryDirectory()
     (Path(tmp.name) / "png").mkdir()
@@ -133,32 +224,15 @@ def bench_png(args) -> int:
     key = tuple(int(x) for x in rows[0, :3])
     w, h, ct = key
     filters = {}
-    import zlib
     for p in paths[:16]:   # which filter types the writer chose
         data = open(p, "rb").read()
         raw = zlib.decompress(b"".join(data[a:a + m] for a, m in _idat(data)))
         for t in raw[::1 + w * 3]:
             filters[int(t)] = filters.get(int(t), 0) + 1
 
-    def e2e(which, entropy):
-        t = time.perf_counter()
-        fr, kept = FR.load_frames(which, device=dev, threads=args.threads, entropy=entropy)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t
-        assert kept.size == n
-        return dt, fr
-
     out_h = torch.empty((n, h, w, 3), dtype=torch.uint8, pin_memory=True)
     status = np.zeros(n, np.int32)
     arr = (C.c_char_p * n)(*[os.fsencode(p) for p in paths])
-
-    def host_decode():
-        t = time.perf_counter()
-        rc = lib.vge_png_decode(arr, n, args.threads, w, h, ct, out_h.data_ptr(), status.ctypes.data)
-        dt = time.perf_counter() - t
-        assert rc == 0, lib.vge_last_error()
-        return dt
-
     raw, raw_off, raw_size = FR._read_files(paths, args.threads, pin=True)
     raw_d = raw.to(dev)
     descs = (L.PngDesc * n)()
@@ -167,14 +241,14 @@ def bench_png(args) -> int:
     seg_cap = int(rows[:, 5].sum())
     segs = (L.PngSegment * seg_cap)()
 
+    def host_decode():
+        return clocked(lib, lambda: lib.vge_png_decode(arr, n, args.threads, w, h, ct, out_h.data_ptr(),
+                                                       status.ctypes.data))
+
     def plan():
-        t = time.perf_counter()
-        rc = lib.vge_png_plan_mem(raw.data_ptr(), int(raw.numel()), raw_off.ctypes.data, raw_size.ctypes.data, n,
-                                  args.threads, w, h, ct, descs, segs, seg_cap, C.byref(n_segs), plan_st.ctypes.data,
-                                  C.byref(ws_bytes))
-        dt = time.perf_counter() - t
-        assert rc == 0, lib.vge_last_error()
-        return dt
+        return clocked(lib, lambda: lib.vge_png_plan_mem(
+            raw.data_ptr(), int(raw.numel()), raw_off.ctypes.data, raw_size.ctypes.data, n, args.threads, w, h, ct,
+            descs, segs, seg_cap, C.byref(n_segs), plan_st.ctypes.data, C.byref(ws_bytes)))
 
     plan()
     descs_d = torch.frombuffer(descs, dtype=torch.uint8).to(dev)
@@ -190,39 +264,21 @@ def bench_png(args) -> int:
                                           out_d.data_ptr(), status_d.data_ptr(), stream.cuda_stream),
                 "vge_png_decode_device")
 
-    def events(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b) * 1e-3
+    def stage(mask):
+        return staged(lib.vge_debug_png_stage_mask, mask, 15, device_call)
 
-    def stage(mask):   # one kernel of the call alone (a hook of the library for this tool), on the data the others left
-        lib.vge_debug_png_stage_mask(mask)
-        try:
-            return events(device_call)
-        finally:
-            lib.vge_debug_png_stage_mask(15)
+    def warm_e2e():
+        for videos, entropy in (([paths], "host"), ([paths], "device"), ([jpegs], "device")):
+            e2e(videos, n, dev, args.threads, entropy)
 
-    res = {}
-    for _ in range(args.warmup):
-        host_decode(); events(device_call); e2e(paths, "host"); e2e(paths, "device"); e2e(jpegs, "device")
-    res["host_decode_s"] = spread([host_decode() for _ in range(args.repeats)])
-    res["plan_s"] = spread([plan() for _ in range(args.repeats)])
-    res["device_call_s"] = spread([events(device_call) for _ in range(args.repeats)])
+    res = measure_calls(args, host_decode, plan, device_call, warm_e2e)
     assert int(status_d.abs().sum()) == 0
     calls_equal = bool(torch.equal(out_d.cpu(), out_h))
     for name, mask in (("gather", 1), ("inflate", 2), ("adler", 4)):   # each after a whole call, before the unfilter
         res[f"{name}_kernel_s"] = spread([stage(mask) for _ in range(args.repeats)])
     device_call()
     res["unfilter_kernel_s"] = spread([stage(8) for _ in range(args.repeats)])
-    eh = [e2e(paths, "host") for _ in range(args.repeats)]
-    ed = [e2e(paths, "device") for _ in range(args.repeats)]
-    ej = [e2e(jpegs, "device") for _ in range(args.repeats)]
-    res["e2e_host_s"] = spread([t for t, _ in eh])
-    res["e2e_device_s"] = spread([t for t, _ in ed])
-    res["e2e_jpeg_device_s"] = spread([t for t, _ in ej])
+    routes_equal = measure_e2e(args, res, [paths], n, dev, more=[("e2e_jpeg_device", [jpegs], "device")])
     report = {
         "what": "vge.frames.load_frames on a PNG folder, both routes, measured on the GPU by tools/bench_frames.py "
                 "--format png",
@@ -232,32 +288,17 @@ def bench_png(args) -> int:
         "filter_types_of_16_files": filters,
         "png_bytes_per_frame": float(raw_size.mean()), "idat_chunks_per_frame": float(rows[:, 5].mean()),
         "jpeg_bytes_per_frame": sum(os.path.getsize(p) for p in jpegs) / n,
-        "stages": res,
-        "ms_per_pass": {key[:-2]: 1e3 * v["median"] for key, v in res.items()},
-        "frames_per_s": {key[:-2]: n / v["median"] for key, v in res.items()},
-        "device_equals_host": calls_equal and bool(torch.equal(ed[-1][1], eh[-1][1])),
+        **rates(res, n),
+        "device_equals_host": calls_equal and routes_equal,
     }
-    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(report, f, indent=1)
-    print(json.dumps(report))
     tmp.cleanup()
-    return 0
+    return write_report(args, report)
 
 
 def write_gifs(folder: Path, n_files: int, per_file: int, size: int):
-    """vge.synth.make_frames content as Pillow writes animated GIFs from RGB frames (each frame quantised to a local
-    table of its own), the way diffusers' export_to_gif calls it."""
-    from PIL import Image
-    from vge import synth
-    paths = []
-    for v in range(n_files):
-        fr = synth.make_frames(1000 + v, per_file, h=size, w=size)
-        ims = [Image.fromarray(fr[f]) for f in range(per_file)]
-        p = folder / f"clip_{v:04d}.gif"
-        ims[0].save(p, format="GIF", save_all=True, append_images=ims[1:], optimize=False, duration=100, loop=0)
-        paths.append(str(p))
-    return paths
+    """Animated GIFs from RGB frames (each frame quantised to a local table of its own), the way diffusers'
+    export_to_gif calls Pillow."""
+    return write_clips(folder, n_files, per_file, size, ".gif", format="GIF", optimize=False)
 
 
 def bench_gif(args) -> int:
@@ -265,9 +306,7 @@ def bench_gif(args) -> int:
     import torch
     from vge import frames as FR
     from vge import lib as L
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_frames.py needs a GPU")
-    dev = torch.device("cuda:0")
+    dev = gpu()
     lib = L.load()
     tmp = tempfile.TemporaryDirectory()
     n_files = args.gif_files
@@ -279,39 +318,24 @@ def bench_gif(args) -> int:
     n_blocks = int(rows[:, 4].sum())
     w, h = int(rows[0, 0]), int(rows[0, 1])
 
-    def e2e(entropy):
-        t = time.perf_counter()
-        out = FR.load_videos(paths, device=dev, threads=args.threads, entropy=entropy)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t
-        assert sum(k.size for _, k in out) == n
-        return dt, torch.cat([f for f, _ in out])
-
     out_h = torch.empty((n, h, w, 3), dtype=torch.uint8, pin_memory=True)
     status = np.zeros(n, np.int32)
     arr = (C.c_char_p * n_files)(*[os.fsencode(p) for p in paths])
-
-    def host_decode():
-        t = time.perf_counter()
-        rc = lib.vge_gif_decode(arr, n_files, args.threads, w, h, n, out_h.data_ptr(), status.ctypes.data, None, None)
-        dt = time.perf_counter() - t
-        assert rc == 0, lib.vge_last_error()
-        return dt
-
     raw, raw_off, raw_size = FR._read_files(paths, args.threads, pin=True)
     raw_d = raw.to(dev)
     descs = (L.GifDesc * n)()
     segs = (L.GifSegment * n_blocks)()
     n_descs, n_segs, ws_bytes = C.c_int64(0), C.c_int64(0), C.c_int64(0)
 
+    def host_decode():
+        return clocked(lib, lambda: lib.vge_gif_decode(arr, n_files, args.threads, w, h, n, out_h.data_ptr(),
+                                                       status.ctypes.data, None, None))
+
     def plan():
-        t = time.perf_counter()
-        rc = lib.vge_gif_plan_mem(raw.data_ptr(), int(raw.numel()), raw_off.ctypes.data, raw_size.ctypes.data, n_files,
-                                  args.threads, w, h, descs, n, C.byref(n_descs), segs, n_blocks, C.byref(n_segs),
-                                  None, None, C.byref(ws_bytes))
-        dt = time.perf_counter() - t
-        assert rc == 0 and n_descs.value == n, lib.vge_last_error()
-        return dt
+        return clocked(lib, lambda: lib.vge_gif_plan_mem(
+            raw.data_ptr(), int(raw.numel()), raw_off.ctypes.data, raw_size.ctypes.data, n_files, args.threads, w, h,
+            descs, n, C.byref(n_descs), segs, n_blocks, C.byref(n_segs), None, None, C.byref(ws_bytes)),
+            also=lambda: n_descs.value == n)
 
     plan()
     descs_d = torch.frombuffer(descs, dtype=torch.uint8).to(dev)
@@ -327,35 +351,16 @@ def bench_gif(args) -> int:
                                           out_d.data_ptr(), status_d.data_ptr(), stream.cuda_stream),
                 "vge_gif_decode_device")
 
-    def events(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b) * 1e-3
+    def warm_e2e():
+        e2e(paths, n, dev, args.threads, "host"); e2e(paths, n, dev, args.threads, "device")
 
-    def stage(mask):   # one kernel of the call alone (a hook of the library for this tool), on the data the others left
-        lib.vge_debug_gif_stage_mask(mask)
-        try:
-            return events(device_call)
-        finally:
-            lib.vge_debug_gif_stage_mask(7)
-
-    res = {}
-    for _ in range(args.warmup):
-        host_decode(); events(device_call); e2e("host"); e2e("device")
-    res["host_decode_s"] = spread([host_decode() for _ in range(args.repeats)])
-    res["plan_s"] = spread([plan() for _ in range(args.repeats)])
-    res["device_call_s"] = spread([events(device_call) for _ in range(args.repeats)])
+    res = measure_calls(args, host_decode, plan, device_call, warm_e2e)
     assert int(status_d.abs().sum()) == 0
     calls_equal = bool(torch.equal(out_d.cpu(), out_h))
     for name, mask in (("gather", 1), ("lzw", 2), ("compose", 4)):   # each on what a whole call left in the workspace
-        res[f"{name}_kernel_s"] = spread([stage(mask) for _ in range(args.repeats)])
-    eh = [e2e("host") for _ in range(args.repeats)]
-    ed = [e2e("device") for _ in range(args.repeats)]
-    res["e2e_host_s"] = spread([t for t, _ in eh])
-    res["e2e_device_s"] = spread([t for t, _ in ed])
+        res[f"{name}_kernel_s"] = spread([staged(lib.vge_debug_gif_stage_mask, mask, 7, device_call)
+                                          for _ in range(args.repeats)])
+    routes_equal = measure_e2e(args, res, paths, n, dev)
     report = {
         "what": "vge.frames.load_videos on animated GIFs, both routes, measured on the GPU by tools/bench_frames.py "
                 "--format gif",
@@ -364,35 +369,20 @@ def bench_gif(args) -> int:
         "source": f"written here by Pillow: vge.synth.make_frames {args.size}x{args.size}, RGB frames, save_all",
         "gif_bytes_per_frame": float(raw_size.sum()) / n, "sub_blocks_per_frame": n_blocks / n,
         "lzw_expansion": "chain walk: each lane walks its code's (prefix, suffix) links backwards from LDS",
-        "stages": res,
-        "ms_per_pass": {key[:-2]: 1e3 * v["median"] for key, v in res.items()},
-        "frames_per_s": {key[:-2]: n / v["median"] for key, v in res.items()},
+        **rates(res, n),
         "yardstick_host_decode_ms": 1e3 * res["host_decode_s"]["median"],
         "device_call_ms": 1e3 * res["device_call_s"]["median"],
         "lzw_share_of_device_call": res["lzw_kernel_s"]["median"] / res["device_call_s"]["median"],
-        "device_equals_host": calls_equal and bool(torch.equal(ed[-1][1], eh[-1][1])),
+        "device_equals_host": calls_equal and routes_equal,
     }
-    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(report, f, indent=1)
-    print(json.dumps(report))
     tmp.cleanup()
-    return 0
+    return write_report(args, report)
 
 
 def write_webps(folder: Path, n_files: int, per_file: int, size: int):
-    """vge.synth.make_frames content as Pillow writes lossless animated WebP (save_all=True, lossless=True: what
-    ComfyUI's SaveAnimatedWEBP node calls with its defaults)."""
-    from PIL import Image
-    from vge import synth
-    paths = []
-    for v in range(n_files):
-        fr = synth.make_frames(1000 + v, per_file, h=size, w=size)
-        ims = [Image.fromarray(fr[f]) for f in range(per_file)]
-        p = folder / f"clip_{v:04d}.webp"
-        ims[0].save(p, format="WEBP", save_all=True, append_images=ims[1:], lossless=True, duration=100, loop=0)
-        paths.append(str(p))
-    return paths
+    """Lossless animated WebP (save_all=True, lossless=True: what ComfyUI's SaveAnimatedWEBP node calls with its
+    defaults)."""
+    return write_clips(folder, n_files, per_file, size, ".webp", format="WEBP", lossless=True)
 
 
 def bench_webp(args) -> int:
@@ -400,9 +390,7 @@ def bench_webp(args) -> int:
     import torch
     from vge import frames as FR
     from vge import lib as L
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_frames.py needs a GPU")
-    dev = torch.device("cuda:0")
+    dev = gpu()
     lib = L.load()
     tmp = tempfile.TemporaryDirectory()
     n_files = args.gif_files
@@ -413,37 +401,22 @@ def bench_webp(args) -> int:
     n = int(rows[:, 2].sum())
     w, h = int(rows[0, 0]), int(rows[0, 1])
 
-    def e2e(entropy):
-        t = time.perf_counter()
-        out = FR.load_videos(paths, device=dev, threads=args.threads, entropy=entropy)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t
-        assert sum(k.size for _, k in out) == n
-        return dt, torch.cat([f for f, _ in out])
-
     out_h = torch.empty((n, h, w, 3), dtype=torch.uint8, pin_memory=True)
     status = np.zeros(n, np.int32)
     arr = (C.c_char_p * n_files)(*[os.fsencode(p) for p in paths])
-
-    def host_decode():
-        t = time.perf_counter()
-        rc = lib.vge_webp_decode(arr, n_files, args.threads, w, h, n, out_h.data_ptr(), status.ctypes.data, None, None)
-        dt = time.perf_counter() - t
-        assert rc == 0, lib.vge_last_error()
-        return dt
-
     raw, raw_off, raw_size = FR._read_files(paths, args.threads, pin=True)
     raw_d = raw.to(dev)
     descs = (L.WebpDesc * n)()
     n_descs, ws_bytes = C.c_int64(0), C.c_int64(0)
 
+    def host_decode():
+        return clocked(lib, lambda: lib.vge_webp_decode(arr, n_files, args.threads, w, h, n, out_h.data_ptr(),
+                                                        status.ctypes.data, None, None))
+
     def plan():
-        t = time.perf_counter()
-        rc = lib.vge_webp_plan_mem(raw.data_ptr(), int(raw.numel()), raw_off.ctypes.data, raw_size.ctypes.data, n_files,
-                                   args.threads, w, h, descs, n, C.byref(n_descs), None, None, C.byref(ws_bytes))
-        dt = time.perf_counter() - t
-        assert rc == 0 and n_descs.value == n, lib.vge_last_error()
-        return dt
+        return clocked(lib, lambda: lib.vge_webp_plan_mem(
+            raw.data_ptr(), int(raw.numel()), raw_off.ctypes.data, raw_size.ctypes.data, n_files, args.threads, w, h,
+            descs, n, C.byref(n_descs), None, None, C.byref(ws_bytes)), also=lambda: n_descs.value == n)
 
     plan()
     # the largest number of prefix-code groups any frame asks for (the table arena holds VGE_WEBP_MAX_GROUPS)
@@ -464,37 +437,17 @@ def bench_webp(args) -> int:
                                            ws.data_ptr(), int(ws.numel()), out_d.data_ptr(), status_d.data_ptr(),
                                            stream.cuda_stream), "vge_webp_decode_device")
 
-    def events(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b) * 1e-3
+    def warm_e2e():
+        e2e(paths, n, dev, args.threads, "host"); e2e(paths, n, dev, args.threads, "device")
 
-    def stage(mask):   # one kernel of the call alone (a hook of the library for this tool), on the data the others left
-        lib.vge_debug_webp_stage_mask(mask)
-        try:
-            return events(device_call)
-        finally:
-            lib.vge_debug_webp_stage_mask(7)
-
-    res = {}
-    for _ in range(args.warmup):
-        host_decode(); events(device_call); e2e("host"); e2e("device")
-    res["host_decode_s"] = spread([host_decode() for _ in range(args.repeats)])
-    res["plan_s"] = spread([plan() for _ in range(args.repeats)])
-    res["device_call_s"] = spread([events(device_call) for _ in range(args.repeats)])
+    res = measure_calls(args, host_decode, plan, device_call, warm_e2e)
     assert int(status_d.abs().sum()) == 0
     calls_equal = bool(torch.equal(out_d.cpu(), out_h))
     # entropy alone rewrites the coded planes; the transforms then run on fresh input once more before compose is timed
-    res["entropy_kernel_s"] = spread([stage(1) for _ in range(args.repeats)])
-    res["entropy_transforms_s"] = spread([stage(3) for _ in range(args.repeats)])
-    res["compose_kernel_s"] = spread([stage(4) for _ in range(args.repeats)])
-    eh = [e2e("host") for _ in range(args.repeats)]
-    ed = [e2e("device") for _ in range(args.repeats)]
-    res["e2e_host_s"] = spread([t for t, _ in eh])
-    res["e2e_device_s"] = spread([t for t, _ in ed])
+    for name, mask in (("entropy_kernel", 1), ("entropy_transforms", 3), ("compose_kernel", 4)):
+        res[f"{name}_s"] = spread([staged(lib.vge_debug_webp_stage_mask, mask, 7, device_call)
+                                   for _ in range(args.repeats)])
+    routes_equal = measure_e2e(args, res, paths, n, dev)
     report = {
         "what": "vge.frames.load_videos on lossless animated WebP, both routes, measured on the GPU by "
                 "tools/bench_frames.py --format webp",
@@ -507,20 +460,14 @@ def bench_webp(args) -> int:
         "group_capacity": L.WEBP_MAX_GROUPS, "most_groups_in_a_frame": most_groups,
         "entropy_kernel": "one wave per frame, the stream walked by one lane (the shared decoder of "
                           "csrc/vge_webp_vp8l.h); transforms and compose are parallel",
-        "stages": res,
-        "ms_per_pass": {key[:-2]: 1e3 * v["median"] for key, v in res.items()},
-        "frames_per_s": {key[:-2]: n / v["median"] for key, v in res.items()},
+        **rates(res, n),
         "yardstick_host_decode_ms": 1e3 * res["host_decode_s"]["median"],
         "device_call_ms": 1e3 * res["device_call_s"]["median"],
         "entropy_share_of_device_call": res["entropy_kernel_s"]["median"] / res["device_call_s"]["median"],
-        "device_equals_host": calls_equal and bool(torch.equal(ed[-1][1], eh[-1][1])),
+        "device_equals_host": calls_equal and routes_equal,
     }
-    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(report, f, indent=1)
-    print(json.dumps(report))
     tmp.cleanup()
-    return 0
+    return write_report(args, report)
 
 
 def write_apngs(folder: Path, n_files: int, per_file: int, size: int, kind: str):
@@ -559,20 +506,10 @@ def bench_apng(args) -> int:
     import torch
     from vge import frames as FR
     from vge import lib as L
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_frames.py needs a GPU")
-    dev = torch.device("cuda:0")
+    dev = gpu()
     lib = L.load()
     n_files = args.gif_files
     per_file = max(1, args.frames // n_files)
-
-    def events(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b) * 1e-3
 
     def one_kind(kind):
         tmp = tempfile.TemporaryDirectory()
@@ -582,40 +519,24 @@ def bench_apng(args) -> int:
         n, n_chunks = int(rows[:, 5].sum()), int(rows[:, 7].sum())
         w, h, ct = int(rows[0, 0]), int(rows[0, 1]), int(rows[0, 2])
 
-        def e2e(entropy):
-            t = time.perf_counter()
-            out = FR.load_videos(paths, device=dev, threads=args.threads, entropy=entropy)
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t
-            assert sum(k.size for _, k in out) == n
-            return dt, torch.cat([f for f, _ in out])
-
         out_h = torch.empty((n, h, w, 3), dtype=torch.uint8, pin_memory=True)
         status = np.zeros(n, np.int32)
         arr = (C.c_char_p * n_files)(*[os.fsencode(p) for p in paths])
-
-        def host_decode():
-            t = time.perf_counter()
-            rc = lib.vge_apng_decode(arr, n_files, args.threads, w, h, ct, n, out_h.data_ptr(), status.ctypes.data, None,
-                                     None)
-            dt = time.perf_counter() - t
-            assert rc == 0, lib.vge_last_error()
-            return dt
-
         raw, raw_off, raw_size = FR._read_files(paths, args.threads, pin=True)
         raw_d = raw.to(dev)
         descs = (L.ApngDesc * n)()
         segs = (L.ApngSegment * n_chunks)()
         n_descs, n_segs, ws_bytes = C.c_int64(0), C.c_int64(0), C.c_int64(0)
 
+        def host_decode():
+            return clocked(lib, lambda: lib.vge_apng_decode(arr, n_files, args.threads, w, h, ct, n, out_h.data_ptr(),
+                                                            status.ctypes.data, None, None))
+
         def plan():
-            t = time.perf_counter()
-            rc = lib.vge_apng_plan_mem(raw.data_ptr(), int(raw.numel()), raw_off.ctypes.data, raw_size.ctypes.data,
-                                       n_files, args.threads, w, h, ct, descs, n, C.byref(n_descs), segs, n_chunks,
-                                       C.byref(n_segs), None, None, C.byref(ws_bytes))
-            dt = time.perf_counter() - t
-            assert rc == 0 and n_descs.value == n, lib.vge_last_error()
-            return dt
+            return clocked(lib, lambda: lib.vge_apng_plan_mem(
+                raw.data_ptr(), int(raw.numel()), raw_off.ctypes.data, raw_size.ctypes.data, n_files, args.threads, w,
+                h, ct, descs, n, C.byref(n_descs), segs, n_chunks, C.byref(n_segs), None, None, C.byref(ws_bytes)),
+                also=lambda: n_descs.value == n)
 
         plan()
         descs_d = torch.frombuffer(descs, dtype=torch.uint8).to(dev)
@@ -631,19 +552,10 @@ def bench_apng(args) -> int:
                                                int(ws.numel()), out_d.data_ptr(), status_d.data_ptr(),
                                                stream.cuda_stream), "vge_apng_decode_device")
 
-        def stage(mask):   # one kernel of the call alone (a hook of the library for this tool)
-            lib.vge_debug_apng_stage_mask(mask)
-            try:
-                return events(device_call)
-            finally:
-                lib.vge_debug_apng_stage_mask(31)
+        def warm_e2e():
+            e2e(paths, n, dev, args.threads, "host"); e2e(paths, n, dev, args.threads, "device")
 
-        res = {}
-        for _ in range(args.warmup):
-            host_decode(); events(device_call); e2e("host"); e2e("device")
-        res["host_decode_s"] = spread([host_decode() for _ in range(args.repeats)])
-        res["plan_s"] = spread([plan() for _ in range(args.repeats)])
-        res["device_call_s"] = spread([events(device_call) for _ in range(args.repeats)])
+        res = measure_calls(args, host_decode, plan, device_call, warm_e2e)
         assert int(status_d.abs().sum()) == 0
         calls_equal = bool(torch.equal(out_d.cpu(), out_h))
         # gather, inflate and adler run on what the call before left; unfilter rewrites its slot in place, so it is
@@ -651,28 +563,24 @@ def bench_apng(args) -> int:
         for name, mask in (("gather", 1), ("inflate", 2), ("adler", 4), ("inflate_unfilter", 2 | 8), ("compose", 16)):
             if name == "compose":
                 events(device_call)
-            res[f"{name}_kernel_s"] = spread([stage(mask) for _ in range(args.repeats)])
-        eh = [e2e("host") for _ in range(args.repeats)]
-        ed = [e2e("device") for _ in range(args.repeats)]
-        res["e2e_host_s"] = spread([t for t, _ in eh])
-        res["e2e_device_s"] = spread([t for t, _ in ed])
+            res[f"{name}_kernel_s"] = spread([staged(lib.vge_debug_apng_stage_mask, mask, 31, device_call)
+                                              for _ in range(args.repeats)])
+        routes_equal = measure_e2e(args, res, paths, n, dev)
         rect = np.array([[descs[k].w, descs[k].h] for k in range(n)])
         tmp.cleanup()
         return {
             "files": n_files, "frames": n, "width": w, "height": h, "color_type": ct,
             "apng_bytes_per_frame": float(raw_size.sum()) / n, "chunks_per_frame": n_chunks / n,
             "mean_rectangle": [float(rect[:, 0].mean()), float(rect[:, 1].mean())],
-            "stages": res,
-            "ms_per_pass": {key[:-2]: 1e3 * v["median"] for key, v in res.items()},
-            "frames_per_s": {key[:-2]: n / v["median"] for key, v in res.items()},
+            **rates(res, n),
             "yardstick_host_decode_ms": 1e3 * res["host_decode_s"]["median"],
             "device_call_ms": 1e3 * res["device_call_s"]["median"],
             "device_call_over_host_decode": res["device_call_s"]["median"] / res["host_decode_s"]["median"],
             "e2e_device_over_e2e_host": res["e2e_device_s"]["median"] / res["e2e_host_s"]["median"],
-            "device_equals_host": calls_equal and bool(torch.equal(ed[-1][1], eh[-1][1])),
+            "device_equals_host": calls_equal and routes_equal,
         }
 
-    report = {
+    return write_report(args, {
         "what": "vge.frames.load_videos on animated PNGs, both routes, measured on the GPU by tools/bench_frames.py "
                 "--format apng",
         "device": torch.cuda.get_device_name(0), "threads": args.threads,
@@ -680,12 +588,7 @@ def bench_apng(args) -> int:
                   "moving square over a fixed frame, cropped by Pillow; rgba: whole RGBA frames blended OVER",
         "deltas": one_kind("deltas"),
         "rgba": one_kind("rgba"),
-    }
-    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(report, f, indent=1)
-    print(json.dumps(report))
-    return 0
+    })
 
 
 def _idat(data: bytes):
@@ -737,9 +640,7 @@ def main(argv=None) -> int:
     import torch
     from vge import frames as FR
     from vge import lib as L
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_frames.py needs a GPU")
-    dev = torch.device("cuda:0")
+    dev = gpu()
     try:
         import PIL
         from PIL import Image
@@ -771,21 +672,8 @@ def main(argv=None) -> int:
     stream = torch.cuda.current_stream(dev)
 
     def entropy():
-        t = time.perf_counter()
-        rc = lib.vge_jpeg_entropy_decode(arr, n, args.threads, C.byref(lay), coef.data_ptr(), qtab.data_ptr(),
-                                         status.ctypes.data)
-        dt = time.perf_counter() - t
-        assert rc == 0, L.load().vge_last_error()
-        return dt
-
-    def events(fn, inner=1):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(inner):
-            fn()
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b) * 1e-3 / inner
+        return clocked(lib, lambda: lib.vge_jpeg_entropy_decode(arr, n, args.threads, C.byref(lay), coef.data_ptr(),
+                                                                qtab.data_ptr(), status.ctypes.data))
 
     def upload():
         coef_d.copy_(coef, non_blocking=True)
@@ -795,14 +683,6 @@ def main(argv=None) -> int:
         L.check(lib.vge_jpeg_reconstruct(coef_d.data_ptr(), qtab_d.data_ptr(), C.byref(lay), n, out.data_ptr(),
                                          stream.cuda_stream), "vge_jpeg_reconstruct")
 
-    def e2e():
-        t = time.perf_counter()
-        fr, kept = FR.load_frames(paths, device=dev, threads=args.threads)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t
-        assert kept.size == n
-        return dt, fr
-
     def pillow():
         t = time.perf_counter()
         with ThreadPoolExecutor(args.threads) as ex:
@@ -811,11 +691,11 @@ def main(argv=None) -> int:
 
     res = {}
     for _ in range(args.warmup):
-        entropy(); events(upload); events(kernel); e2e()
+        entropy(); events(upload); events(kernel); e2e([paths], n, dev, args.threads, "host")
     res["entropy_s"] = spread([entropy() for _ in range(args.repeats)])
     res["upload_s"] = spread([events(upload) for _ in range(args.repeats)])
     res["kernel_s"] = spread([events(kernel, args.inner) for _ in range(args.repeats)])
-    e = [e2e() for _ in range(args.repeats)]
+    e = [e2e([paths], n, dev, args.threads, "host") for _ in range(args.repeats)]
     res["e2e_s"] = spread([t for t, _ in e])
     frames = e[-1][1]
     exact = None
@@ -850,27 +730,15 @@ def main(argv=None) -> int:
                                                        qtab_d.data_ptr(), status_d.data_ptr(), rounds_d.data_ptr(),
                                                        stream.cuda_stream), "vge_jpeg_entropy_decode_device")
 
-        def prepare():   # the same call stopped after headers + scan preparation (a hook of the library for this tool)
-            lib.vge_debug_jpeg_dehuff_prepare_only(1)
-            try:
-                return events(device_entropy)
-            finally:
-                lib.vge_debug_jpeg_dehuff_prepare_only(0)
-
-        def e2e_device():
-            t = time.perf_counter()
-            fr, kept = FR.load_frames(paths, device=dev, threads=args.threads, entropy="device")
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t
-            assert kept.size == n
-            return dt, fr
+        def prepare():   # the same call stopped after headers + scan preparation
+            return staged(lib.vge_debug_jpeg_dehuff_prepare_only, 1, 0, device_entropy)
 
         for _ in range(args.warmup):
-            read_upload(); events(device_entropy); prepare(); e2e_device()
+            read_upload(); events(device_entropy); prepare(); e2e([paths], n, dev, args.threads, "device")
         res["read_upload_s"] = spread([read_upload() for _ in range(args.repeats)])
         res["prepare_s"] = spread([prepare() for _ in range(args.repeats)])
         res["device_entropy_s"] = spread([events(device_entropy) for _ in range(args.repeats)])
-        ed = [e2e_device() for _ in range(args.repeats)]
+        ed = [e2e([paths], n, dev, args.threads, "device") for _ in range(args.repeats)]
         res["e2e_device_s"] = spread([t for t, _ in ed])
         device_entropy()
         torch.cuda.synchronize()
@@ -903,13 +771,9 @@ def main(argv=None) -> int:
     }
     if device_rows is not None:
         report["device_entropy"] = device_rows
-    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(report, f, indent=1)
-    print(json.dumps(report))
     if tmp is not None:
         tmp.cleanup()
-    return 0
+    return write_report(args, report)
 
 
 if __name__ == "__main__":

@@ -348,10 +348,9 @@ def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root
     if frame_format not in ("jpg", "png", "gif", "webp", "apng"):
         raise ValueError(f"frame_format must be 'jpg', 'png', 'gif', 'webp' or 'apng', not {frame_format!r}")
     ext = "." + frame_format
-    is_gif = frame_format in ("gif", "webp", "apng")   # a video is one file
+    video_format = FR.VIDEO_FILE_FORMATS.get(frame_format)
+    one_file = video_format is not None   # a video is one file
     exts = (".png", ".apng") if frame_format == "apng" else (ext,)   # the later suffix wins when both files exist
-    probe_file = {"webp": FR.webp_probe, "apng": FR.apng_probe}.get(frame_format, FR.gif_probe)
-    count_col = 5 if frame_format == "apng" else 2   # the probe row's frame count
     frames_root, log_root = Path(frames_root), Path(log_root)
     all_actions = sorted(d.name for d in frames_root.iterdir() if d.is_dir())
     if actions is None:
@@ -364,7 +363,7 @@ def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root
     summary: Dict[str, Dict[str, list]] = {}
     for action in actions:
         action_dir = frames_root / action
-        if is_gif:
+        if one_file:
             files = [p for p in action_dir.iterdir() if p.is_file() and p.suffix in exts]
             videos = sorted({p.stem for p in files})
             for v in videos:
@@ -374,7 +373,7 @@ def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root
             videos = sorted(d.name for d in action_dir.iterdir() if d.is_dir())
 
         def source(video):
-            if not is_gif:
+            if not one_file:
                 return action_dir / video
             found = [e for e in exts if (action_dir / (video + e)).is_file()]
             return action_dir / (video + (found[-1] if found else exts[0]))
@@ -415,9 +414,9 @@ def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root
                 print(f"[SKIP] {action}/{video} (already processed)")
                 done["skipped"].append(video)
                 continue
-            todo.append((video, str(source(video)) if is_gif else FR.list_frames(action_dir / video, ext=ext)))
-        if is_gif:   # a video is one file: the probe gives its frame count
-            counts = probe_file([p for _, p in todo], threads)[:, count_col] if todo else []
+            todo.append((video, str(source(video)) if one_file else FR.list_frames(action_dir / video, ext=ext)))
+        if one_file:   # a video is one file: the probe gives its frame count
+            counts = FR._probe(video_format, [p for _, p in todo], threads)[:, video_format.count_col] if todo else []
             entries = []
             for (v, p), n in zip(todo, counts):
                 if int(n) > 0:
@@ -442,7 +441,7 @@ def extract_frame_tree(hmr, wholebody, detector, frames_root, mesh_root, kp_root
             for (video, paths, count), dec in zip(group, decoded):
                 if isinstance(dec, Exception):
                     fail(video, str(dec))
-                elif is_gif and dec[1].size == 0:
+                elif one_file and dec[1].size == 0:
                     fail(video, f"none of the {count} frames of {paths} could be decoded")
                 elif not paths:
                     fail(video, f"no frames (*{ext}) in {action_dir / video}")

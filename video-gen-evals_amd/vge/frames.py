@@ -38,8 +38,9 @@ from __future__ import annotations
 import ctypes as C
 import logging
 import os
+from functools import partial
 from pathlib import Path
-from typing import List, Optional, Sequence, Tuple, Union
+from typing import List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -230,38 +231,124 @@ def _raise_unsupported(names, statuses) -> None:
                                        f"({L.JPEG_STATUS[int(s)]})")
 
 
-# ---- PNG frames (include/vge_png.h)
+# ---- PNG frames (include/vge_png.h) and the videos in one file: GIF (include/vge_gif.h), lossless WebP
+# ---- (include/vge_webp.h), APNG (include/vge_apng.h)
 
-def _png_rows(info, n: int) -> np.ndarray:
-    return np.array([[i.width, i.height, i.color_type, i.bit_depth, i.interlace, i.n_idat, i.idat_bytes, i.status]
-                     for i in info[:n]], dtype=np.int64).reshape(-1, 8)
+class _VideoFormat(NamedTuple):
+    """What differs between the formats whose Python front end is otherwise one text: plain data, no behaviour.  The
+    first ten fields describe the format's C interface and its refusals, and the PNG still frames have them too; the
+    others belong to the formats in which a file is a video (VIDEO_FILE_FORMATS)."""
+    lib: str                         # the prefix of the format's C functions
+    info: type                       # L.*Info, a probe's record
+    fields: Tuple[str, ...]          # its fields in the order of a probe row's columns; the status is the last
+    desc: type                       # L.*Desc, the device plan's record of a frame
+    segment: Optional[type]          # L.*Segment, the plan's record of a run of bytes to gather; None: gathers nothing
+    n_key: int                       # the leading columns that files of one decode call share
+    status: dict                     # the status names of the log lines
+    unsupported: dict                # the statuses refused by name ...
+    error: type                      # ... the exception they raise ...
+    kind: str                        # ... and what its message calls the format
+    count_col: Optional[int] = None  # the probe column of a file's frame count
+    seg_col: Optional[int] = None    # the probe column of a file's segment count, with `segment`
+    raise_in_keep: bool = False      # an unsupported status can also come from the decoders, and is raised then too
+    noun: str = ""                   # what decode_*'s refusal of device memory says the plan walks
+    public: str = ""                 # the decode_* function that refusal names
+
+
+_PNG = _VideoFormat("vge_png", L.PngInfo, ("width", "height", "color_type", "bit_depth", "interlace", "n_idat",
+                                           "idat_bytes", "status"), L.PngDesc, L.PngSegment, 3, L.PNG_STATUS,
+                    L.PNG_UNSUPPORTED, UnsupportedPngError, "PNG")
+_GIF = _VideoFormat("vge_gif", L.GifInfo, ("width", "height", "n_frames", "lzw_bytes", "n_blocks", "status"),
+                    L.GifDesc, L.GifSegment, 2, L.GIF_STATUS, L.GIF_UNSUPPORTED, UnsupportedGifError, "GIF",
+                    count_col=2, seg_col=4, noun="data sub-block", public="decode_gifs")
+# raise_in_keep is WebP's alone: only its decoders see that a frame asks for more prefix-code groups than they hold
+_WEBP = _VideoFormat("vge_webp", L.WebpInfo, ("width", "height", "n_frames", "vp8l_bytes", "n_chunks", "status"),
+                     L.WebpDesc, None, 2, L.WEBP_STATUS, L.WEBP_UNSUPPORTED, UnsupportedWebpError, "WebP",
+                     count_col=2, raise_in_keep=True, noun="chunk", public="decode_webps")
+# an APNG is refused by name for the kinds the still path refuses, in the same words and under the same status names
+_APNG = _VideoFormat("vge_apng", L.ApngInfo, ("width", "height", "color_type", "bit_depth", "interlace", "n_frames",
+                                              "default_image", "n_chunks", "data_bytes", "status"),
+                     L.ApngDesc, L.ApngSegment, 3, L.APNG_STATUS, L.APNG_UNSUPPORTED, UnsupportedPngError, "PNG",
+                     count_col=5, seg_col=7, noun="chunk", public="decode_apngs")
+VIDEO_FILE_FORMATS = {"gif": _GIF, "webp": _WEBP, "apng": _APNG}
+
+
+def _rows(fmt: _VideoFormat, info, n: int) -> np.ndarray:
+    return np.array([[getattr(i, f) for f in fmt.fields] for i in info[:n]],
+                    dtype=np.int64).reshape(-1, len(fmt.fields))
+
+
+# the tests' case files read the C probes through these
+_png_rows, _gif_rows, _webp_rows, _apng_rows = (partial(_rows, f) for f in (_PNG, _GIF, _WEBP, _APNG))
+
+
+def _probe(fmt: _VideoFormat, paths: Sequence[PathLike], threads: int) -> np.ndarray:
+    paths = [os.fspath(p) for p in paths]
+    info = (fmt.info * max(len(paths), 1))()
+    if paths:
+        getattr(L.load(), fmt.lib + "_probe")(_paths_array(paths), len(paths), int(threads), info)
+    return _rows(fmt, info, len(paths))
+
+
+def _probe_mem(fmt: _VideoFormat, data: np.ndarray, offsets: np.ndarray, sizes: np.ndarray, threads: int) -> np.ndarray:
+    n = len(offsets)
+    info = (fmt.info * max(n, 1))()
+    if n:
+        offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
+        getattr(L.load(), fmt.lib + "_probe_mem")(data.ctypes.data, data.size, offsets.ctypes.data, sizes.ctypes.data,
+                                                  n, int(threads), info)
+    return _rows(fmt, info, n)
 
 
 def png_probe(paths: Sequence[PathLike], threads: int = 0) -> np.ndarray:
     """Headers only: int64 [n, 8] rows of (width, height, colour type, bit depth, interlace, IDAT chunks, IDAT bytes,
     status) (vge_png_probe)."""
-    paths = [os.fspath(p) for p in paths]
-    info = (L.PngInfo * max(len(paths), 1))()
-    if paths:
-        L.load().vge_png_probe(_paths_array(paths), len(paths), int(threads), info)
-    return _png_rows(info, len(paths))
+    return _probe(_PNG, paths, threads)
 
 
 def png_probe_mem(data: np.ndarray, offsets: np.ndarray, sizes: np.ndarray, threads: int = 0) -> np.ndarray:
     """png_probe() for files in host memory: file i is data[offsets[i]:offsets[i] + sizes[i]] (vge_png_probe_mem)."""
-    n = len(offsets)
-    info = (L.PngInfo * max(n, 1))()
-    if n:
-        offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
-        L.load().vge_png_probe_mem(data.ctypes.data, data.size, offsets.ctypes.data, sizes.ctypes.data, n,
-                                   int(threads), info)
-    return _png_rows(info, n)
+    return _probe_mem(_PNG, data, offsets, sizes, threads)
 
 
-def _raise_unsupported_png(names, statuses) -> None:
+def gif_probe(paths: Sequence[PathLike], threads: int = 0) -> np.ndarray:
+    """Headers and block structure only: int64 [n, 6] rows of (screen width, screen height, frames, LZW bytes, data
+    sub-blocks, status) (vge_gif_probe)."""
+    return _probe(_GIF, paths, threads)
+
+
+def gif_probe_mem(data: np.ndarray, offsets: np.ndarray, sizes: np.ndarray, threads: int = 0) -> np.ndarray:
+    """gif_probe() for files in host memory: file i is data[offsets[i]:offsets[i] + sizes[i]] (vge_gif_probe_mem)."""
+    return _probe_mem(_GIF, data, offsets, sizes, threads)
+
+
+def webp_probe(paths: Sequence[PathLike], threads: int = 0) -> np.ndarray:
+    """Headers and chunk structure only: int64 [n, 6] rows of (canvas width, canvas height, frames, VP8L payload
+    bytes, chunks, status) (vge_webp_probe)."""
+    return _probe(_WEBP, paths, threads)
+
+
+def webp_probe_mem(data: np.ndarray, offsets: np.ndarray, sizes: np.ndarray, threads: int = 0) -> np.ndarray:
+    """webp_probe() for files in host memory: file i is data[offsets[i]:offsets[i] + sizes[i]] (vge_webp_probe_mem)."""
+    return _probe_mem(_WEBP, data, offsets, sizes, threads)
+
+
+def apng_probe(paths: Sequence[PathLike], threads: int = 0) -> np.ndarray:
+    """Chunk headers only: int64 [n, 10] rows of (canvas width, canvas height, colour type, bit depth, interlace,
+    frames, whether frame 0 is a default image outside the animation, non-empty IDAT / fdAT payloads, their bytes,
+    status) (vge_apng_probe).  A PNG that is not animated is a video of one frame."""
+    return _probe(_APNG, paths, threads)
+
+
+def apng_probe_mem(data: np.ndarray, offsets: np.ndarray, sizes: np.ndarray, threads: int = 0) -> np.ndarray:
+    """apng_probe() for files in host memory: file i is data[offsets[i]:offsets[i] + sizes[i]] (vge_apng_probe_mem)."""
+    return _probe_mem(_APNG, data, offsets, sizes, threads)
+
+
+def _refuse(fmt: _VideoFormat, names, statuses) -> None:
     for p, s in zip(names, statuses):
-        if int(s) in L.PNG_UNSUPPORTED:
-            raise UnsupportedPngError(f"{p}: unsupported PNG: {L.PNG_UNSUPPORTED[int(s)]} ({L.PNG_STATUS[int(s)]})")
+        if int(s) in fmt.unsupported:
+            raise fmt.error(f"{p}: unsupported {fmt.kind}: {fmt.unsupported[int(s)]} ({fmt.status[int(s)]})")
 
 
 def _png_decode_group(paths, data, offsets, sizes, key, device, threads: int):
@@ -320,106 +407,83 @@ def _png_decode_group_device(data_h: np.ndarray, data_d, offsets: np.ndarray, si
     return out, np.where(planned != 0, planned, status).astype(np.int32)
 
 
-# ---- GIF videos (include/vge_gif.h)
-
-def _gif_rows(info, n: int) -> np.ndarray:
-    return np.array([[i.width, i.height, i.n_frames, i.lzw_bytes, i.n_blocks, i.status] for i in info[:n]],
-                    dtype=np.int64).reshape(-1, 6)
-
-
-def gif_probe(paths: Sequence[PathLike], threads: int = 0) -> np.ndarray:
-    """Headers and block structure only: int64 [n, 6] rows of (screen width, screen height, frames, LZW bytes, data
-    sub-blocks, status) (vge_gif_probe)."""
-    paths = [os.fspath(p) for p in paths]
-    info = (L.GifInfo * max(len(paths), 1))()
-    if paths:
-        L.load().vge_gif_probe(_paths_array(paths), len(paths), int(threads), info)
-    return _gif_rows(info, len(paths))
-
-
-def gif_probe_mem(data: np.ndarray, offsets: np.ndarray, sizes: np.ndarray, threads: int = 0) -> np.ndarray:
-    """gif_probe() for files in host memory: file i is data[offsets[i]:offsets[i] + sizes[i]] (vge_gif_probe_mem)."""
-    n = len(offsets)
-    info = (L.GifInfo * max(n, 1))()
-    if n:
-        offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
-        L.load().vge_gif_probe_mem(data.ctypes.data, data.size, offsets.ctypes.data, sizes.ctypes.data, n,
-                                   int(threads), info)
-    return _gif_rows(info, n)
-
-
-def _raise_unsupported_gif(names, statuses) -> None:
-    for p, s in zip(names, statuses):
-        if int(s) in L.GIF_UNSUPPORTED:
-            raise UnsupportedGifError(f"{p}: unsupported GIF: {L.GIF_UNSUPPORTED[int(s)]} ({L.GIF_STATUS[int(s)]})")
-
-
-def _gif_decode_group(paths, data, offsets, sizes, screen, n_frames: int, device, threads: int):
-    """The GIF files of one logical screen on host threads, from paths or (paths None) from files in host memory
-    (data: a uint8 CPU tensor) -> (uint8 [n_frames, H, W, 3] tensor on `device`, int32 status [n_frames]):
-    vge_gif_decode / vge_gif_decode_mem into pinned memory, then one upload.  n_frames: the probe's sum."""
+def _video_decode_group(fmt: _VideoFormat, paths, data, offsets, sizes, key, n_frames: int, device, threads: int):
+    """The files of one group -- one logical screen or canvas, for APNG also one colour type: `key` -- on host threads,
+    from paths or (paths None) from files in host memory (data: a uint8 CPU tensor) -> (uint8 [n_frames, H, W, 3] tensor
+    on `device`, int32 status [n_frames]): vge_*_decode / vge_*_decode_mem into pinned memory, then one upload.
+    n_frames: the probe's sum."""
     import torch
     lib = L.load()
-    w, h = screen
+    w, h = key[:2]
     on_gpu = device.type == "cuda"
     out = torch.empty((n_frames, h, w, 3), dtype=torch.uint8, pin_memory=on_gpu)
     status = np.zeros(n_frames, np.int32)
     if paths is not None:
-        lib.vge_gif_decode(_paths_array(paths), len(paths), int(threads), w, h, n_frames, out.data_ptr(),
-                           status.ctypes.data, None, None)
+        getattr(lib, fmt.lib + "_decode")(_paths_array(paths), len(paths), int(threads), *key, n_frames,
+                                          out.data_ptr(), status.ctypes.data, None, None)
     else:
         offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
-        lib.vge_gif_decode_mem(data.data_ptr(), int(data.numel()), offsets.ctypes.data, sizes.ctypes.data,
-                               len(offsets), int(threads), w, h, n_frames, out.data_ptr(), status.ctypes.data, None,
-                               None)
+        getattr(lib, fmt.lib + "_decode_mem")(data.data_ptr(), int(data.numel()), offsets.ctypes.data,
+                                              sizes.ctypes.data, len(offsets), int(threads), *key, n_frames,
+                                              out.data_ptr(), status.ctypes.data, None, None)
     if on_gpu:
         with torch.cuda.device(device):
             out = out.to(device, non_blocking=True)
     return out, status
 
 
-def _gif_decode_group_device(data_h: np.ndarray, data_d, offsets: np.ndarray, sizes: np.ndarray, screen,
-                             n_frames: int, n_blocks: int, threads: int):
-    """The GIF files of one logical screen, their bytes both in host memory (data_h, which only the plan's block walk
-    reads) and on the GPU (data_d) -> (uint8 [n_frames, H, W, 3] tensor on that GPU, int32 status [n_frames]):
-    vge_gif_plan_mem on the host, one upload of the descriptors and segments, vge_gif_decode_device on the current
-    stream; the one host synchronisation is the copy of the statuses at the end.  n_frames, n_blocks: the probe's sums."""
+def _video_decode_group_device(fmt: _VideoFormat, data_h: np.ndarray, data_d, offsets: np.ndarray, sizes: np.ndarray,
+                               key, n_frames: int, seg_cap: int, threads: int):
+    """The files of one group, their bytes both in host memory (data_h, which only the plan's walk over the blocks or
+    chunks reads) and on the GPU (data_d) -> (uint8 [n_frames, H, W, 3] tensor on that GPU, int32 status [n_frames]):
+    vge_*_plan_mem on the host, one upload of the descriptors and (a format that gathers) the segments,
+    vge_*_decode_device on the current stream; the one host synchronisation is the copy of the statuses at the end.
+    n_frames, seg_cap: the probe's sums."""
     import torch
     lib = L.load()
     dev = data_d.device
-    w, h = screen
+    w, h = key[:2]
     offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
-    descs = (L.GifDesc * max(n_frames, 1))()
-    segs = (L.GifSegment * max(n_blocks, 1))()
+    descs = (fmt.desc * max(n_frames, 1))()
     planned = np.zeros(max(n_frames, 1), np.int32)
     n_descs, n_segs, ws_bytes = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-    lib.vge_gif_plan_mem(data_h.ctypes.data, data_h.size, offsets.ctypes.data, sizes.ctypes.data, len(offsets),
-                         int(threads), w, h, descs, n_frames, C.byref(n_descs), segs, n_blocks, C.byref(n_segs),
-                         planned.ctypes.data, None, C.byref(ws_bytes))
+    seg_args = ()
+    if fmt.segment is not None:
+        segs = (fmt.segment * max(seg_cap, 1))()
+        seg_args = (segs, seg_cap, C.byref(n_segs))
+    getattr(lib, fmt.lib + "_plan_mem")(data_h.ctypes.data, data_h.size, offsets.ctypes.data, sizes.ctypes.data,
+                                        len(offsets), int(threads), *key, descs, n_frames, C.byref(n_descs), *seg_args,
+                                        planned.ctypes.data, None, C.byref(ws_bytes))
     if n_descs.value != n_frames:
-        raise L.VgeError("vge_gif_plan_mem: " + lib.vge_last_error().decode(errors="replace"))
+        raise L.VgeError(fmt.lib + "_plan_mem: " + lib.vge_last_error().decode(errors="replace"))
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
         descs_d = torch.frombuffer(descs, dtype=torch.uint8).to(dev)
-        segs_d = torch.frombuffer(segs, dtype=torch.uint8).to(dev)
+        if fmt.segment is not None:
+            segs_d = torch.frombuffer(segs, dtype=torch.uint8).to(dev)
+            seg_args = (segs_d.data_ptr(), n_segs.value)
         ws = torch.empty(int(ws_bytes.value), dtype=torch.uint8, device=dev)
         status_d = torch.empty(n_frames, dtype=torch.int32, device=dev)
         out = torch.empty((n_frames, h, w, 3), dtype=torch.uint8, device=dev)
-        L.check(lib.vge_gif_decode_device(data_d.data_ptr(), int(data_d.numel()), descs_d.data_ptr(), n_frames,
-                                          segs_d.data_ptr(), n_segs.value, n_frames, len(offsets), w, h, ws.data_ptr(),
-                                          int(ws.numel()), out.data_ptr(), status_d.data_ptr(), stream.cuda_stream),
-                "vge_gif_decode_device")
+        L.check(getattr(lib, fmt.lib + "_decode_device")(data_d.data_ptr(), int(data_d.numel()), descs_d.data_ptr(),
+                                                         n_frames, *seg_args, n_frames, len(offsets), *key,
+                                                         ws.data_ptr(), int(ws.numel()), out.data_ptr(),
+                                                         status_d.data_ptr(), stream.cuda_stream),
+                fmt.lib + "_decode_device")
         status = status_d.cpu().numpy()
     planned = planned[:n_frames]
     return out, np.where(planned != 0, planned, status).astype(np.int32)
 
 
-def _keep_gif_frames(name, out, status, device):
-    """(frames, kept) of one GIF video: the frames in front of the first one that failed."""
+def _keep_video_frames(fmt: _VideoFormat, name, out, status):
+    """(frames, kept) of one video in one file: the frames in front of the first one that failed (the later ones are
+    deltas on it)."""
     bad = np.flatnonzero(status != 0)
     n = int(bad[0]) if bad.size else len(status)
     if bad.size:
-        log.warning("dropping frames %d.. of %s: %s", n, name, L.GIF_STATUS.get(int(status[n]), int(status[n])))
+        if fmt.raise_in_keep:   # what only the decoders see
+            _refuse(fmt, [name], [status[n]])
+        log.warning("dropping frames %d.. of %s: %s", n, name, fmt.status.get(int(status[n]), int(status[n])))
     return out[:n], np.arange(n, dtype=np.int64)
 
 
@@ -428,238 +492,61 @@ def _empty_video(device):
     return torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=device), np.zeros(0, np.int64)
 
 
-def _decode_gif_files(names, paths, raw, raw_off, raw_size, info, device, threads: int, entropy: str):
-    """The GIF videos of a call, from paths (host route) or from their bytes in one host tensor `raw` -> one
-    (frames, kept) per file.  info: their probe rows.  Files of one logical screen share one call."""
+def _decode_video_files(fmt: _VideoFormat, names, paths, raw, raw_off, raw_size, info, device, threads: int,
+                        entropy: str):
+    """The videos of one format of a call, one file each, from paths (host route) or from their bytes in one host
+    tensor `raw` -> one (frames, kept) per file.  info: their probe rows.  Files of one key (_VideoFormat.n_key) share
+    one call.  A refusal by name is raised for the whole call before any group decodes."""
     import torch
-    _raise_unsupported_gif(names, info[:, 5])
+    _refuse(fmt, names, info[:, -1])
     results: List[Optional[Tuple]] = [None] * len(names)
     groups: dict = {}
     for i, row in enumerate(info):
-        if int(row[2]) > 0 and int(row[5]) != 1:   # a file with frames, of a size the decoders take
-            groups.setdefault((int(row[0]), int(row[1])), []).append(i)
+        # A file with frames, of a size the decoders take.  Only a WebP probe can give frames on a canvas without
+        # width or height (a still whose VP8L header it could not read); the GIF and APNG probes give a zero width or
+        # height only with zero frames (csrc/vge_gif.cpp, csrc/vge_apng.cpp: both return in front of the first frame,
+        # and every file of tests/gif_cases.py and tests/apng_cases.py agrees), and vge_gif_decode refuses such a
+        # screen outright (screen_ok).
+        if int(row[fmt.count_col]) > 0 and int(row[-1]) != 1 and int(row[0]) > 0 and int(row[1]) > 0:
+            groups.setdefault(tuple(int(x) for x in row[:fmt.n_key]), []).append(i)
         else:
-            log.warning("no decodable frame in %s: %s", names[i], L.GIF_STATUS.get(int(row[5]), int(row[5])))
+            log.warning("no decodable frame in %s: %s", names[i], fmt.status.get(int(row[-1]), int(row[-1])))
             results[i] = _empty_video(device)
     raw_d = None
     if entropy == "device" and groups:
         with torch.cuda.device(device):
             raw_d = raw.to(device, non_blocking=True)   # the one upload: every group decodes out of this buffer
-    for screen, members in groups.items():
-        counts = [int(info[i, 2]) for i in members]
-        total, blocks = sum(counts), int(sum(info[i, 4] for i in members))
-        if entropy == "device":
-            with torch.cuda.device(device):
-                out, status = _gif_decode_group_device(raw.numpy(), raw_d, raw_off[members], raw_size[members], screen,
-                                                       total, blocks, threads)
-        elif paths is not None:
-            out, status = _gif_decode_group([paths[i] for i in members], None, None, None, screen, total, device,
-                                            threads)
-        else:
-            out, status = _gif_decode_group(None, raw, raw_off[members], raw_size[members], screen, total, device,
-                                            threads)
-        o = 0
-        for i, n in zip(members, counts):
-            results[i] = _keep_gif_frames(names[i], out[o:o + n], status[o:o + n], device)
-            if results[i][1].size == 0:
-                log.warning("no decodable frame in %s", names[i])
-            o += n
-    return results
-
-
-def _load_gif_videos(paths: List[str], device, threads: int, entropy: str):
-    """load_videos for the GIF videos of a call."""
-    if entropy == "device":
-        raw, raw_off, raw_size = _read_files(paths, threads, pin=True)
-        info = gif_probe_mem(raw.numpy(), raw_off, raw_size, threads)
-        return _decode_gif_files(paths, None, raw, raw_off, raw_size, info, device, threads, entropy)
-    return _decode_gif_files(paths, paths, None, None, None, gif_probe(paths, threads), device, threads, entropy)
-
-
-def decode_gifs(data, offsets, device=None, threads: int = 0, entropy: Optional[str] = None):
-    """GIF videos packed in host memory -- (data, offsets[F + 1]): file i at data[offsets[i]:offsets[i + 1]] of a
-    one-dimensional uint8 CPU tensor -- -> one (frames, kept) per file, as load_videos gives them.  entropy "host" (the
-    default without a GPU) decodes on host threads (vge_gif_decode_mem) and uploads the pixels to `device`; entropy
-    "device" (the default with one) uploads the file bytes and runs vge_gif_plan_mem and vge_gif_decode_device.  The
-    plan walks every sub-block of every file on the host, so a buffer that lives on a GPU is refused, not copied back."""
-    import torch
-    if not (isinstance(data, torch.Tensor) and data.dtype == torch.uint8 and data.dim() == 1):
-        raise ValueError("data must be a one-dimensional uint8 tensor")
-    if data.device.type != "cpu":
-        raise ValueError("decode_gifs needs the file bytes in host memory: the plan walks every data sub-block on "
-                         "the host; pass a CPU tensor (entropy='device' uploads it once)")
-    off = np.ascontiguousarray(offsets.cpu().numpy() if isinstance(offsets, torch.Tensor) else offsets, np.int64)
-    if off.ndim != 1 or off.size < 1:
-        raise ValueError("offsets must be int64 [F + 1]")
-    device = _resolve_device(device)
-    if entropy is None:
-        entropy = "device" if device.type == "cuda" else "host"
-    if entropy not in ("host", "device"):
-        raise ValueError(f"entropy must be 'host' or 'device', not {entropy!r}")
-    if entropy == "device" and device.type != "cuda":
-        raise ValueError("entropy='device' needs a GPU")
-    F = off.size - 1
-    if F == 0:
-        return []
-    starts, sizes = off[:F].copy(), np.diff(off)
-    if (sizes < 0).any() or off[0] < 0 or off[F] > data.numel():
-        raise ValueError("offsets must be non-decreasing and inside data")
-    data = data.contiguous()
-    names = [f"file {i}" for i in range(F)]
-    info = gif_probe_mem(data.numpy(), starts, sizes, threads)
-    return _decode_gif_files(names, None, data, starts, sizes, info, device, threads, entropy)
-
-
-# ---- lossless WebP videos and frames (include/vge_webp.h)
-
-def _webp_rows(info, n: int) -> np.ndarray:
-    return np.array([[i.width, i.height, i.n_frames, i.vp8l_bytes, i.n_chunks, i.status] for i in info[:n]],
-                    dtype=np.int64).reshape(-1, 6)
-
-
-def webp_probe(paths: Sequence[PathLike], threads: int = 0) -> np.ndarray:
-    """Headers and chunk structure only: int64 [n, 6] rows of (canvas width, canvas height, frames, VP8L payload
-    bytes, chunks, status) (vge_webp_probe)."""
-    paths = [os.fspath(p) for p in paths]
-    info = (L.WebpInfo * max(len(paths), 1))()
-    if paths:
-        L.load().vge_webp_probe(_paths_array(paths), len(paths), int(threads), info)
-    return _webp_rows(info, len(paths))
-
-
-def webp_probe_mem(data: np.ndarray, offsets: np.ndarray, sizes: np.ndarray, threads: int = 0) -> np.ndarray:
-    """webp_probe() for files in host memory: file i is data[offsets[i]:offsets[i] + sizes[i]] (vge_webp_probe_mem)."""
-    n = len(offsets)
-    info = (L.WebpInfo * max(n, 1))()
-    if n:
-        offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
-        L.load().vge_webp_probe_mem(data.ctypes.data, data.size, offsets.ctypes.data, sizes.ctypes.data, n,
-                                    int(threads), info)
-    return _webp_rows(info, n)
-
-
-def _raise_unsupported_webp(names, statuses) -> None:
-    for p, s in zip(names, statuses):
-        if int(s) in L.WEBP_UNSUPPORTED:
-            raise UnsupportedWebpError(
-                f"{p}: unsupported WebP: {L.WEBP_UNSUPPORTED[int(s)]} ({L.WEBP_STATUS[int(s)]})")
-
-
-def _webp_decode_group(paths, data, offsets, sizes, canvas, n_frames: int, device, threads: int):
-    """The WebP files of one canvas on host threads, from paths or (paths None) from files in host memory (data: a
-    uint8 CPU tensor) -> (uint8 [n_frames, H, W, 3] tensor on `device`, int32 status [n_frames]): vge_webp_decode /
-    vge_webp_decode_mem into pinned memory, then one upload.  n_frames: the probe's sum."""
-    import torch
-    lib = L.load()
-    w, h = canvas
-    on_gpu = device.type == "cuda"
-    out = torch.empty((n_frames, h, w, 3), dtype=torch.uint8, pin_memory=on_gpu)
-    status = np.zeros(n_frames, np.int32)
-    if paths is not None:
-        lib.vge_webp_decode(_paths_array(paths), len(paths), int(threads), w, h, n_frames, out.data_ptr(),
-                            status.ctypes.data, None, None)
-    else:
-        offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
-        lib.vge_webp_decode_mem(data.data_ptr(), int(data.numel()), offsets.ctypes.data, sizes.ctypes.data,
-                                len(offsets), int(threads), w, h, n_frames, out.data_ptr(), status.ctypes.data, None,
-                                None)
-    if on_gpu:
-        with torch.cuda.device(device):
-            out = out.to(device, non_blocking=True)
-    return out, status
-
-
-def _webp_decode_group_device(data_h: np.ndarray, data_d, offsets: np.ndarray, sizes: np.ndarray, canvas,
-                              n_frames: int, threads: int):
-    """The WebP files of one canvas, their bytes both in host memory (data_h, which only the plan's chunk walk reads)
-    and on the GPU (data_d) -> (uint8 [n_frames, H, W, 3] tensor on that GPU, int32 status [n_frames]):
-    vge_webp_plan_mem on the host, one upload of the descriptors, vge_webp_decode_device on the current stream; the
-    one host synchronisation is the copy of the statuses at the end.  n_frames: the probe's sum."""
-    import torch
-    lib = L.load()
-    dev = data_d.device
-    w, h = canvas
-    offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
-    descs = (L.WebpDesc * max(n_frames, 1))()
-    planned = np.zeros(max(n_frames, 1), np.int32)
-    n_descs, ws_bytes = C.c_int64(0), C.c_int64(0)
-    lib.vge_webp_plan_mem(data_h.ctypes.data, data_h.size, offsets.ctypes.data, sizes.ctypes.data, len(offsets),
-                          int(threads), w, h, descs, n_frames, C.byref(n_descs), planned.ctypes.data, None,
-                          C.byref(ws_bytes))
-    if n_descs.value != n_frames:
-        raise L.VgeError("vge_webp_plan_mem: " + lib.vge_last_error().decode(errors="replace"))
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev)
-        descs_d = torch.frombuffer(descs, dtype=torch.uint8).to(dev)
-        ws = torch.empty(int(ws_bytes.value), dtype=torch.uint8, device=dev)
-        status_d = torch.empty(n_frames, dtype=torch.int32, device=dev)
-        out = torch.empty((n_frames, h, w, 3), dtype=torch.uint8, device=dev)
-        L.check(lib.vge_webp_decode_device(data_d.data_ptr(), int(data_d.numel()), descs_d.data_ptr(), n_frames,
-                                           n_frames, len(offsets), w, h, ws.data_ptr(), int(ws.numel()),
-                                           out.data_ptr(), status_d.data_ptr(), stream.cuda_stream),
-                "vge_webp_decode_device")
-        status = status_d.cpu().numpy()
-    planned = planned[:n_frames]
-    return out, np.where(planned != 0, planned, status).astype(np.int32)
-
-
-def _keep_webp_frames(name, out, status, device):
-    """(frames, kept) of one WebP video: the frames in front of the first one that failed."""
-    bad = np.flatnonzero(status != 0)
-    n = int(bad[0]) if bad.size else len(status)
-    if bad.size:
-        if int(status[n]) in L.WEBP_UNSUPPORTED:   # what only the decoders see: the group capacity
-            _raise_unsupported_webp([name], [status[n]])
-        log.warning("dropping frames %d.. of %s: %s", n, name, L.WEBP_STATUS.get(int(status[n]), int(status[n])))
-    return out[:n], np.arange(n, dtype=np.int64)
-
-
-def _decode_webp_files(names, paths, raw, raw_off, raw_size, info, device, threads: int, entropy: str):
-    """The WebP files of a call, from paths (host route) or from their bytes in one host tensor `raw` -> one
-    (frames, kept) per file.  info: their probe rows.  Files of one canvas share one call."""
-    import torch
-    _raise_unsupported_webp(names, info[:, 5])
-    results: List[Optional[Tuple]] = [None] * len(names)
-    groups: dict = {}
-    for i, row in enumerate(info):
-        if int(row[2]) > 0 and int(row[5]) != 1 and int(row[0]) > 0 and int(row[1]) > 0:
-            groups.setdefault((int(row[0]), int(row[1])), []).append(i)
-        else:
-            log.warning("no decodable frame in %s: %s", names[i], L.WEBP_STATUS.get(int(row[5]), int(row[5])))
-            results[i] = _empty_video(device)
-    raw_d = None
-    if entropy == "device" and groups:
-        with torch.cuda.device(device):
-            raw_d = raw.to(device, non_blocking=True)   # the one upload: every group decodes out of this buffer
-    for canvas, members in groups.items():
-        counts = [int(info[i, 2]) for i in members]
+    for key, members in groups.items():
+        counts = [int(info[i, fmt.count_col]) for i in members]
         total = sum(counts)
         if entropy == "device":
+            seg_cap = int(sum(info[i, fmt.seg_col] for i in members)) if fmt.seg_col is not None else 0
             with torch.cuda.device(device):
-                out, status = _webp_decode_group_device(raw.numpy(), raw_d, raw_off[members], raw_size[members],
-                                                        canvas, total, threads)
+                out, status = _video_decode_group_device(fmt, raw.numpy(), raw_d, raw_off[members], raw_size[members],
+                                                         key, total, seg_cap, threads)
         elif paths is not None:
-            out, status = _webp_decode_group([paths[i] for i in members], None, None, None, canvas, total, device,
-                                             threads)
+            out, status = _video_decode_group(fmt, [paths[i] for i in members], None, None, None, key, total, device,
+                                              threads)
         else:
-            out, status = _webp_decode_group(None, raw, raw_off[members], raw_size[members], canvas, total, device,
-                                             threads)
+            out, status = _video_decode_group(fmt, None, raw, raw_off[members], raw_size[members], key, total, device,
+                                              threads)
         o = 0
         for i, n in zip(members, counts):
-            results[i] = _keep_webp_frames(names[i], out[o:o + n], status[o:o + n], device)
+            results[i] = _keep_video_frames(fmt, names[i], out[o:o + n], status[o:o + n])
             if results[i][1].size == 0:
                 log.warning("no decodable frame in %s", names[i])
             o += n
     return results
 
 
-def _load_webp_files(paths: List[str], device, threads: int, entropy: str):
-    """One (frames, kept) per WebP file of a call."""
+def _load_video_files(fmt: _VideoFormat, paths: List[str], device, threads: int, entropy: str):
+    """load_videos for the videos of one format that are one file each: one (frames, kept) per file."""
     if entropy == "device":
         raw, raw_off, raw_size = _read_files(paths, threads, pin=True)
-        info = webp_probe_mem(raw.numpy(), raw_off, raw_size, threads)
-        return _decode_webp_files(paths, None, raw, raw_off, raw_size, info, device, threads, entropy)
-    return _decode_webp_files(paths, paths, None, None, None, webp_probe(paths, threads), device, threads, entropy)
+        info = _probe_mem(fmt, raw.numpy(), raw_off, raw_size, threads)
+        return _decode_video_files(fmt, paths, None, raw, raw_off, raw_size, info, device, threads, entropy)
+    return _decode_video_files(fmt, paths, paths, None, None, None, _probe(fmt, paths, threads), device, threads,
+                               entropy)
 
 
 def _load_webp_still_videos(vids: List[List[str]], device, threads: int, entropy: str):
@@ -667,7 +554,7 @@ def _load_webp_still_videos(vids: List[List[str]], device, threads: int, entropy
     frames of a video have one size (a file of another size is refused with a ValueError that names it)."""
     import torch
     flat = [p for v in vids for p in v]
-    per_file = _load_webp_files(flat, device, threads, entropy)
+    per_file = _load_video_files(_WEBP, flat, device, threads, entropy)
     results, o = [], 0
     for v in vids:
         frames, kept, size = [], [], None
@@ -687,187 +574,74 @@ def _load_webp_still_videos(vids: List[List[str]], device, threads: int, entropy
     return results
 
 
+def _packed_offsets(data, offsets, fmt: Optional[_VideoFormat] = None) -> np.ndarray:
+    """The first check of the decode_* calls: files packed in a one-dimensional uint8 tensor and their offsets[F + 1]
+    as a contiguous int64 array.  fmt: a format whose plan needs the file bytes in host memory."""
+    import torch
+    if not (isinstance(data, torch.Tensor) and data.dtype == torch.uint8 and data.dim() == 1):
+        raise ValueError("data must be a one-dimensional uint8 tensor")
+    if fmt is not None and data.device.type != "cpu":
+        raise ValueError(f"{fmt.public} needs the file bytes in host memory: the plan walks every {fmt.noun} on the "
+                         "host; pass a CPU tensor (entropy='device' uploads it once)")
+    off = np.ascontiguousarray(offsets.cpu().numpy() if isinstance(offsets, torch.Tensor) else offsets, np.int64)
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError("offsets must be int64 [F + 1]")
+    return off
+
+
+def _entropy_word(entropy: Optional[str], default: str) -> str:
+    if entropy is None:
+        entropy = default
+    if entropy not in ("host", "device"):
+        raise ValueError(f"entropy must be 'host' or 'device', not {entropy!r}")
+    return entropy
+
+
+def _file_spans(data, off: np.ndarray):
+    """offsets[F + 1] -> (starts [F], sizes [F]); a call without files is checked no further."""
+    F = off.size - 1
+    starts, sizes = off[:F].copy(), np.diff(off)
+    if F and ((sizes < 0).any() or off[0] < 0 or off[F] > data.numel()):
+        raise ValueError("offsets must be non-decreasing and inside data")
+    return starts, sizes
+
+
+def _check_packed(data, offsets, device, entropy: Optional[str], fmt: _VideoFormat):
+    """The arguments of decode_gifs / decode_webps / decode_apngs -> (device, entropy, starts [F], sizes [F])."""
+    off = _packed_offsets(data, offsets, fmt)
+    device = _resolve_device(device)
+    entropy = _entropy_word(entropy, "device" if device.type == "cuda" else "host")
+    if entropy == "device" and device.type != "cuda":
+        raise ValueError("entropy='device' needs a GPU")
+    return (device, entropy) + _file_spans(data, off)
+
+
+def _decode_packed_videos(fmt: _VideoFormat, data, offsets, device, threads: int, entropy: Optional[str]):
+    device, entropy, starts, sizes = _check_packed(data, offsets, device, entropy, fmt)
+    if starts.size == 0:
+        return []
+    data = data.contiguous()
+    names = [f"file {i}" for i in range(starts.size)]
+    info = _probe_mem(fmt, data.numpy(), starts, sizes, threads)
+    return _decode_video_files(fmt, names, None, data, starts, sizes, info, device, threads, entropy)
+
+
+def decode_gifs(data, offsets, device=None, threads: int = 0, entropy: Optional[str] = None):
+    """GIF videos packed in host memory -- (data, offsets[F + 1]): file i at data[offsets[i]:offsets[i + 1]] of a
+    one-dimensional uint8 CPU tensor -- -> one (frames, kept) per file, as load_videos gives them.  entropy "host" (the
+    default without a GPU) decodes on host threads (vge_gif_decode_mem) and uploads the pixels to `device`; entropy
+    "device" (the default with one) uploads the file bytes and runs vge_gif_plan_mem and vge_gif_decode_device.  The
+    plan walks every sub-block of every file on the host, so a buffer that lives on a GPU is refused, not copied back."""
+    return _decode_packed_videos(_GIF, data, offsets, device, threads, entropy)
+
+
 def decode_webps(data, offsets, device=None, threads: int = 0, entropy: Optional[str] = None):
     """WebP files packed in host memory -- (data, offsets[F + 1]): file i at data[offsets[i]:offsets[i + 1]] of a
     one-dimensional uint8 CPU tensor -- -> one (frames, kept) per file, as load_videos gives them.  entropy "host" (the
     default without a GPU) decodes on host threads (vge_webp_decode_mem) and uploads the pixels to `device`; entropy
     "device" (the default with one) uploads the file bytes and runs vge_webp_plan_mem and vge_webp_decode_device.  The
     plan walks every chunk of every file on the host, so a buffer that lives on a GPU is refused, not copied back."""
-    import torch
-    if not (isinstance(data, torch.Tensor) and data.dtype == torch.uint8 and data.dim() == 1):
-        raise ValueError("data must be a one-dimensional uint8 tensor")
-    if data.device.type != "cpu":
-        raise ValueError("decode_webps needs the file bytes in host memory: the plan walks every chunk on the host; "
-                         "pass a CPU tensor (entropy='device' uploads it once)")
-    off = np.ascontiguousarray(offsets.cpu().numpy() if isinstance(offsets, torch.Tensor) else offsets, np.int64)
-    if off.ndim != 1 or off.size < 1:
-        raise ValueError("offsets must be int64 [F + 1]")
-    device = _resolve_device(device)
-    if entropy is None:
-        entropy = "device" if device.type == "cuda" else "host"
-    if entropy not in ("host", "device"):
-        raise ValueError(f"entropy must be 'host' or 'device', not {entropy!r}")
-    if entropy == "device" and device.type != "cuda":
-        raise ValueError("entropy='device' needs a GPU")
-    F = off.size - 1
-    if F == 0:
-        return []
-    starts, sizes = off[:F].copy(), np.diff(off)
-    if (sizes < 0).any() or off[0] < 0 or off[F] > data.numel():
-        raise ValueError("offsets must be non-decreasing and inside data")
-    data = data.contiguous()
-    names = [f"file {i}" for i in range(F)]
-    info = webp_probe_mem(data.numpy(), starts, sizes, threads)
-    return _decode_webp_files(names, None, data, starts, sizes, info, device, threads, entropy)
-
-
-# ---- APNG videos (include/vge_apng.h)
-
-def _apng_rows(info, n: int) -> np.ndarray:
-    return np.array([[i.width, i.height, i.color_type, i.bit_depth, i.interlace, i.n_frames, i.default_image,
-                      i.n_chunks, i.data_bytes, i.status] for i in info[:n]], dtype=np.int64).reshape(-1, 10)
-
-
-def apng_probe(paths: Sequence[PathLike], threads: int = 0) -> np.ndarray:
-    """Chunk headers only: int64 [n, 10] rows of (canvas width, canvas height, colour type, bit depth, interlace,
-    frames, whether frame 0 is a default image outside the animation, non-empty IDAT / fdAT payloads, their bytes,
-    status) (vge_apng_probe).  A PNG that is not animated is a video of one frame."""
-    paths = [os.fspath(p) for p in paths]
-    info = (L.ApngInfo * max(len(paths), 1))()
-    if paths:
-        L.load().vge_apng_probe(_paths_array(paths), len(paths), int(threads), info)
-    return _apng_rows(info, len(paths))
-
-
-def apng_probe_mem(data: np.ndarray, offsets: np.ndarray, sizes: np.ndarray, threads: int = 0) -> np.ndarray:
-    """apng_probe() for files in host memory: file i is data[offsets[i]:offsets[i] + sizes[i]] (vge_apng_probe_mem)."""
-    n = len(offsets)
-    info = (L.ApngInfo * max(n, 1))()
-    if n:
-        offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
-        L.load().vge_apng_probe_mem(data.ctypes.data, data.size, offsets.ctypes.data, sizes.ctypes.data, n,
-                                    int(threads), info)
-    return _apng_rows(info, n)
-
-
-def _apng_decode_group(paths, data, offsets, sizes, key, n_frames: int, device, threads: int):
-    """The APNG files of one (canvas width, canvas height, colour type) on host threads, from paths or (paths None)
-    from files in host memory (data: a uint8 CPU tensor) -> (uint8 [n_frames, H, W, 3] tensor on `device`, int32
-    status [n_frames]): vge_apng_decode / vge_apng_decode_mem into pinned memory, then one upload.  n_frames: the
-    probe's sum."""
-    import torch
-    lib = L.load()
-    w, h, ct = key
-    on_gpu = device.type == "cuda"
-    out = torch.empty((n_frames, h, w, 3), dtype=torch.uint8, pin_memory=on_gpu)
-    status = np.zeros(n_frames, np.int32)
-    if paths is not None:
-        lib.vge_apng_decode(_paths_array(paths), len(paths), int(threads), w, h, ct, n_frames, out.data_ptr(),
-                            status.ctypes.data, None, None)
-    else:
-        offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
-        lib.vge_apng_decode_mem(data.data_ptr(), int(data.numel()), offsets.ctypes.data, sizes.ctypes.data,
-                                len(offsets), int(threads), w, h, ct, n_frames, out.data_ptr(), status.ctypes.data,
-                                None, None)
-    if on_gpu:
-        with torch.cuda.device(device):
-            out = out.to(device, non_blocking=True)
-    return out, status
-
-
-def _apng_decode_group_device(data_h: np.ndarray, data_d, offsets: np.ndarray, sizes: np.ndarray, key, n_frames: int,
-                              n_chunks: int, threads: int):
-    """The APNG files of one (canvas width, canvas height, colour type), their bytes both in host memory (data_h, which
-    only the plan's chunk walk reads) and on the GPU (data_d) -> (uint8 [n_frames, H, W, 3] tensor on that GPU, int32
-    status [n_frames]): vge_apng_plan_mem on the host, one upload of the descriptors and segments,
-    vge_apng_decode_device on the current stream; the one host synchronisation is the copy of the statuses at the end.
-    n_frames, n_chunks: the probe's sums."""
-    import torch
-    lib = L.load()
-    dev = data_d.device
-    w, h, ct = key
-    offsets, sizes = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(sizes, np.int64)
-    descs = (L.ApngDesc * max(n_frames, 1))()
-    segs = (L.ApngSegment * max(n_chunks, 1))()
-    planned = np.zeros(max(n_frames, 1), np.int32)
-    n_descs, n_segs, ws_bytes = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-    lib.vge_apng_plan_mem(data_h.ctypes.data, data_h.size, offsets.ctypes.data, sizes.ctypes.data, len(offsets),
-                          int(threads), w, h, ct, descs, n_frames, C.byref(n_descs), segs, n_chunks, C.byref(n_segs),
-                          planned.ctypes.data, None, C.byref(ws_bytes))
-    if n_descs.value != n_frames:
-        raise L.VgeError("vge_apng_plan_mem: " + lib.vge_last_error().decode(errors="replace"))
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev)
-        descs_d = torch.frombuffer(descs, dtype=torch.uint8).to(dev)
-        segs_d = torch.frombuffer(segs, dtype=torch.uint8).to(dev)
-        ws = torch.empty(int(ws_bytes.value), dtype=torch.uint8, device=dev)
-        status_d = torch.empty(n_frames, dtype=torch.int32, device=dev)
-        out = torch.empty((n_frames, h, w, 3), dtype=torch.uint8, device=dev)
-        L.check(lib.vge_apng_decode_device(data_d.data_ptr(), int(data_d.numel()), descs_d.data_ptr(), n_frames,
-                                           segs_d.data_ptr(), n_segs.value, n_frames, len(offsets), w, h, ct,
-                                           ws.data_ptr(), int(ws.numel()), out.data_ptr(), status_d.data_ptr(),
-                                           stream.cuda_stream),
-                "vge_apng_decode_device")
-        status = status_d.cpu().numpy()
-    planned = planned[:n_frames]
-    return out, np.where(planned != 0, planned, status).astype(np.int32)
-
-
-def _keep_apng_frames(name, out, status, device):
-    """(frames, kept) of one APNG video: the frames in front of the first one that failed."""
-    bad = np.flatnonzero(status != 0)
-    n = int(bad[0]) if bad.size else len(status)
-    if bad.size:
-        log.warning("dropping frames %d.. of %s: %s", n, name, L.APNG_STATUS.get(int(status[n]), int(status[n])))
-    return out[:n], np.arange(n, dtype=np.int64)
-
-
-def _decode_apng_files(names, paths, raw, raw_off, raw_size, info, device, threads: int, entropy: str):
-    """The APNG videos of a call, from paths (host route) or from their bytes in one host tensor `raw` -> one
-    (frames, kept) per file.  info: their probe rows.  Files of one canvas and colour type share one call."""
-    import torch
-    _raise_unsupported_png(names, info[:, -1])
-    results: List[Optional[Tuple]] = [None] * len(names)
-    groups: dict = {}
-    for i, row in enumerate(info):
-        if int(row[5]) > 0 and int(row[-1]) != 1:   # a file with frames, of a size the decoders take
-            groups.setdefault((int(row[0]), int(row[1]), int(row[2])), []).append(i)
-        else:
-            log.warning("no decodable frame in %s: %s", names[i], L.APNG_STATUS.get(int(row[-1]), int(row[-1])))
-            results[i] = _empty_video(device)
-    raw_d = None
-    if entropy == "device" and groups:
-        with torch.cuda.device(device):
-            raw_d = raw.to(device, non_blocking=True)   # the one upload: every group decodes out of this buffer
-    for key, members in groups.items():
-        counts = [int(info[i, 5]) for i in members]
-        total, chunks = sum(counts), int(sum(info[i, 7] for i in members))
-        if entropy == "device":
-            with torch.cuda.device(device):
-                out, status = _apng_decode_group_device(raw.numpy(), raw_d, raw_off[members], raw_size[members], key,
-                                                        total, chunks, threads)
-        elif paths is not None:
-            out, status = _apng_decode_group([paths[i] for i in members], None, None, None, key, total, device,
-                                             threads)
-        else:
-            out, status = _apng_decode_group(None, raw, raw_off[members], raw_size[members], key, total, device,
-                                             threads)
-        o = 0
-        for i, n in zip(members, counts):
-            results[i] = _keep_apng_frames(names[i], out[o:o + n], status[o:o + n], device)
-            if results[i][1].size == 0:
-                log.warning("no decodable frame in %s", names[i])
-            o += n
-    return results
-
-
-def _load_apng_videos(paths: List[str], device, threads: int, entropy: str):
-    """load_videos for the APNG videos of a call."""
-    if entropy == "device":
-        raw, raw_off, raw_size = _read_files(paths, threads, pin=True)
-        info = apng_probe_mem(raw.numpy(), raw_off, raw_size, threads)
-        return _decode_apng_files(paths, None, raw, raw_off, raw_size, info, device, threads, entropy)
-    return _decode_apng_files(paths, paths, None, None, None, apng_probe(paths, threads), device, threads, entropy)
+    return _decode_packed_videos(_WEBP, data, offsets, device, threads, entropy)
 
 
 def decode_apngs(data, offsets, device=None, threads: int = 0, entropy: Optional[str] = None):
@@ -876,32 +650,7 @@ def decode_apngs(data, offsets, device=None, threads: int = 0, entropy: Optional
     default without a GPU) decodes on host threads (vge_apng_decode_mem) and uploads the pixels to `device`; entropy
     "device" (the default with one) uploads the file bytes and runs vge_apng_plan_mem and vge_apng_decode_device.  The
     plan walks every chunk of every file on the host, so a buffer that lives on a GPU is refused, not copied back."""
-    import torch
-    if not (isinstance(data, torch.Tensor) and data.dtype == torch.uint8 and data.dim() == 1):
-        raise ValueError("data must be a one-dimensional uint8 tensor")
-    if data.device.type != "cpu":
-        raise ValueError("decode_apngs needs the file bytes in host memory: the plan walks every chunk on the host; "
-                         "pass a CPU tensor (entropy='device' uploads it once)")
-    off = np.ascontiguousarray(offsets.cpu().numpy() if isinstance(offsets, torch.Tensor) else offsets, np.int64)
-    if off.ndim != 1 or off.size < 1:
-        raise ValueError("offsets must be int64 [F + 1]")
-    device = _resolve_device(device)
-    if entropy is None:
-        entropy = "device" if device.type == "cuda" else "host"
-    if entropy not in ("host", "device"):
-        raise ValueError(f"entropy must be 'host' or 'device', not {entropy!r}")
-    if entropy == "device" and device.type != "cuda":
-        raise ValueError("entropy='device' needs a GPU")
-    F = off.size - 1
-    if F == 0:
-        return []
-    starts, sizes = off[:F].copy(), np.diff(off)
-    if (sizes < 0).any() or off[0] < 0 or off[F] > data.numel():
-        raise ValueError("offsets must be non-decreasing and inside data")
-    data = data.contiguous()
-    names = [f"file {i}" for i in range(F)]
-    info = apng_probe_mem(data.numpy(), starts, sizes, threads)
-    return _decode_apng_files(names, None, data, starts, sizes, info, device, threads, entropy)
+    return _decode_packed_videos(_APNG, data, offsets, device, threads, entropy)
 
 
 def _first_good_key(rows: np.ndarray, n_key: int):
@@ -922,18 +671,23 @@ def _keep_decoded(names, out, status, status_names, device):
     return out, kept
 
 
+def _unreadable_video(names, device):
+    """The empty video of frames of which none could be read."""
+    for p in names:
+        log.warning("dropping frame %s: unreadable", p)
+    return _empty_video(device)
+
+
 def _decode_frames_png(data, starts, sizes, names, device, threads: int, entropy: str):
     """decode_frames for PNG files.  The plan walks chunk headers that lie all over a file, so for data on a GPU the
     file bytes are copied to the host once for it (the pixels never are)."""
     import torch
     data_h = data.cpu() if data.device.type == "cuda" else data
     info = png_probe_mem(data_h.numpy(), starts, sizes, threads)
-    _raise_unsupported_png(names, info[:, -1])
+    _refuse(_PNG, names, info[:, -1])
     key = _first_good_key(info, 3)
     if key is None:
-        for p in names:
-            log.warning("dropping frame %s: unreadable", p)
-        return torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=device), np.zeros(0, np.int64)
+        return _unreadable_video(names, device)
     if entropy == "device":
         data_d = data if data.device.type == "cuda" else data.to(device)
         with torch.cuda.device(device):
@@ -971,31 +725,20 @@ def decode_frames(data, offsets, device=None, threads: int = 0, entropy: Optiona
     message.
     PNG files (the first file's signature decides) take the same arguments: entropy "host" is vge_png_decode_mem,
     entropy "device" vge_png_plan_mem and vge_png_decode_device; UnsupportedPngError for an unsupported kind."""
-    import torch
-    if not (isinstance(data, torch.Tensor) and data.dtype == torch.uint8 and data.dim() == 1):
-        raise ValueError("data must be a one-dimensional uint8 tensor")
-    off = np.ascontiguousarray(offsets.cpu().numpy() if isinstance(offsets, torch.Tensor) else offsets, np.int64)
-    if off.ndim != 1 or off.size < 1:
-        raise ValueError("offsets must be int64 [F + 1]")
-    data_on_gpu = data.device.type == "cuda"
-    if entropy is None:
-        entropy = "device" if data_on_gpu else "host"
-    if entropy not in ("host", "device"):
-        raise ValueError(f"entropy must be 'host' or 'device', not {entropy!r}")
+    off = _packed_offsets(data, offsets)
+    data_on_gpu = data.device.type == "cuda"   # such data stays where it is, and is decoded there
+    entropy = _entropy_word(entropy, "device" if data_on_gpu else "host")
     if entropy == "host" and data_on_gpu:
         raise ValueError("entropy='host' needs data on the CPU")
     device = data.device if data_on_gpu else _resolve_device(device)
     if entropy == "device" and device.type != "cuda":
         raise ValueError("entropy='device' needs a GPU")
     data = data.contiguous()
-    F = off.size - 1
-    starts, sizes = off[:F].copy(), np.diff(off)
-    names = [f"file {i}" for i in range(F)]
-    empty = (torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=device), np.zeros(0, np.int64))
+    starts, sizes = _file_spans(data, off)
+    F = starts.size
     if F == 0:
-        return empty
-    if (sizes < 0).any() or off[0] < 0 or off[F] > data.numel():
-        raise ValueError("offsets must be non-decreasing and inside data")
+        return _empty_video(device)
+    names = [f"file {i}" for i in range(F)]
     if data[int(starts[0]):int(starts[0]) + min(int(sizes[0]), 8)].cpu().numpy().tobytes() == PNG_SIGNATURE:
         return _decode_frames_png(data, starts, sizes, names, device, threads, entropy)
     key = None
@@ -1009,12 +752,9 @@ def decode_frames(data, offsets, device=None, threads: int = 0, entropy: Optiona
     else:
         info = probe_mem(data.numpy(), starts, sizes, threads)
         _raise_unsupported(names, info[:, 5])
-        good = np.flatnonzero(info[:, 5] == 0)
-        key = tuple(int(x) for x in info[good[0], :5]) if good.size else None
+        key = _first_good_key(info, 5)
     if key is None:
-        for p in names:
-            log.warning("dropping frame %s: unreadable", p)
-        return empty
+        return _unreadable_video(names, device)
     lay = make_layout(*key)
     if entropy == "device":
         data_d = data if data_on_gpu else data.to(device)
@@ -1022,13 +762,7 @@ def decode_frames(data, offsets, device=None, threads: int = 0, entropy: Optiona
         _raise_unsupported(names, status)
     else:
         out, status = _decode_group_mem(data, starts, sizes, lay, device, threads)
-    for p, s in zip(names, status):
-        if s != 0:
-            log.warning("dropping frame %s: %s", p, L.JPEG_STATUS.get(int(s), int(s)))
-    kept = np.flatnonzero(status == 0)
-    if kept.size != F:
-        out = out[torch.as_tensor(kept, device=device)]
-    return out, kept
+    return _keep_decoded(names, out, status, L.JPEG_STATUS, device)
 
 
 SUBSAMPLING = {"420": (2, 2), "422": (2, 1), "444": (1, 1)}   # luma sampling factors (h0, v0)
@@ -1258,37 +992,21 @@ def load_videos(videos: Sequence[Union[PathLike, Sequence[PathLike]]], device=No
         raise ValueError(f"entropy must be 'host' or 'device', not {entropy!r}")
     if entropy == "device" and device.type != "cuda":
         raise ValueError("entropy='device' needs a GPU")
-    is_webp = [isinstance(v, (str, os.PathLike)) and _is_webp_file(os.fspath(v)) for v in videos]
-    is_gif = [isinstance(v, (str, os.PathLike)) and not wp and _is_gif_file(os.fspath(v))
-              for v, wp in zip(videos, is_webp)]
-    is_apng = [isinstance(v, (str, os.PathLike)) and not wp and not g and _is_apng_file(os.fspath(v))
-               for v, wp, g in zip(videos, is_webp, is_gif)]
-    one_file = [g or wp or a for g, wp, a in zip(is_gif, is_webp, is_apng)]   # a video in one file: no frame list
-    vids = [[] if one else _list_video(v) if isinstance(v, (str, os.PathLike)) else [os.fspath(p) for p in v]
-            for v, one in zip(videos, one_file)]
-    is_png = [_is_png_file(v[0]) if v else False for v in vids]
-    is_stills = [bool(v) and _is_webp_file(v[0]) for v in vids]
+    # what each entry is: a video in one file ("gif", "webp", "apng": no frame list), or a folder or list of still WebP
+    # frames ("stills"), of PNG frames ("png") or of JPEG frames ("jpg") by its first file
+    kinds = [_file_signature(os.fspath(v)) if isinstance(v, (str, os.PathLike)) else None for v in videos]
+    vids = [[] if kind else _list_video(v) if isinstance(v, (str, os.PathLike)) else [os.fspath(p) for p in v]
+            for v, kind in zip(videos, kinds)]
+    kinds = [kind or {"webp": "stills", "apng": "png"}.get(_file_signature(v[0]) if v else None, "jpg")
+             for v, kind in zip(vids, kinds)]
+    loaders = [(name, partial(_load_video_files, VIDEO_FILE_FORMATS[name])) for name in ("apng", "gif", "webp")]
+    loaders += [("stills", _load_webp_still_videos), ("jpg", _load_jpeg_videos), ("png", _load_png_videos)]
     results: List[Optional[Tuple]] = [None] * len(vids)
-    apngs = [vi for vi, a in enumerate(is_apng) if a]
-    if apngs:
-        for vi, r in zip(apngs, _load_apng_videos([os.fspath(videos[vi]) for vi in apngs], device, threads, entropy)):
-            results[vi] = r
-    gifs = [vi for vi, g in enumerate(is_gif) if g]
-    if gifs:
-        for vi, r in zip(gifs, _load_gif_videos([os.fspath(videos[vi]) for vi in gifs], device, threads, entropy)):
-            results[vi] = r
-    webps = [vi for vi, wp in enumerate(is_webp) if wp]
-    if webps:
-        for vi, r in zip(webps, _load_webp_files([os.fspath(videos[vi]) for vi in webps], device, threads, entropy)):
-            results[vi] = r
-    stills = [vi for vi, k in enumerate(is_stills) if k]
-    if stills:
-        for vi, r in zip(stills, _load_webp_still_videos([vids[vi] for vi in stills], device, threads, entropy)):
-            results[vi] = r
-    for png, load in ((False, _load_jpeg_videos), (True, _load_png_videos)):
-        which = [vi for vi, k in enumerate(is_png) if k == png and not one_file[vi] and not is_stills[vi]]
+    for kind, load in loaders:   # in this order: of several files that are refused, the first loader's is raised
+        which = [vi for vi, k in enumerate(kinds) if k == kind]
         if which:
-            for vi, r in zip(which, load([vids[vi] for vi in which], device, threads, entropy)):
+            entries = [os.fspath(videos[vi]) if kind in VIDEO_FILE_FORMATS else vids[vi] for vi in which]
+            for vi, r in zip(which, load(entries, device, threads, entropy)):
                 results[vi] = r
     return results
 
@@ -1299,43 +1017,22 @@ def _list_video(folder: PathLike) -> List[str]:
     return list_frames(folder) or list_frames(folder, ext=".png") or list_frames(folder, ext=".webp")
 
 
-def _is_webp_file(path: str) -> bool:
-    """A path to a regular file that begins RIFF....WEBP: a WebP video or still."""
+def _file_signature(path: str) -> Optional[str]:
+    """What a path to a regular file is by its first bytes: "webp" (RIFF....WEBP: a WebP video or still), else "gif"
+    (GIF87a or GIF89a: a GIF video), else "apng" (the PNG signature: an APNG video, or a still PNG, which is a video of
+    one frame); None for any other file and for what is not a regular file."""
     try:
         if not os.path.isfile(path):
-            return False
+            return None
         with open(path, "rb") as f:
             head = f.read(12)
-        return len(head) == 12 and head[:4] == b"RIFF" and head[8:] == b"WEBP"
     except OSError:
-        return False
-
-
-def _is_gif_file(path: str) -> bool:
-    """A path to a regular file whose first six bytes are a GIF signature: a GIF video."""
-    try:
-        if not os.path.isfile(path):
-            return False
-        with open(path, "rb") as f:
-            return f.read(6) in GIF_SIGNATURES
-    except OSError:
-        return False
-
-
-def _is_apng_file(path: str) -> bool:
-    """A path to a regular file with the PNG signature: an APNG video (a still PNG is a video of one frame)."""
-    try:
-        return os.path.isfile(path) and _is_png_file(path)
-    except OSError:
-        return False
-
-
-def _is_png_file(path: str) -> bool:
-    try:
-        with open(path, "rb") as f:
-            return f.read(8) == PNG_SIGNATURE
-    except OSError:
-        return False
+        return None
+    if len(head) == 12 and head[:4] == b"RIFF" and head[8:] == b"WEBP":
+        return "webp"
+    if head[:6] in GIF_SIGNATURES:
+        return "gif"
+    return "apng" if head[:8] == PNG_SIGNATURE else None
 
 
 def _load_png_videos(vids: List[List[str]], device, threads: int, entropy: str):
@@ -1350,7 +1047,7 @@ def _load_png_videos(vids: List[List[str]], device, threads: int, entropy: str):
             raw_d = raw.to(device, non_blocking=True)   # the one upload: every group decodes out of this buffer
     else:
         info = png_probe(flat, threads)
-    _raise_unsupported_png(flat, info[:, -1])
+    _refuse(_PNG, flat, info[:, -1])
     keys = [_first_good_key(info[first_of[vi]:first_of[vi + 1]], 3) for vi in range(len(vids))]
     groups: dict = {}
     for vi, key in enumerate(keys):
@@ -1372,9 +1069,7 @@ def _load_png_videos(vids: List[List[str]], device, threads: int, entropy: str):
             o += n
     for vi, key in enumerate(keys):
         if key is None:
-            for p in vids[vi]:
-                log.warning("dropping frame %s: unreadable", p)
-            results[vi] = (torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=device), np.zeros(0, np.int64))
+            results[vi] = _unreadable_video(vids[vi], device)
     return results
 
 
@@ -1382,53 +1077,38 @@ def _load_jpeg_videos(vids: List[List[str]], device, threads: int, entropy: str)
     """load_videos for the JPEG videos of a call."""
     import torch
     flat = [p for v in vids for p in v]
+    first_of = np.concatenate([[0], np.cumsum([len(v) for v in vids])]).astype(np.int64)
     if entropy == "device":
         raw, raw_off, raw_size = _read_files(flat, threads, pin=True)
         info = probe_mem(raw.numpy(), raw_off, raw_size, threads)
         with torch.cuda.device(device):
             raw_d = raw.to(device, non_blocking=True)   # the one upload: every group decodes out of this buffer
-        first_of = np.concatenate([[0], np.cumsum([len(v) for v in vids])]).astype(np.int64)
     else:
         info = probe(flat, threads)
     _raise_unsupported(flat, info[:, 5])
     # a video's layout is its first readable frame's; frames of another size get the shape status and are dropped
-    groups, keys, f0 = {}, [], 0
-    for vi, v in enumerate(vids):
-        rows = info[f0:f0 + len(v)]
-        good = np.flatnonzero(rows[:, 5] == 0)
-        key = tuple(int(x) for x in rows[good[0], :5]) if good.size else None
-        keys.append(key)
+    keys = [_first_good_key(info[first_of[vi]:first_of[vi + 1]], 5) for vi in range(len(vids))]
+    groups: dict = {}
+    for vi, key in enumerate(keys):
         if key is not None:
             groups.setdefault(key, []).append(vi)
-        f0 += len(v)
     results: List[Optional[Tuple]] = [None] * len(vids)
     for key, members in groups.items():
         lay = make_layout(*key)
-        paths = [p for vi in members for p in vids[vi]]
         if entropy == "device":
             idx = np.concatenate([np.arange(first_of[vi], first_of[vi + 1]) for vi in members])
             with torch.cuda.device(device):
                 out, status = _decode_group_device(raw_d, raw_off[idx], raw_size[idx], lay)
         else:
-            out, status = _decode_group(paths, lay, device, threads)
+            out, status = _decode_group([p for vi in members for p in vids[vi]], lay, device, threads)
         o = 0
         for vi in members:
             n = len(vids[vi])
-            st = status[o:o + n]
-            for p, s in zip(vids[vi], st):
-                if s != 0:
-                    log.warning("dropping frame %s: %s", p, L.JPEG_STATUS.get(int(s), int(s)))
-            kept = np.flatnonzero(st == 0)
-            fr = out[o:o + n]
-            if kept.size != n:
-                fr = fr[torch.as_tensor(kept, device=device)]
-            results[vi] = (fr, kept)
+            results[vi] = _keep_decoded(vids[vi], out[o:o + n], status[o:o + n], L.JPEG_STATUS, device)
             o += n
     for vi, key in enumerate(keys):
         if key is None:
-            for p in vids[vi]:
-                log.warning("dropping frame %s: unreadable", p)
-            results[vi] = (torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=device), np.zeros(0, np.int64))
+            results[vi] = _unreadable_video(vids[vi], device)
     return results
 
 
