@@ -1,6 +1,8 @@
-// The gather kernel of the device decoders that read a stream cut into pieces (vge_png.hip: IDAT chunks; vge_gif.hip:
-// data sub-blocks; vge_apng.hip: IDAT and fdAT chunks): one workgroup per segment copies a payload to its place in the
-// frame's gathered run of the workspace, so that the bit reader sees one contiguous stream however the writer cut it.
+// What all the device frame decoders share (vge_png.hip, vge_gif.hip, vge_webp.hip, vge_apng.hip): the workgroup sizes,
+// the end of an entry function, and the gather kernel of those that read a stream cut into pieces (vge_png.hip: IDAT
+// chunks; vge_gif.hip: data sub-blocks; vge_apng.hip: IDAT and fdAT chunks): one workgroup per segment copies a payload
+// to its place in the frame's gathered run of the workspace, so that the bit reader sees one contiguous stream however
+// the writer cut it.
 //
 // Route supplies the call's argument struct and its descriptor check:
 //   Route::Args          with data, descs, segs, n_segs, n_descs, ws; descriptors with file_off, file_bytes, gat_off,
@@ -12,9 +14,22 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
+
+#include "vge_error.h"
+
 namespace vge_gather {
 
-constexpr int WIDE = 256;  // threads of a gather workgroup
+constexpr int WAVE = 64;   // threads of the per-frame workgroups: one wavefront
+constexpr int WIDE = 256;  // threads of the gather, Adler and compose workgroups
+
+// For an entry function after its memset and its launches: HIP's last error, which this clears, as the entry's
+// message.  False when there is none.
+inline bool hip_failed(const char* entry) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) vge::set_last_error(std::string(entry) + ": " + hipGetErrorString(e));
+  return e != hipSuccess;
+}
 
 template <class Route>
 __global__ __launch_bounds__(WIDE) void gather_kernel(typename Route::Args A) {

@@ -1,7 +1,7 @@
 // The device half of the GIF video front end (include/vge_gif.h): GIF files in device memory -> uint8 RGB frames, from
 // the host's plan (csrc/vge_gif.cpp: one descriptor per frame, one segment per data sub-block) and the file bytes alone.
 //
-//   gather    vge_gather.h's kernel, shared with the PNG route: each frame's sub-blocks into one run of the workspace.
+//   gather    vge_gather.h's kernel: each frame's sub-blocks into one run of the workspace.
 //   lzw       one wave per frame, the dictionary (4096 entries of 8 bytes) in LDS.  A batch is the next 64 codes: their
 //             widths depend only on how many codes were read since the last clear code, so lane l knows the width of
 //             code l, a wave scan gives its bit position, and all 64 are read at once.  A ballot finds the first clear
@@ -10,24 +10,16 @@
 //             same call the host decoder makes, executed by the whole wave on wave-uniform values; its running sum of
 //             string lengths is each code's output position.  Then every lane expands its own code: it walks the
 //             (prefix, suffix) chain backwards from LDS and stores the string's bytes last to first.
-//   compose   a row of workgroups per file (the file's first descriptor is found by a binary search on the owner
-//             field), a lane per screen pixel: it walks the file's frames in order with the canvas value and the
-//             pending restore in registers (vge_gif_lzw.h compose_pixel, the host's call), looks colours up in the
-//             file bytes and stores RGB for every frame.  It stops at the first frame whose status is set and gives
-//             the later frames that status.
+//   compose   vge_compose.h's kernel, with vge_gif_lzw.h's compose_pixel, the host's call, which looks colours up in
+//             the file bytes; a file's canvas starts as its first descriptor's first_rgb.
 //
-// Hard rules, the same as in vge_png.hip:
-//   - every descriptor and segment is checked against the sizes the host passed (data_bytes, workspace_bytes, n_frames,
-//     the screen) before anything is read or written through it;
-//   - a frame reads only its own file bytes and gathered run, writes only its own slot and its own output frame;
-//   - every loop consumes input bits or produces output; the chain walk is bounded by the string's length;
-//   - a bad code sets the frame's status (atomicCAS from 0: the first failure wins) and ends the frame;
-//   - no workgroup waits for another.
+// The hard rules are vge_compose.h's, and hold for the LZW kernel as well: a frame reads only its own gathered run and
+// writes only its own slot, every loop consumes input bits or produces output (the chain walk is bounded by the
+// string's length), and a bad code sets the frame's status and ends the frame.
 #include <hip/hip_runtime.h>
 
-#include <string>
-
 #include "../../include/vge_gif.h"
+#include "vge_compose.h"
 #include "vge_error.h"
 #include "vge_gather.h"
 #include "vge_gif_lzw.h"
@@ -37,8 +29,9 @@ namespace {
 using namespace vge_gif;
 using vge::set_last_error;
 
-constexpr int WAVE = 64;
-constexpr int WIDE = vge_gather::WIDE;  // threads of the gather and compose workgroups
+using vge_compose::reachable;
+using vge_gather::WAVE;
+using vge_gather::WIDE;
 
 struct Args {
   const uint8_t* data;
@@ -52,8 +45,6 @@ struct Args {
   int32_t* status;
   int32_t n_descs, n_frames, n_files, width, height;
 };
-
-__host__ __device__ inline int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 
 // 0: run it; -1: an unused slot (or nobody to report to); else the plan's code, or the code of a descriptor that does
 // not fit the call.
@@ -85,40 +76,20 @@ __device__ inline void fail(const Args& A, int frame, int code) {
   if (threadIdx.x == 0) atomicCAS(&A.status[frame], 0, code);
 }
 
+// What the shared kernels (vge_gather.h, vge_compose.h) need of this route.
 struct Route {
   using Args = ::Args;
+  using Pixel = vge_gif::Pixel;
   static constexpr int ERR_ARG = VGE_GIF_ERR_ARG;
   static __device__ int check_desc(const Args& A, const vge_gif_desc& d) { return ::check_desc(A, d); }
   static __device__ void fail(const Args& A, int frame, int code) { ::fail(A, frame, code); }
+  static __device__ Pixel first_pixel(const vge_gif_desc& d0) { return Pixel{d0.first_rgb, 0, 0}; }
+  static __device__ void step(Pixel& P, const Args& A, const vge_gif_desc& d, const vge_gif_desc&, int px, int py) {
+    compose_pixel(P, d, px, py, A.ws + d.slot_off, A.data + d.file_off + d.ct_off);
+  }
 };
 
 __device__ inline int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-// The first descriptor whose file is not below f (the plan emits files in increasing order); n_descs when there is none.
-__device__ int lower_bound_file(const Args& A, int f) {
-  int lo = 0, hi = A.n_descs;
-  while (lo < hi) {
-    const int mid = lo + (hi - lo) / 2;
-    if (A.descs[mid].file < f) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// Descriptor k continues the chain of k - 1: the same file, the next frame index.
-__device__ inline bool continues(const vge_gif_desc& prev, const vge_gif_desc& d) {
-  return prev.file == d.file && d.index > 0 && prev.index == d.index - 1;
-}
-
-// The compose kernel reaches descriptor k when the chain it belongs to starts at index 0 and that start is where the
-// search for its file lands.  Anything else is a descriptor array the plan does not emit: the frame is refused here,
-// so that no frame is left with status 0 and no pixels.
-__device__ bool reachable(const Args& A, int k) {
-  int j = k;
-  while (j > 0 && continues(A.descs[j - 1], A.descs[j])) --j;  // at most `index` steps
-  const vge_gif_desc h = A.descs[j];
-  return h.index == 0 && h.file >= 0 && h.file < A.n_files && lower_bound_file(A, h.file) == j;
-}
 
 __global__ __launch_bounds__(WAVE) void lzw_kernel(Args A) {
   __shared__ Entry table[TABLE];
@@ -207,42 +178,6 @@ __global__ __launch_bounds__(WAVE) void lzw_kernel(Args A) {
   }
 }
 
-__global__ __launch_bounds__(WIDE) void compose_kernel(Args A) {
-  const int64_t npix = (int64_t)A.width * A.height;
-  const int64_t pix = (int64_t)blockIdx.x * WIDE + threadIdx.x;
-  const bool active = pix < npix;
-  const int px = (int)(pix % A.width), py = (int)(pix / A.width);
-  const bool reporter = blockIdx.x == 0 && threadIdx.x == 0;
-  for (int f = blockIdx.y; f < A.n_files; f += gridDim.y) {  // a row of workgroups per file
-    const int k0 = lower_bound_file(A, f);
-    if (k0 >= A.n_descs) continue;
-    const vge_gif_desc d0 = A.descs[k0];
-    if (d0.file != f || d0.index != 0) continue;  // a file without frames; a headless chain was refused by the LZW kernel
-    Pixel P{d0.first_rgb, 0, 0};
-    int carried = 0;
-    for (int k = k0; k < A.n_descs; ++k) {
-      const vge_gif_desc d = A.descs[k];
-      if (k > k0 && !continues(A.descs[k - 1], d)) break;
-      const int chk = check_desc(A, d);
-      if (chk < 0) {  // an unused slot inside a file: nobody to report to, and the later frames are deltas on it
-        if (carried == 0) carried = VGE_GIF_ERR_ARG;
-        continue;
-      }
-      if (carried == 0) carried = chk > 0 ? chk : A.status[d.frame];
-      if (carried != 0) {
-        if (reporter) atomicCAS(&A.status[d.frame], 0, carried);
-        continue;
-      }
-      if (!active) continue;
-      compose_pixel(P, d, px, py, A.ws + d.slot_off, A.data + d.file_off + d.ct_off);
-      uint8_t* o = A.rgb + ((int64_t)d.frame * npix + pix) * 3;
-      o[0] = (uint8_t)P.canvas;
-      o[1] = (uint8_t)(P.canvas >> 8);
-      o[2] = (uint8_t)(P.canvas >> 16);
-    }
-  }
-}
-
 }  // namespace
 
 // For tools/bench_frames.py, which times the kernels one by one: bit 0 gather, 1 lzw, 2 compose.
@@ -275,7 +210,7 @@ extern "C" int vge_gif_decode_device(const uint8_t* data, int64_t data_bytes, co
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (hipMemsetAsync(status, 0, (size_t)n_frames * 4, s) != hipSuccess) {
-    set_last_error(std::string("vge_gif_decode_device: ") + hipGetErrorString(hipGetLastError()));
+    vge_gather::hip_failed("vge_gif_decode_device");
     return VGE_GIF_ERR_HIP;
   }
   if (n_descs == 0) return VGE_GIF_OK;
@@ -300,12 +235,7 @@ extern "C" int vge_gif_decode_device(const uint8_t* data, int64_t data_bytes, co
     hipLaunchKernelGGL(vge_gather::gather_kernel<Route>, dim3((unsigned)n_segs), dim3(WIDE), 0, s, A);
   if (stages & 2) hipLaunchKernelGGL(lzw_kernel, dim3((unsigned)n_descs), dim3(WAVE), 0, s, A);
   if ((stages & 4) && n_files > 0)
-    hipLaunchKernelGGL(compose_kernel, dim3(pix_groups, (unsigned)(n_files < 65535 ? n_files : 65535)), dim3(WIDE), 0, s,
-                       A);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_last_error(std::string("vge_gif_decode_device: ") + hipGetErrorString(e));
-    return VGE_GIF_ERR_HIP;
-  }
-  return VGE_GIF_OK;
+    hipLaunchKernelGGL(vge_compose::compose_kernel<Route>,
+                       dim3(pix_groups, (unsigned)(n_files < 65535 ? n_files : 65535)), dim3(WIDE), 0, s, A);
+  return vge_gather::hip_failed("vge_gif_decode_device") ? VGE_GIF_ERR_HIP : VGE_GIF_OK;
 }

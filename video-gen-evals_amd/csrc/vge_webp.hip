@@ -17,24 +17,17 @@
 //               another lane of the band wrote; the band's first row reads the last row of the band before it from
 //               the slot, after a block fence and barrier.  The rightmost column's top-right is the row's own first
 //               pixel.  Cross-colour, add-green and palette unbundling are pointwise.
-//   compose     a row of workgroups per file (the file's first descriptor is found by a binary search on the owner
-//               field), a lane per canvas pixel: it walks the file's frames in order with the RGBA canvas pixel and
-//               its disposed value in registers (compose_pixel, the host's call) and stores RGB for every frame.  It
-//               stops at the first frame whose status is set and gives the later frames that status.
+//   compose     vge_compose.h's kernel, with vge_webp_vp8l.h's compose_pixel, the host's call, on an RGBA canvas
+//               pixel; it is the step that needs the frame before, whose disposal it applies.
 //
-// Hard rules, the same as in vge_gif.hip:
-//   - every descriptor is checked against the sizes the host passed (data_bytes, workspace_bytes, n_frames, the
-//     canvas) before anything is read or written through it;
-//   - a frame reads only its own payload, writes only its own slot and its own output frame; what the entropy kernel
-//     leaves for the transforms is checked again before it is used;
-//   - every loop consumes input bits or produces output;
-//   - a bad stream sets the frame's status (atomicCAS from 0: the first failure wins) and ends the frame;
-//   - no workgroup waits for another.
+// The hard rules are vge_compose.h's, and hold for the entropy and transform kernels as well: a frame reads only its
+// own payload and writes only its own slot, every loop consumes input bits or produces output, a bad stream sets the
+// frame's status and ends the frame, and what the entropy kernel leaves for the transforms is checked again before it
+// is used.
 #include <hip/hip_runtime.h>
 
-#include <string>
-
 #include "../../include/vge_webp.h"
+#include "vge_compose.h"
 #include "vge_error.h"
 #include "vge_webp_vp8l.h"
 
@@ -43,8 +36,9 @@ namespace {
 using namespace vge_webp;
 using vge::set_last_error;
 
-constexpr int WAVE = 64;
-constexpr int WIDE = 256;  // threads of the compose workgroups
+using vge_compose::reachable;
+using vge_gather::WAVE;
+using vge_gather::WIDE;
 
 struct Args {
   const uint8_t* data;
@@ -80,31 +74,20 @@ __device__ inline void fail(const Args& A, int frame, int code) {
   if (threadIdx.x == 0) atomicCAS(&A.status[frame], 0, code);
 }
 
-__device__ inline int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-// The first descriptor whose file is not below f (the plan emits files in increasing order); n_descs when there is none.
-__device__ int lower_bound_file(const Args& A, int f) {
-  int lo = 0, hi = A.n_descs;
-  while (lo < hi) {
-    const int mid = lo + (hi - lo) / 2;
-    if (A.descs[mid].file < f) lo = mid + 1;
-    else hi = mid;
+// What the shared compose kernel (vge_compose.h) needs of this route.
+struct Route {
+  using Args = ::Args;
+  using Pixel = vge_webp::Pixel;
+  static constexpr int ERR_ARG = VGE_WEBP_ERR_ARG;
+  static __device__ int check_desc(const Args& A, const vge_webp_desc& d) { return ::check_desc(A, d); }
+  static __device__ Pixel first_pixel(const vge_webp_desc&) { return Pixel{0, 0}; }
+  static __device__ void step(Pixel& P, const Args& A, const vge_webp_desc& d, const vge_webp_desc& prev, int px,
+                              int py) {
+    compose_pixel(P, d, prev, px, py, reinterpret_cast<const uint32_t*>(A.ws + d.slot_off));
   }
-  return lo;
-}
+};
 
-__device__ inline bool continues(const vge_webp_desc& prev, const vge_webp_desc& d) {
-  return prev.file == d.file && d.index > 0 && prev.index == d.index - 1;
-}
-
-// As in vge_gif.hip: the compose kernel reaches descriptor k when its chain starts at index 0 and that start is where
-// the search for its file lands.
-__device__ bool reachable(const Args& A, int k) {
-  int j = k;
-  while (j > 0 && continues(A.descs[j - 1], A.descs[j])) --j;  // at most `index` steps
-  const vge_webp_desc h = A.descs[j];
-  return h.index == 0 && h.file >= 0 && h.file < A.n_files && lower_bound_file(A, h.file) == j;
-}
+__device__ inline int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 __global__ __launch_bounds__(WAVE) void entropy_kernel(Args A) {
   __shared__ Scratch S;
@@ -227,45 +210,6 @@ __global__ __launch_bounds__(WAVE) void transform_kernel(Args A) {
   }
 }
 
-__global__ __launch_bounds__(WIDE) void compose_kernel(Args A) {
-  const int64_t npix = (int64_t)A.width * A.height;
-  const int64_t pix = (int64_t)blockIdx.x * WIDE + threadIdx.x;
-  const bool active = pix < npix;
-  const int px = (int)(pix % A.width), py = (int)(pix / A.width);
-  const bool reporter = blockIdx.x == 0 && threadIdx.x == 0;
-  for (int f = blockIdx.y; f < A.n_files; f += gridDim.y) {  // a row of workgroups per file
-    const int k0 = lower_bound_file(A, f);
-    if (k0 >= A.n_descs) continue;
-    const vge_webp_desc d0 = A.descs[k0];
-    if (d0.file != f || d0.index != 0) continue;  // a file without frames; a headless chain was refused before
-    Pixel P{0, 0};
-    int carried = 0;
-    vge_webp_desc prev = d0;
-    for (int k = k0; k < A.n_descs; ++k) {
-      const vge_webp_desc d = A.descs[k];
-      if (k > k0 && !continues(A.descs[k - 1], d)) break;
-      const int chk = check_desc(A, d);
-      if (chk < 0) {  // an unused slot inside a file: nobody to report to, and the later frames are deltas on it
-        if (carried == 0) carried = VGE_WEBP_ERR_ARG;
-        continue;
-      }
-      if (carried == 0) carried = chk > 0 ? chk : A.status[d.frame];
-      if (carried != 0) {
-        if (reporter) atomicCAS(&A.status[d.frame], 0, carried);
-        continue;
-      }
-      if (active) {
-        compose_pixel(P, d, prev, px, py, reinterpret_cast<const uint32_t*>(A.ws + d.slot_off));
-        uint8_t* o = A.rgb + ((int64_t)d.frame * npix + pix) * 3;
-        o[0] = (uint8_t)P.canvas;
-        o[1] = (uint8_t)(P.canvas >> 8);
-        o[2] = (uint8_t)(P.canvas >> 16);
-      }
-      prev = d;
-    }
-  }
-}
-
 }  // namespace
 
 // For tools/bench_frames.py, which times the kernels one by one: bit 0 entropy, 1 transforms, 2 compose.
@@ -296,7 +240,7 @@ extern "C" int vge_webp_decode_device(const uint8_t* data, int64_t data_bytes, c
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (hipMemsetAsync(status, 0, (size_t)n_frames * 4, s) != hipSuccess) {
-    set_last_error(std::string("vge_webp_decode_device: ") + hipGetErrorString(hipGetLastError()));
+    vge_gather::hip_failed("vge_webp_decode_device");
     return VGE_WEBP_ERR_HIP;
   }
   if (n_descs == 0) return VGE_WEBP_OK;
@@ -318,12 +262,7 @@ extern "C" int vge_webp_decode_device(const uint8_t* data, int64_t data_bytes, c
   if (stages & 1) hipLaunchKernelGGL(entropy_kernel, dim3((unsigned)n_descs), dim3(WAVE), 0, s, A);
   if (stages & 2) hipLaunchKernelGGL(transform_kernel, dim3((unsigned)n_descs), dim3(WAVE), 0, s, A);
   if ((stages & 4) && n_files > 0)
-    hipLaunchKernelGGL(compose_kernel, dim3(pix_groups, (unsigned)(n_files < 65535 ? n_files : 65535)), dim3(WIDE), 0, s,
-                       A);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_last_error(std::string("vge_webp_decode_device: ") + hipGetErrorString(e));
-    return VGE_WEBP_ERR_HIP;
-  }
-  return VGE_WEBP_OK;
+    hipLaunchKernelGGL(vge_compose::compose_kernel<Route>,
+                       dim3(pix_groups, (unsigned)(n_files < 65535 ? n_files : 65535)), dim3(WIDE), 0, s, A);
+  return vge_gather::hip_failed("vge_webp_decode_device") ? VGE_WEBP_ERR_HIP : VGE_WEBP_OK;
 }
