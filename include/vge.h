@@ -244,7 +244,8 @@ int vge_centroid_finalize(const float* sums, const float* counts, int C, int d, 
 /* ---------------------------------------------------------------------------------------------
  * Held-out validation loss: the checkpoint-selection criterion of the reference's training loop
  * (evaluate_test_set, train.py:286-333: TCL + 10 x SupConWithHardNegatives against shuffled, reversed and static
- * windows; train.py:450-455 keeps the checkpoint with the lowest value).  Forward only.  Every reduction runs in an
+ * windows; train.py:450-455 keeps the checkpoint with the lowest value), and the gradients of its two losses for the
+ * training step (the *_grad entries at the end).  Every reduction runs in an
  * order fixed by the problem size (no floating-point atomics): two calls on the same input give the same bits.
  *
  * vge_time_gather: out[b,t,:] = feats[b, src[b,t], :] -- partial_shuffle_within_window, reverse_sequence and
@@ -273,6 +274,21 @@ int vge_centroid_finalize(const float* sums, const float* counts, int C, int d, 
  * vge_centroid_distance: evaluate_test_set_centroid_distance's per-sample term (train.py:366-378):
  *   dist[i] = || normalize(emb_i) - centroids[labels[i]] ||_2 (F.normalize eps 1e-12), float32; a label outside
  *   [0, C) gives NaN (the reference's `continue`).  emb [n,d], centroids [C,d], dist [n]: device float.
+ *
+ * vge_tcl_loss_grad / vge_hardneg_loss_grad: the same losses with their gradients (what a training step needs), one
+ *   call each.  `loss` is written by the forward entry's own kernels, so it has the forward's bits, NaN included.  The
+ *   gradients are float64 inside (f32 products accumulated in f64, f64 exp) and are rounded to float32 once, at the
+ *   store; no floating-point atomics, every sum in an order fixed by (B, d): two calls give the same bits.  The
+ *   [B,B] matrix is never stored (the dot products are recomputed) and the workspace stays O(B).
+ *   vge_tcl_loss_grad: grad: device float [B,d], not aliasing emb;  with s_jk = <z_j,z_k>, e_jk = exp(s_jk / t):
+ *       k in P(j): W_jk = (e_jk / t - k1 exp(-s_jk)) / den_j - 1 / (t |P(j)|)
+ *       k in N(j): W_jk = k2 e_jk / (t den_j);   W_jj = 0;   grad_j = (1 / B) sum_k (W_jk + W_kj) z_k
+ *     the derivative of the loss above wherever every |P| >= 1 (the row-j broadcast and the row-i reading are then
+ *     the same function of z).  When a label appears once `loss` is NaN as the forward's is and `grad` is
+ *     unspecified: the caller skips that step.  Limits of vge_tcl_loss; workspace >= vge_tcl_grad_workspace_bytes(B).
+ *   vge_hardneg_loss_grad: grad_anchor / grad_neg: device float [B,d], 16-byte aligned, aliasing nothing;  with
+ *       p_i = sigmoid((<a_i,n_i> - <a_i,a_i>) / t):  grad_neg_i = p_i a_i / (t B),
+ *       grad_anchor_i = p_i (n_i - 2 a_i) / (t B)   (anchor is the positive too: both of its uses carry gradient).
  */
 int vge_time_gather(const float* feats, const int32_t* src, int B, int T, int D, float* out, vge_stream_t stream);
 size_t vge_tcl_workspace_bytes(int B);
@@ -280,6 +296,11 @@ int vge_tcl_loss(const float* emb, const int32_t* labels, int B, int d, double t
                  void* workspace, size_t workspace_bytes, double* loss, vge_stream_t stream);
 int vge_hardneg_loss(const float* anchor, const float* neg, int B, int d, double temperature, double* loss,
                      vge_stream_t stream);
+size_t vge_tcl_grad_workspace_bytes(int B);
+int vge_tcl_loss_grad(const float* emb, const int32_t* labels, int B, int d, double temperature, double k1, double k2,
+                      void* workspace, size_t workspace_bytes, double* loss, float* grad, vge_stream_t stream);
+int vge_hardneg_loss_grad(const float* anchor, const float* neg, int B, int d, double temperature, double* loss,
+                          float* grad_anchor, float* grad_neg, vge_stream_t stream);
 int vge_centroid_distance(const float* emb, const int32_t* labels, const float* centroids, int n, int C, int d,
                           float* dist, vge_stream_t stream);
 

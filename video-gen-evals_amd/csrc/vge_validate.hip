@@ -13,6 +13,11 @@
 //   hardneg_kernel         SupConWithHardNegatives(anchor, anchor, neg) (losses.py:37-56): cross entropy of the two
 //                          logits (<a,a>, <a,n>) / temperature against class 0, mean over the batch.
 //   centroid_dist_kernel   || normalize(emb_i) - centroid[label_i] ||_2 (train.py:366-378).
+// and the gradients of the two losses for the training step (vge_tcl_loss_grad / vge_hardneg_loss_grad; the loss
+// itself comes from the forward kernels above, launched as they are):
+//   tcl_count_kernel       |P(j)| per row.
+//   tcl_grad_kernel        grad_j = (1 / B) sum_k (W_jk + W_kj) z_k, the dot products recomputed a third time.
+//   hardneg_grad_kernel    grad_neg_i = p_i a_i / (temp B), grad_anchor_i = p_i (n_i - 2 a_i) / (temp B).
 //
 // Every reduction runs in an order fixed by the problem size alone: each thread owns a fixed set of columns, wave
 // sums are xor butterflies, wave partials are added in wave order; no floating-point atomics, and no kernel waits
@@ -170,6 +175,93 @@ __global__ void __launch_bounds__(256) mean_kernel(const double* __restrict__ x,
   if (threadIdx.x == 0) out[0] = (((red[0] + red[1]) + red[2]) + red[3]) / (double)n;
 }
 
+// ---------------------------------------------------------------------------------------------- TCL gradient
+// grid ceil(B / 256).  cnt[j] = |P(j)|: the rows with j's label, without j.
+__global__ void __launch_bounds__(256) tcl_count_kernel(const int* __restrict__ lab, int B, double* __restrict__ cnt) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= B) return;
+  const int lj = lab[j];
+  int n = 0;
+  for (int k = 0; k < B; ++k) n += (lab[k] == lj);
+  cnt[j] = (double)(n - 1);
+}
+
+// grid ceil(B / TCL_R).  grad_j = (1 / B) sum_k (W_jk + W_kj) z_k for the workgroup's TCL_R rows j, with
+//   k in P(j): W_jk = (e_jk / temp - k1 exp(-s_jk)) / den_j - 1 / (temp |P(j)|)
+//   k in N(j): W_jk = k2 e_jk / (temp den_j),          W_jj = 0
+// (the derivative of mean_j [log den_j - (1 / (temp |P(j)|)) sum_{k in P(j)} s_jk], which is the loss whenever every
+// |P| >= 1).  The columns k go by in chunks of TCL_TH: thread t forms the TCL_R coefficients of column k0 + t from
+// the recomputed dot products and leaves them in LDS; then thread (g, c) = (t / d, t % d), g < G = TCL_TH / d, adds
+// coef[r][kk] * z[k0 + kk][c] for kk = g, g + G, ... in that order.  After the last chunk the G partials of a
+// column are added in g order.  Nothing but (B, d) enters the order of any sum.
+__global__ void __launch_bounds__(TCL_TH) tcl_grad_kernel(const float* __restrict__ emb, const int* __restrict__ lab,
+                                                         int B, int d, double temp, double k1, double k2,
+                                                         const double* __restrict__ den,
+                                                         const double* __restrict__ cnt, float* __restrict__ grad) {
+  __shared__ double zr[TCL_R][TCL_DMAX];
+  __shared__ double coef[TCL_R][TCL_TH];   // after the last chunk: the partial sums, [TCL_R][g * d + c]
+  __shared__ double dr[TCL_R], pr[TCL_R];  // 1 / den_j and 1 / (temp |P(j)|) of the workgroup's rows
+  __shared__ int lr[TCL_R];
+  const int r0 = blockIdx.x * TCL_R;
+  tcl_load_rows(emb, B, d, r0, zr);
+  if (threadIdx.x < TCL_R) {
+    const int j = r0 + threadIdx.x;
+    lr[threadIdx.x] = (j < B) ? lab[j] : 0;
+    dr[threadIdx.x] = (j < B) ? 1.0 / den[j] : 0.0;
+    pr[threadIdx.x] = (j < B) ? 1.0 / (temp * cnt[j]) : 0.0;
+  }
+  __syncthreads();
+  const int G = TCL_TH / d, g = threadIdx.x / d, c = threadIdx.x - g * d;
+  double acc[TCL_R];
+#pragma unroll
+  for (int r = 0; r < TCL_R; ++r) acc[r] = 0.0;
+  for (int k0 = 0; k0 < B; k0 += TCL_TH) {
+    const int k = k0 + threadIdx.x;
+    if (k < B) {
+      double dot[TCL_R];
+      tcl_dots(emb + (size_t)k * d, d, zr, dot);
+      const int lk = lab[k];
+      const double dk = 1.0 / den[k], pk = 1.0 / (temp * cnt[k]);
+#pragma unroll
+      for (int r = 0; r < TCL_R; ++r) {
+        const double e = exp(dot[r] / temp) / temp;
+        double w;
+        if (r0 + r >= B || r0 + r == k) w = 0.0;
+        else if (lr[r] != lk) w = k2 * e * dr[r] + k2 * e * dk;
+        else {
+          const double num = e - k1 * exp(-dot[r]);
+          w = (num * dr[r] - pr[r]) + (num * dk - pk);
+        }
+        coef[r][threadIdx.x] = w;
+      }
+    }
+    __syncthreads();
+    if (g < G) {
+      const int nk = min(TCL_TH, B - k0);
+      for (int kk = g; kk < nk; kk += G) {
+        const double z = (double)emb[(size_t)(k0 + kk) * d + c];
+#pragma unroll
+        for (int r = 0; r < TCL_R; ++r) acc[r] = fma(coef[r][kk], z, acc[r]);
+      }
+    }
+    __syncthreads();
+  }
+  if (g < G) {
+#pragma unroll
+    for (int r = 0; r < TCL_R; ++r) coef[r][threadIdx.x] = acc[r];
+  }
+  __syncthreads();
+  if (g == 0) {
+#pragma unroll
+    for (int r = 0; r < TCL_R; ++r) {
+      if (r0 + r >= B) break;
+      double s = coef[r][c];
+      for (int q = 1; q < G; ++q) s += coef[r][q * d + c];
+      grad[(size_t)(r0 + r) * d + c] = (float)(s / (double)B);
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------- hard negatives
 // one workgroup of 16 waves (the order of the sum is then a function of B alone, without a second launch).  Wave w
 // takes the row groups w, w + 16, ...: HN_R consecutive rows per group, loaded together (one float4 per lane covers a
@@ -229,6 +321,50 @@ __global__ void __launch_bounds__(HN_WAVES * 64) hardneg_kernel(const float* __r
     for (int k = 0; k < HN_WAVES; ++k)
       for (int r = 0; r < HN_R; ++r) t += red[k][r];
     loss[0] = t / (double)B;
+  }
+}
+
+// gradient of hardneg_kernel's loss: one wave per row, 4 rows per workgroup.  With p_i = sigmoid((<a_i,n_i> -
+// <a_i,a_i>) / temp):  grad_neg_i = p_i a_i / (temp B),  grad_anchor_i = p_i (n_i - 2 a_i) / (temp B)  (anchor is
+// also the positive, so both of its uses carry gradient).  Rows are independent: no sum crosses a wave.
+__global__ void __launch_bounds__(256) hardneg_grad_kernel(const float* __restrict__ a, const float* __restrict__ ng,
+                                                           int B, int d, double temp, float* __restrict__ ga,
+                                                           float* __restrict__ gn) {
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (i >= B) return;
+  const float* ai = a + (size_t)i * d;
+  const float* ni = ng + (size_t)i * d;
+  double ap = 0.0, ah = 0.0;
+  for (int c = lane * 4; c < d; c += 256) {
+    const float4 x = *reinterpret_cast<const float4*>(ai + c);
+    const float4 y = *reinterpret_cast<const float4*>(ni + c);
+    ap = fma((double)x.x, (double)x.x, ap);
+    ap = fma((double)x.y, (double)x.y, ap);
+    ap = fma((double)x.z, (double)x.z, ap);
+    ap = fma((double)x.w, (double)x.w, ap);
+    ah = fma((double)x.x, (double)y.x, ah);
+    ah = fma((double)x.y, (double)y.y, ah);
+    ah = fma((double)x.z, (double)y.z, ah);
+    ah = fma((double)x.w, (double)y.w, ah);
+  }
+  const double m = (wave_sum_d(ah) - wave_sum_d(ap)) / temp;
+  const double em = exp(-fabs(m));                              // sigmoid without overflow on either side
+  const double p = (m >= 0.0 ? 1.0 : em) / (1.0 + em);
+  const double s = p / (temp * (double)B);
+  for (int c = lane * 4; c < d; c += 256) {
+    const float4 x = *reinterpret_cast<const float4*>(ai + c);
+    const float4 y = *reinterpret_cast<const float4*>(ni + c);
+    float4 u, v;
+    u.x = (float)(s * ((double)y.x - 2.0 * (double)x.x));
+    u.y = (float)(s * ((double)y.y - 2.0 * (double)x.y));
+    u.z = (float)(s * ((double)y.z - 2.0 * (double)x.z));
+    u.w = (float)(s * ((double)y.w - 2.0 * (double)x.w));
+    v.x = (float)(s * (double)x.x);
+    v.y = (float)(s * (double)x.y);
+    v.z = (float)(s * (double)x.z);
+    v.w = (float)(s * (double)x.w);
+    *reinterpret_cast<float4*>(ga + (size_t)i * d + c) = u;
+    *reinterpret_cast<float4*>(gn + (size_t)i * d + c) = v;
   }
 }
 
@@ -322,6 +458,41 @@ int vge_hardneg_loss(const float* anchor, const float* neg, int B, int d, double
   if (!aligned16(anchor) || !aligned16(neg)) return fail(VGE_ERR_ARG, "vge_hardneg_loss: anchor / neg must be 16-byte aligned");
   if (!(temperature > 0.0)) return fail(VGE_ERR_ARG, "vge_hardneg_loss: temperature must be positive");
   hipLaunchKernelGGL(hardneg_kernel, dim3(1), dim3(HN_WAVES * 64), 0, S(stream), anchor, neg, B, d, temperature, loss);
+  HIPCHK(hipGetLastError());
+  return VGE_OK;
+}
+
+size_t vge_tcl_grad_workspace_bytes(int B) { return B > 0 ? (size_t)B * 3 * sizeof(double) : 0; }
+
+int vge_tcl_loss_grad(const float* emb, const int32_t* labels, int B, int d, double temperature, double k1, double k2,
+                      void* workspace, size_t workspace_bytes, double* loss, float* grad, vge_stream_t stream) {
+  if (!grad) return fail(VGE_ERR_ARG, "vge_tcl_loss_grad: null grad");
+  if (grad == emb) return fail(VGE_ERR_ARG, "vge_tcl_loss_grad: grad must not alias emb");
+  if (B > 0 && workspace_bytes < vge_tcl_grad_workspace_bytes(B))
+    return fail(VGE_ERR_ARG, "vge_tcl_loss_grad: workspace smaller than vge_tcl_grad_workspace_bytes(B)");
+  // the loss is the forward's own three launches (den and rowloss in the first 2 B doubles of the workspace)
+  const int st = vge_tcl_loss(emb, labels, B, d, temperature, k1, k2, workspace, workspace_bytes, loss, stream);
+  if (st != VGE_OK) return st;
+  const double* den = static_cast<const double*>(workspace);
+  double* cnt = static_cast<double*>(workspace) + 2 * (size_t)B;
+  hipLaunchKernelGGL(tcl_count_kernel, dim3((B + 255) / 256), dim3(256), 0, S(stream), labels, B, cnt);
+  hipLaunchKernelGGL(tcl_grad_kernel, dim3((B + TCL_R - 1) / TCL_R), dim3(TCL_TH), 0, S(stream), emb, labels, B, d,
+                     temperature, k1, k2, den, cnt, grad);
+  HIPCHK(hipGetLastError());
+  return VGE_OK;
+}
+
+int vge_hardneg_loss_grad(const float* anchor, const float* neg, int B, int d, double temperature, double* loss,
+                          float* grad_anchor, float* grad_neg, vge_stream_t stream) {
+  if (!grad_anchor || !grad_neg) return fail(VGE_ERR_ARG, "vge_hardneg_loss_grad: null grad_anchor / grad_neg");
+  if (!aligned16(grad_anchor) || !aligned16(grad_neg))
+    return fail(VGE_ERR_ARG, "vge_hardneg_loss_grad: grad_anchor / grad_neg must be 16-byte aligned");
+  if (grad_anchor == grad_neg || grad_anchor == anchor || grad_anchor == neg || grad_neg == anchor || grad_neg == neg)
+    return fail(VGE_ERR_ARG, "vge_hardneg_loss_grad: grad_anchor / grad_neg must not alias each other or an input");
+  const int st = vge_hardneg_loss(anchor, neg, B, d, temperature, loss, stream);   // the forward's own launch
+  if (st != VGE_OK) return st;
+  hipLaunchKernelGGL(hardneg_grad_kernel, dim3((B + 3) / 4), dim3(256), 0, S(stream), anchor, neg, B, d, temperature,
+                     grad_anchor, grad_neg);
   HIPCHK(hipGetLastError());
   return VGE_OK;
 }

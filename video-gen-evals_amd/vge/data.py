@@ -201,6 +201,79 @@ def enumerate_test_windows(ds: NpzVideoDataset, clip_len: int, stride: int,
     return samples
 
 
+class PKBatchSampler:
+    """The reference's balanced batch sampler (utils.py:922-1015): every batch holds P classes with K window indices
+    each, P * K in all; an epoch is N // (P * K) batches.
+
+    Given the same numpy Generator it draws from it in the reference's order and yields the reference's batches:
+      epoch state   per class (first-appearance order) one shuffle of its indices into a queue, then one shuffle of
+                    the class order.  Drawn by the constructor and AGAIN at the start of every __iter__ (the
+                    reference resets twice before its first epoch; so does this).
+      a batch       the next P classes of the order; when fewer than P are left, the rest of the order plus its
+                    first classes, and the order is reshuffled for the next cycle (the cursor stays behind the
+                    classes just taken from the old order, as in the reference).  Per class the first K of its
+                    queue, or, when the queue holds fewer, what is left topped up by choice(with replacement) from
+                    all of the class's indices.  Then one shuffle of the batch.
+    Every batch therefore has exactly P * K entries and drop_last never drops one; the argument is kept for the
+    reference's signature.
+
+    generator None gives default_rng() -- unseeded, which is how the reference's training constructs it
+    (train.py:169).  vge.train passes default_rng(seed) instead, so a run here is repeatable where the reference's
+    is not; no other behaviour differs."""
+
+    def __init__(self, labels, P: int, K: int, drop_last: bool = False, generator=None):
+        self.labels = np.asarray(labels)
+        self.P, self.K, self.drop_last = int(P), int(K), drop_last
+        self.rng = np.random.default_rng() if generator is None else generator
+        self.class_to_indices: Dict[int, List[int]] = {}
+        for i, y in enumerate(self.labels):
+            self.class_to_indices.setdefault(int(y), []).append(i)
+        self.classes = list(self.class_to_indices)
+        if len(self.classes) < self.P:
+            raise ValueError(f"PKBatchSampler: P = {self.P} exceeds the {len(self.classes)} classes of the labels")
+        if self.P < 1 or self.K < 1:
+            raise ValueError("PKBatchSampler: P and K must be positive")
+        self._reset_epoch()
+
+    def __len__(self) -> int:
+        return len(self.labels) // (self.P * self.K)
+
+    def _reset_epoch(self) -> None:
+        self.queues = {}
+        for c, idxs in self.class_to_indices.items():
+            q = np.array(idxs)
+            self.rng.shuffle(q)
+            self.queues[c] = q.tolist()
+        self.order = list(self.classes)
+        self.rng.shuffle(self.order)
+        self.cursor = 0
+
+    def _next_classes(self) -> List[int]:
+        end = self.cursor + self.P
+        if end <= len(self.order):
+            chosen = self.order[self.cursor:end]
+            self.cursor = end
+            return chosen
+        wrapped = end - len(self.order)
+        chosen = self.order[self.cursor:] + self.order[:wrapped]
+        self.rng.shuffle(self.order)
+        self.cursor = wrapped
+        return chosen
+
+    def __iter__(self):
+        self._reset_epoch()
+        for _ in range(max(1, len(self))):      # the reference yields before it counts: one batch even when N < P K
+            batch: List[int] = []
+            for c in self._next_classes():
+                q = self.queues[c]
+                take, q[:] = q[:self.K], q[self.K:]
+                if len(take) < self.K:
+                    take += self.rng.choice(self.class_to_indices[c], size=self.K - len(take), replace=True).tolist()
+                batch += take
+            self.rng.shuffle(batch)
+            yield batch
+
+
 # Keypoint directory layout.  "auto" is the reference's name sniffing (utils.py:410-417: a directory whose path
 # contains SAVE_GEN / SAVE_NEW / generated_kps is flat, <dir>/<stem>/keypoints.npy, any other is per class,
 # <dir>/<Class>/<stem>/keypoints.npy); "flat" and "per_class" state the layout explicitly, so a directory whose

@@ -62,7 +62,8 @@ EXPORTS = ["vge_featurize", "vge_featurize_layout", "vge_layout_feat_dim", "vge_
            "vge_webp_decode_device", "vge_webp_decode_device_workspace_bytes", "vge_webp_slot_bytes",
            "vge_apng_probe", "vge_apng_probe_mem", "vge_apng_decode", "vge_apng_decode_mem", "vge_apng_plan_mem",
            "vge_apng_decode_device", "vge_apng_decode_device_workspace_bytes",
-           "vge_time_gather", "vge_tcl_workspace_bytes", "vge_tcl_loss", "vge_hardneg_loss", "vge_centroid_distance"]
+           "vge_time_gather", "vge_tcl_workspace_bytes", "vge_tcl_loss", "vge_hardneg_loss", "vge_centroid_distance",
+           "vge_tcl_grad_workspace_bytes", "vge_tcl_loss_grad", "vge_hardneg_loss_grad"]
 
 
 class VgeError(RuntimeError):
@@ -324,6 +325,9 @@ def load() -> C.CDLL:
         "vge_tcl_loss": [vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, vp, C.c_size_t, vp, vp],
         "vge_hardneg_loss": [vp, vp, i32, i32, C.c_double, vp, vp],
         "vge_centroid_distance": [vp, vp, vp, i32, i32, i32, vp, vp],
+        "vge_tcl_grad_workspace_bytes": [i32],
+        "vge_tcl_loss_grad": [vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, vp, C.c_size_t, vp, vp, vp],
+        "vge_hardneg_loss_grad": [vp, vp, i32, i32, C.c_double, vp, vp, vp, vp],
     }
     for name, args in sig.items():
         f = getattr(lib, name)
@@ -331,6 +335,7 @@ def load() -> C.CDLL:
         f.restype = C.c_int
     lib.vge_stats_workspace_bytes.restype = C.c_size_t
     lib.vge_tcl_workspace_bytes.restype = C.c_size_t
+    lib.vge_tcl_grad_workspace_bytes.restype = C.c_size_t
     lib.vge_jpeg_entropy_workspace_bytes.restype = C.c_size_t
     lib.vge_jpeg_entropy_decode_workspace_bytes.restype = C.c_size_t
     lib.vge_ingest_decode_device_workspace_bytes.restype = C.c_size_t

@@ -356,6 +356,59 @@ def hardneg_loss(anchor: torch.Tensor, neg: torch.Tensor, temperature: float = 0
     return out
 
 
+def _f32_rows(fn: str, name: str, t: torch.Tensor, shape=None) -> None:
+    if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or \
+            (shape is not None and tuple(t.shape) != tuple(shape)):
+        want = "[B,d]" if shape is None else f"[{shape[0]},{shape[1]}]"
+        raise L.VgeError(f"{fn}: {name} must be a contiguous float32 {want} tensor, got {t.dtype} {tuple(t.shape)}")
+
+
+def tcl_loss_grad(emb: torch.Tensor, labels: torch.Tensor, temperature: float = 0.1, k1: float = 5000.0,
+                  k2: float = 1.0, out: Optional[torch.Tensor] = None, grad: Optional[torch.Tensor] = None):
+    """tcl_loss and its gradient in one call (vge_tcl_loss_grad) -> (device float64 [1], float32 [B,d]).  The loss has
+    tcl_loss's bits; where it is NaN (a label that appears once) the gradient is unspecified."""
+    lib = L.load()
+    _f32_rows("tcl_loss_grad", "emb", emb)
+    B, d = emb.shape
+    if labels.dtype != torch.int32 or labels.dim() != 1 or labels.numel() != B or labels.device != emb.device:
+        raise L.VgeError(f"tcl_loss_grad: labels must be int32 [{B}] on {emb.device}")
+    if out is None:
+        out = torch.empty((1,), device=emb.device, dtype=torch.float64)
+    if grad is None:
+        grad = torch.empty_like(emb)
+    else:
+        _f32_rows("tcl_loss_grad", "grad", grad, (B, d))
+    wsb = int(lib.vge_tcl_grad_workspace_bytes(B))
+    ws = torch.empty(max(wsb, 8) // 8, dtype=torch.float64, device=emb.device)
+    L.check(lib.vge_tcl_loss_grad(_ptr(emb), _ptr(labels), B, d, float(temperature), float(k1), float(k2), _ptr(ws),
+                                  wsb, _ptr(out), _ptr(grad), _stream(emb.device)), "vge_tcl_loss_grad")
+    return out, grad
+
+
+def hardneg_loss_grad(anchor: torch.Tensor, neg: torch.Tensor, temperature: float = 0.07,
+                      out: Optional[torch.Tensor] = None, grad_anchor: Optional[torch.Tensor] = None,
+                      grad_neg: Optional[torch.Tensor] = None):
+    """hardneg_loss and its gradients in one call (vge_hardneg_loss_grad) -> (device float64 [1], grad_anchor
+    float32 [B,d], grad_neg float32 [B,d]); anchor is the positive too, and grad_anchor covers both of its uses."""
+    lib = L.load()
+    _f32_rows("hardneg_loss_grad", "anchor", anchor)
+    B, d = anchor.shape
+    _f32_rows("hardneg_loss_grad", "neg", neg, (B, d))
+    if out is None:
+        out = torch.empty((1,), device=anchor.device, dtype=torch.float64)
+    if grad_anchor is None:
+        grad_anchor = torch.empty_like(anchor)
+    else:
+        _f32_rows("hardneg_loss_grad", "grad_anchor", grad_anchor, (B, d))
+    if grad_neg is None:
+        grad_neg = torch.empty_like(anchor)
+    else:
+        _f32_rows("hardneg_loss_grad", "grad_neg", grad_neg, (B, d))
+    L.check(lib.vge_hardneg_loss_grad(_ptr(anchor), _ptr(neg), B, d, float(temperature), _ptr(out), _ptr(grad_anchor),
+                                      _ptr(grad_neg), _stream(anchor.device)), "vge_hardneg_loss_grad")
+    return out, grad_anchor, grad_neg
+
+
 def centroid_distance(emb: torch.Tensor, labels: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
     """|| normalize(emb_i) - centroids[labels[i]] ||_2 (train.py:366-378) -> float32 [n]; NaN where the label is
     outside [0, C)."""

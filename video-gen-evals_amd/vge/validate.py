@@ -10,7 +10,10 @@
                           validate_checkpoint; train.py:450-455 keeps the checkpoint with the lowest loss
   python -m vge.validate  the command line
 
-Forward only: training itself (train.py's optimiser loop, PKBatchSampler) is not part of this library.  The batches
+  build_data_path         that data path by itself: vge.train builds its loop on it
+
+This module is the forward side: the optimiser loop that minimises this loss is vge.train, the gradients of the two
+losses are vge.losses (vge_tcl_loss_grad / vge_hardneg_loss_grad), the batch sampler is data.PKBatchSampler.  The batches
 run on one GPU; sharding them over ranks is out of scope (a batch's TCL couples all of its windows, so the unit of
 work is a whole batch -- a few per checkpoint).
 """
@@ -18,6 +21,7 @@ from __future__ import annotations
 
 import json
 import math
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -149,6 +153,44 @@ def validate_checkpoint(model: ops.Encoder, store: ops.DeviceFrameStore, windows
     return out
 
 
+# ----------------------------------------------------------------------------- the data path
+
+@dataclass
+class DataPath:
+    """BaseExperiment.__init__'s data path (train.py:117-128), built once: what rank_checkpoints and vge.train share."""
+    train_ds: object
+    test_ds: object
+    label_dict: Dict[str, int]
+    train_store: ops.DeviceFrameStore
+    stats: object
+    dims_raw: Dict[str, int]
+    dims_diff: Dict[str, int]
+    test_store: ops.DeviceFrameStore
+    windows: torch.Tensor           # the held-out split's windows, device int32 [N,2] (enumerate_test_windows order)
+    labels: torch.Tensor            # their labels, device int32 [N]
+
+
+def build_data_path(real_meshes_dir: str, real_kp_dir: Optional[str], clip_len: int = 32, stride: int = 8,
+                    device="cuda", ingest: str = "host") -> DataPath:
+    """NpzVideoDataset over the ten classes, train_test_split(0.8, 1337), stats from the train split, label_dict
+    from the sorted classes of the full set; both frame stores on the device."""
+    from . import eval as E
+    from .data import ACTION_CLASSES, NpzVideoDataset, enumerate_test_windows, train_test_split
+    real_ds = NpzVideoDataset(real_meshes_dir, filter_classes=ACTION_CLASSES)
+    train_ds, test_ds = train_test_split(real_ds, train_ratio=0.8, seed=1337)
+    label_dict = {cls: i for i, cls in enumerate(sorted({it.cls for it in real_ds.items}))}
+    train_store = E.device_frame_store(train_ds.items, real_kp_dir, False, device, ingest)
+    stats = E.compute_stats_from_npz(train_ds.items, real_kp_dir, device=device, store=train_store)
+    dims_raw, dims_diff = E.infer_dims_from_stats(stats)
+    test_store = E.device_frame_store(test_ds.items, real_kp_dir, real_kp_dir is not None, device, ingest)
+    samples = enumerate_test_windows(test_ds, clip_len, stride)
+    idx = {it.path: i for i, it in enumerate(test_ds.items)}
+    windows = E._window_tensor(samples, idx, device)
+    labels = torch.as_tensor([label_dict[it.cls] for it, _ in samples], dtype=torch.int32, device=device)
+    return DataPath(train_ds, test_ds, label_dict, train_store, stats, dims_raw, dims_diff, test_store, windows,
+                    labels)
+
+
 # ----------------------------------------------------------------------------- many checkpoints
 
 def rank_checkpoints(real_meshes_dir: str, real_kp_dir: Optional[str], checkpoints: Sequence, compute: str = "f32x3",
@@ -163,18 +205,10 @@ def rank_checkpoints(real_meshes_dir: str, real_kp_dir: Optional[str], checkpoin
     ranked last.  -> a list of {"checkpoint", "loss", ...validate_checkpoint's keys} sorted by loss.  One GPU; the
     batches are not sharded over ranks."""
     from . import eval as E
-    from .data import ACTION_CLASSES, NpzVideoDataset, enumerate_test_windows, train_test_split
-    real_ds = NpzVideoDataset(real_meshes_dir, filter_classes=ACTION_CLASSES)
-    train_ds, test_ds = train_test_split(real_ds, train_ratio=0.8, seed=1337)
-    label_dict = {cls: i for i, cls in enumerate(sorted({it.cls for it in real_ds.items}))}
-    train_store = E.device_frame_store(train_ds.items, real_kp_dir, False, device, ingest)
-    stats = E.compute_stats_from_npz(train_ds.items, real_kp_dir, device=device, store=train_store)
-    dims_raw, dims_diff = E.infer_dims_from_stats(stats)
-    test_store = E.device_frame_store(test_ds.items, real_kp_dir, real_kp_dir is not None, device, ingest)
-    samples = enumerate_test_windows(test_ds, clip_len, stride)
-    idx = {it.path: i for i, it in enumerate(test_ds.items)}
-    windows = E._window_tensor(samples, idx, device)
-    labels = torch.as_tensor([label_dict[it.cls] for it, _ in samples], dtype=torch.int32, device=device)
+    dp = build_data_path(real_meshes_dir, real_kp_dir, clip_len, stride, device, ingest)
+    train_ds, label_dict, train_store, stats = dp.train_ds, dp.label_dict, dp.train_store, dp.stats
+    dims_raw, dims_diff = dp.dims_raw, dp.dims_diff
+    test_store, windows, labels = dp.test_store, dp.windows, dp.labels
     results = []
     for ck in checkpoints:
         entry = {"checkpoint": str(ck) if not isinstance(ck, (dict, tuple)) else f"<state_dict {len(results)}>"}
