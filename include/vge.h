@@ -304,6 +304,51 @@ int vge_hardneg_loss_grad(const float* anchor, const float* neg, int B, int d, d
 int vge_centroid_distance(const float* emb, const int32_t* labels, const float* centroids, int n, int C, int d,
                           float* dist, vge_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * One residual block of MovementConvEncoder (the reference's TemporalConvBlock, model.py:21-58) for training:
+ * a forward that keeps what the backward needs, and the backward to every input and parameter.  Exact f32 on the
+ * f32-input MFMA; activations channels-last.
+ *
+ *   x [B,T,C];  w1, w2 [C,C,5] in torch's Conv1d layout [C_out, C_in, k];  dilation d in {1, 2, 4, 8}, zero padding
+ *   2 d;  mask [B,T,C] the dropout multiplier (entries 0 or 1 / (1 - p)), or NULL for all ones;  gamma, beta [C];
+ *   eps 1e-5.   conv(v; W)[b,t,o] = sum_j sum_i v[b, t + (j - 2) d, i] W[o,i,j], rows outside 0 .. T-1 read as zero.
+ *
+ *   forward    a = conv(x; w1)          h = gelu(a) mask        u = conv(h; w2) + x        g = gelu(u)
+ *              mean_b, rstd_b over the sample's (T, C), biased variance      g^ = (g - mean_b) rstd_b
+ *              y = g^ gamma + beta          gelu(z) = z Phi(z) (the erf form),  gelu'(z) = Phi(z) + z phi(z)
+ *   backward   dbeta[c] = sum_{b,t} dy      dgamma[c] = sum_{b,t} dy g^      q = dy gamma
+ *              dg = rstd_b (q - mean_{t,c}(q) - g^ mean_{t,c}(q g^))         du = dg gelu'(u)
+ *              dw2[o,i,j] = sum_{b,t} du[b,t,o] h[b, t + (j - 2) d, i]
+ *              dh[b,s,i]  = sum_j sum_o du[b, s - (j - 2) d, o] w2[o,i,j]    da = dh mask gelu'(a)
+ *              dw1[o,i,j] = sum_{b,t} da[b,t,o] x[b, t + (j - 2) d, i]
+ *              dx = du + sum_j sum_o da[b, s - (j - 2) d, o] w1[o,i,j]
+ *
+ * Saved tensors: the forward writes a, u [B,T,C] and mean, rstd [B]; the backward takes them back with x, mask, the
+ * weights and gamma (h is recomputed from a and mask).  Pass a, u, mean and rstd all NULL to a forward whose backward
+ * will not run: nothing is saved then.
+ * Shapes: C a multiple of 32 in [32, 256], 1 <= T <= 64, B >= 1 with B T C < 2^31, dilation in {1, 2, 4, 8}; anything
+ * else returns VGE_ERR_UNSUPPORTED.  Every pointer is device memory, 16-byte aligned (VGE_ERR_ARG otherwise, and for
+ * a NULL other than mask or the saved set); inputs may alias each other, an output or the workspace may overlap
+ * nothing else that is passed (VGE_ERR_ARG).  workspace: >= vge_convblock_workspace_bytes(B, T, C) bytes for the
+ * backward, which is enough for either call; the forward alone needs vge_convblock_forward_workspace_bytes(C), its two
+ * weight images (VGE_ERR_WORKSPACE otherwise; 0 is returned for an unsupported shape); its contents do not carry over from one
+ * call to the next -- the weights are repacked on the device in every call, because a training step changes them.
+ * All of these checks run before the first HIP call.  No allocation, no host synchronisation, everything on `stream`.
+ * Sums: a sample is owned by one workgroup, which forms its statistics; dgamma, dbeta, dw1 and dw2 are per-workgroup
+ * partials in the workspace added by a second pass in index order.  No floating-point atomics; the order of every
+ * sum is fixed by (B, T, C, dilation), so two calls on the same input give the same bits.  A NaN in one sample's x
+ * stays in that sample's y (and reaches the parameter gradients); other samples' y and dx do not see it.
+ */
+size_t vge_convblock_workspace_bytes(int B, int T, int C);
+size_t vge_convblock_forward_workspace_bytes(int C);
+int vge_convblock_forward(const float* x, const float* w1, const float* w2, const float* mask, const float* gamma,
+                          const float* beta, int B, int T, int C, int dilation, float* a, float* u, float* mean,
+                          float* rstd, float* y, void* workspace, size_t workspace_bytes, vge_stream_t stream);
+int vge_convblock_backward(const float* dy, const float* x, const float* w1, const float* w2, const float* mask,
+                           const float* gamma, const float* a, const float* u, const float* mean, const float* rstd,
+                           int B, int T, int C, int dilation, float* dx, float* dw1, float* dw2, float* dgamma,
+                           float* dbeta, void* workspace, size_t workspace_bytes, vge_stream_t stream);
+
 const char* vge_last_error(void);
 const char* vge_version(void);
 

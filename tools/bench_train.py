@@ -3,14 +3,22 @@
 config-2 synthetic set (256 synthetic 32-frame clips, one window each), d_model 256, dropout 0.1, after a warm-up.
 Prints one JSON object and nothing else.
 
-    python tools/bench_train.py
+    python tools/bench_train.py [--conv-backend hip]
 
 ms are medians over the timed repetitions.  Per repetition the pieces of one step are timed in order -- featurise,
 the three time gathers, the four module forwards, the loss forward + backward (to the gradients of the four
 embeddings), the module's backward, the optimiser step -- once with the HIP loss and once with the torch loss, in
 alternating order; "step" is vge.train.train_step as the loop calls it (its device-to-host copy of the four loss
 values included).  "loss_2048" is the loss pair alone (TCL + three hard-negative terms, forward + backward) at
-B = 2048 on unit embeddings of ten classes."""
+B = 2048 on unit embeddings of ten classes.
+
+--conv-backend hip adds a third column, "conv_hip": the same step with the movement encoders' residual blocks on the
+forward / backward kernels of vge_convblock.hip (a second module with the same initial weights and its own optimiser,
+HIP loss), alternated with the two existing columns in the same repetitions; and "convblock_240", one block alone
+(B = 240, T = 32, C = 256; events around 20 calls) with its FLOPs over the time against the 155 TFLOP/s the f32-input
+MFMA was measured at.  Without the flag the output is what it was."""
+import argparse
+import copy
 import json
 import statistics
 import sys
@@ -45,7 +53,41 @@ def loss_pair(tcl, hard, emb, negs, labels):
     return total, torch.autograd.grad(total, [emb] + list(negs))
 
 
+MFMA_F32_TFLOPS = 155.0      # v_mfma_f32_16x16x4_f32 / 32x32x2, measured back-to-back issue rate on an MI355X
+
+
+def convblock_alone(dev, B=240, Tn=32, Cn=256, calls=20):
+    """One block's forward and backward alone -> ms per call, TFLOP/s, and the share of the f32-MFMA ceiling."""
+    g = torch.Generator().manual_seed(11)
+    x, dy = (torch.randn(B, Tn, Cn, generator=g).to(dev) for _ in range(2))
+    w1, w2 = (torch.randn(Cn, Cn, 5, generator=g).div_((5 * Cn) ** 0.5).to(dev) for _ in range(2))
+    gamma, beta = torch.ones(Cn, device=dev), torch.zeros(Cn, device=dev)
+    mask = torch.nn.functional.dropout(torch.ones_like(x), 0.1, True)
+    conv_flop = 2.0 * B * Tn * 5 * Cn * Cn           # one dilated k = 5 convolution, or one weight gradient
+    out = {}
+    for dil in (1, 8):
+        _, saved = ops.convblock_forward(x, w1, w2, gamma, beta, dil, mask)
+        fwd, bwd = [], []
+        for rep in range(WARMUP + REPS):
+            e, _ = timed(lambda: [ops.convblock_forward(x, w1, w2, gamma, beta, dil, mask) for _ in range(calls)])
+            f, _ = timed(lambda: [ops.convblock_backward(dy, x, w1, w2, gamma, dil, saved, mask) for _ in range(calls)])
+            torch.cuda.synchronize(dev)
+            if rep >= WARMUP:
+                fwd.append(e[0].elapsed_time(e[1]) / calls)
+                bwd.append(f[0].elapsed_time(f[1]) / calls)
+        for name, ms, flop in (("forward", statistics.median(fwd), 2 * conv_flop),
+                               ("backward", statistics.median(bwd), 4 * conv_flop)):
+            tf = flop / (ms * 1e-3) / 1e12
+            out[f"{name}_dil{dil}"] = {"ms": round(ms, 4), "gflop": round(flop / 1e9, 3), "tflops": round(tf, 2),
+                                       "share_of_f32_mfma_ceiling": round(tf / MFMA_F32_TFLOPS, 4)}
+    return out
+
+
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--conv-backend", default="torch", choices=["torch", "hip"],
+                    help="hip: add the conv_hip column (residual blocks on vge_convblock.hip) and convblock_240")
+    conv_backend = ap.parse_args().conv_backend
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     clips, names = [], []
@@ -66,14 +108,22 @@ def main():
     model = HumanActionScorer(dims_raw, dims_diff, dropout=0.1).to(dev).train()
     opt, sched = T.make_optimizer(model, 3e-4, 100, 30)
     losses = {b: (TCL(backend=b), SupConWithHardNegatives(backend=b)) for b in BACKENDS}
+    # column -> (module, optimiser, scheduler, loss backend); the two existing columns share one module
+    columns = {b: (model, opt, sched, b) for b in BACKENDS}
+    if conv_backend == "hip":
+        model_h = HumanActionScorer(dims_raw, dims_diff, dropout=0.1, conv_backend="hip").to(dev).train()
+        model_h.load_state_dict(copy.deepcopy(model.state_dict()))
+        columns["conv_hip"] = (model_h, *T.make_optimizer(model_h, 3e-4, 100, 30), "hip")
+    order = tuple(columns)
     gen = torch.Generator().manual_seed(1337)
     tables = [V.partial_shuffle_indices(B, 32, generator=gen).to(dev), V.reverse_indices(B).to(dev),
               V.static_indices(B).to(dev)]
-    times = {b: {k: [] for k in PIECES} for b in BACKENDS}
+    times = {b: {k: [] for k in PIECES} for b in order}
     values = {}
     for rep in range(WARMUP + REPS):
-        for backend in (BACKENDS if rep % 2 == 0 else BACKENDS[::-1]):
-            tcl, hard = losses[backend]
+        for backend in (order if rep % 2 == 0 else order[::-1]):
+            model, opt, sched, loss_backend = columns[backend]
+            tcl, hard = losses[loss_backend]
             ev = {}
             ev["featurize"], feats = timed(lambda: ops.featurize(store, win, mean, std))
             ev["gathers"], variants = timed(lambda: [ops.time_gather(feats, t) for t in tables])
@@ -94,12 +144,16 @@ def main():
             times[backend]["pieces_total"].append(ev["featurize"][0].elapsed_time(ev["optimizer"][1]))
     out = {"windows": B, "d_model": 256, "dropout": 0.1, "reps": REPS,
            "parameters": int(sum(p.numel() for p in model.parameters()))}
-    for backend in BACKENDS:
+    for backend in order:
         ms = {k: statistics.median(v) for k, v in times[backend].items()}
         out[backend] = {k + "_ms": round(v, 4) for k, v in ms.items()}
         out[backend]["loss_share_of_pieces"] = round(ms["loss_fwd_bwd"] / ms["pieces_total"], 5)
         out[backend]["last_loss"] = values[backend]
     out["loss_hip_over_torch_240"] = round(out["hip"]["loss_fwd_bwd_ms"] / out["torch"]["loss_fwd_bwd_ms"], 4)
+    if conv_backend == "hip":
+        for k in ("forwards", "module_backward", "step"):
+            out[f"conv_hip_over_torch_{k}"] = round(out["conv_hip"][k + "_ms"] / out["hip"][k + "_ms"], 4)
+        out["convblock_240"] = convblock_alone(dev)
 
     # the loss pair alone at B = 2048
     Bl = 2048

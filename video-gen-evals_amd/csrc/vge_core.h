@@ -1,6 +1,7 @@
 // The scoring core's interface between the C ABI (vge_api.cpp) and its kernels: every kernel-argument struct, defined
 // once for host and device, and every launcher of vge_featurize.hip, vge_encoder.hip, vge_encoder_x3.hip,
-// vge_encoder_x3s.hip, vge_encoder_gen.hip, vge_transformer_x3.hip and vge_score.hip.  Host-safe: no device helpers.
+// vge_encoder_x3s.hip, vge_encoder_gen.hip, vge_transformer_x3.hip, vge_convblock.hip and vge_score.hip.  Host-safe: no
+// device helpers.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -183,6 +184,38 @@ hipError_t launch_gen_attn(const float* qkv, int n_windows, int d, int heads, fl
 hipError_t launch_gen_add_ln(const float* a, const float* b, int rows, int d, const float* g, const float* be, float* out,
                              hipStream_t s);
 hipError_t launch_gen_embed_tc(const float* x, int n_windows, int d, float* seq, float* frame, float* tc, hipStream_t s);
+
+// ------------------------------------------------------------------ vge_convblock.hip (training: one conv block)
+// x, m (null: all ones), a, u, y and the gradients: [B][T][C]; P1 / P2: weight images of launch_convblock_pack
+struct ConvBlockFwdArgs {
+  const float* x; const float* m; const float* P1; const float* P2; const float* gamma; const float* beta;
+  float* a; float* u; float* mu; float* rstd;  // the saved set: all four or all null
+  float* y;
+  int B, T, C, dil;
+};
+
+struct ConvBlockBwdArgs {
+  const float* x; const float* m; const float* a; const float* u; const float* mu; const float* rstd;
+  const float* gamma; const float* dy;
+  const float* P1b; const float* P2b;  // flipped images of W1, W2
+  float* du; float* da; float* h;      // [B][T][C] scratch the weight gradient reads
+  float* dx;
+  double* gb_part;                     // [B][2][C] per-sample sums of dy g^ (dgamma) and dy (dbeta)
+  int B, T, C, dil;
+};
+
+struct ConvBlockWgradArgs {
+  const float* x; const float* h; const float* da; const float* du;
+  float* part;                         // [chunks][2][5][C][C]
+  int B, T, C, dil, per_chunk;         // per_chunk: set by the launcher
+};
+
+int convblock_chunks(int B, int* per_chunk);  // sample chunks of the weight gradient, and samples per chunk
+hipError_t launch_convblock_pack(const float* W, int C, int flip, float* P, hipStream_t s);
+hipError_t launch_convblock_forward(const ConvBlockFwdArgs& a, hipStream_t s);
+hipError_t launch_convblock_backward(const ConvBlockBwdArgs& a, hipStream_t s);
+hipError_t launch_convblock_wgrad(const ConvBlockWgradArgs& a, float* dw1, float* dw2, hipStream_t s);
+hipError_t launch_convblock_gbreduce(const double* gb_part, int B, int C, float* dgamma, float* dbeta, hipStream_t s);
 
 // ------------------------------------------------------------------ vge_score.hip
 // d <= 256

@@ -63,7 +63,8 @@ EXPORTS = ["vge_featurize", "vge_featurize_layout", "vge_layout_feat_dim", "vge_
            "vge_apng_probe", "vge_apng_probe_mem", "vge_apng_decode", "vge_apng_decode_mem", "vge_apng_plan_mem",
            "vge_apng_decode_device", "vge_apng_decode_device_workspace_bytes",
            "vge_time_gather", "vge_tcl_workspace_bytes", "vge_tcl_loss", "vge_hardneg_loss", "vge_centroid_distance",
-           "vge_tcl_grad_workspace_bytes", "vge_tcl_loss_grad", "vge_hardneg_loss_grad"]
+           "vge_tcl_grad_workspace_bytes", "vge_tcl_loss_grad", "vge_hardneg_loss_grad",
+           "vge_convblock_workspace_bytes", "vge_convblock_forward_workspace_bytes", "vge_convblock_forward", "vge_convblock_backward"]
 
 
 class VgeError(RuntimeError):
@@ -328,6 +329,10 @@ def load() -> C.CDLL:
         "vge_tcl_grad_workspace_bytes": [i32],
         "vge_tcl_loss_grad": [vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, vp, C.c_size_t, vp, vp, vp],
         "vge_hardneg_loss_grad": [vp, vp, i32, i32, C.c_double, vp, vp, vp, vp],
+        "vge_convblock_workspace_bytes": [i32, i32, i32],
+        "vge_convblock_forward_workspace_bytes": [i32],
+        "vge_convblock_forward": [vp] * 6 + [i32] * 4 + [vp] * 6 + [C.c_size_t, vp],
+        "vge_convblock_backward": [vp] * 10 + [i32] * 4 + [vp] * 6 + [C.c_size_t, vp],
     }
     for name, args in sig.items():
         f = getattr(lib, name)
@@ -336,6 +341,8 @@ def load() -> C.CDLL:
     lib.vge_stats_workspace_bytes.restype = C.c_size_t
     lib.vge_tcl_workspace_bytes.restype = C.c_size_t
     lib.vge_tcl_grad_workspace_bytes.restype = C.c_size_t
+    lib.vge_convblock_workspace_bytes.restype = C.c_size_t
+    lib.vge_convblock_forward_workspace_bytes.restype = C.c_size_t
     lib.vge_jpeg_entropy_workspace_bytes.restype = C.c_size_t
     lib.vge_jpeg_entropy_decode_workspace_bytes.restype = C.c_size_t
     lib.vge_ingest_decode_device_workspace_bytes.restype = C.c_size_t

@@ -19,7 +19,11 @@ temporal stack's attention takes scaled_dot_product_attention's "math" route (tw
 fused attention kernels: those are the least exact float32 step of the backward.
 
 This module's forward and backward run on torch's kernels (rocBLAS / hipBLASLt and native ones); the hand-written
-encoder kernels keep no activations and have no backward.  The new HIP of a training step is the loss (vge.losses).
+encoder kernels keep no activations and have no backward.  The HIP of a training step is the loss (vge.losses) and,
+with conv_backend="hip", the residual blocks of the movement encoders: each block is then one autograd node
+(vge.convblock.ConvBlockFunction) on the forward and backward kernels of vge_convblock.hip, with the same parameters
+under the same state-dict keys.  The default conv_backend="torch" is the graph described above, unchanged.  The stem,
+the projection, the fusion and the temporal stack run on torch under either backend.
 """
 from __future__ import annotations
 
@@ -31,8 +35,17 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.nn.attention import SDPBackend, sdpa_kernel
 
+from .convblock import convblock
+
 KERNEL_SIZE = 5
 DILATIONS = (1, 2, 4, 8)
+CONV_BACKENDS = ("torch", "hip")
+
+
+def _check_conv_backend(conv_backend: str) -> str:
+    if conv_backend not in CONV_BACKENDS:
+        raise ValueError(f"conv_backend must be one of {CONV_BACKENDS}, got {conv_backend!r}")
+    return conv_backend
 
 
 def _uniform_fan_in(shape, fan_in: int) -> nn.Parameter:
@@ -74,14 +87,20 @@ class _ChannelAffine(nn.Module):
 
 
 class _Block(nn.Module):
-    def __init__(self, channels: int, dilation: int, p: float):
+    def __init__(self, channels: int, dilation: int, p: float, conv_backend: str = "torch"):
         super().__init__()
+        self.conv_backend = _check_conv_backend(conv_backend)
         self.conv1 = _ConvWeight(channels, channels, KERNEL_SIZE, dilation)
         self.conv2 = _ConvWeight(channels, channels, KERNEL_SIZE, dilation)
         self.norm = _ChannelAffine(channels)
         self.drop = nn.Dropout(p)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.conv_backend == "hip":
+            # the multiplier self.drop would apply, drawn where the torch backend draws it (after conv1)
+            mask = F.dropout(torch.ones_like(x), self.drop.p, True) if self.training and self.drop.p > 0 else None
+            return convblock(x, self.conv1.weight, self.conv2.weight, self.norm.weight, self.norm.bias,
+                             self.conv1.dilation, mask)
         y = self.conv2(self.drop(F.gelu(self.conv1(x))))
         return self.norm(F.gelu(y + x))
 
@@ -98,10 +117,10 @@ class _Linear(nn.Module):
 
 
 class _MovementEncoder(nn.Module):
-    def __init__(self, d_in: int, d_out: int, p: float):
+    def __init__(self, d_in: int, d_out: int, p: float, conv_backend: str = "torch"):
         super().__init__()
         self.stem = _ConvWeight(d_in, d_out, 1)
-        self.blocks = nn.ModuleList([_Block(d_out, dil, p) for dil in DILATIONS])
+        self.blocks = nn.ModuleList([_Block(d_out, dil, p, conv_backend) for dil in DILATIONS])
         self.proj = _Linear(d_out, d_out)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -148,8 +167,10 @@ class _Positions(nn.Module):
 
 class HumanActionScorer(nn.Module):
     def __init__(self, dims_map_raw: Dict[str, int], dims_map_diff: Dict[str, int], d_model: int = 256,
-                 latent_dim: int = 128, time_layers: int = 4, time_heads: int = 8, dropout: float = 0.1):
+                 latent_dim: int = 128, time_layers: int = 4, time_heads: int = 8, dropout: float = 0.1,
+                 conv_backend: str = "torch"):
         super().__init__()
+        self.conv_backend = _check_conv_backend(conv_backend)
         if not isinstance(dims_map_raw, dict) or not isinstance(dims_map_diff, dict):
             raise ValueError("dims_map_raw and dims_map_diff must be dicts of {modality: dim}")
         if set(dims_map_raw) != set(dims_map_diff):
@@ -160,10 +181,10 @@ class HumanActionScorer(nn.Module):
         self.hyper_parameters = {"d_model": int(d_model), "latent_dim": int(latent_dim),
                                  "time_layers": int(time_layers), "time_heads": int(time_heads),
                                  "dropout": float(dropout)}
-        self.state_enc = nn.ModuleDict({m: _MovementEncoder(self.dims_raw[m], d_model, dropout)
+        self.state_enc = nn.ModuleDict({m: _MovementEncoder(self.dims_raw[m], d_model, dropout, conv_backend)
                                         for m in self.modalities})
         with_diff = [m for m in self.modalities if self.dims_diff[m] > 0]
-        self.motion_enc = nn.ModuleDict({m: _MovementEncoder(self.dims_diff[m], d_model, dropout)
+        self.motion_enc = nn.ModuleDict({m: _MovementEncoder(self.dims_diff[m], d_model, dropout, conv_backend)
                                          for m in with_diff}) if with_diff else None
         self.fusion = _Fusion(d_model, len(self.modalities), dropout)
         self.cls = nn.Parameter(torch.randn(1, 1, d_model))

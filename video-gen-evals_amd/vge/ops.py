@@ -422,3 +422,79 @@ def centroid_distance(emb: torch.Tensor, labels: torch.Tensor, centroids: torch.
     L.check(lib.vge_centroid_distance(_ptr(emb), _ptr(labels), _ptr(centroids), n, C_, d, _ptr(out),
                                       _stream(emb.device)), "vge_centroid_distance")
     return out
+
+
+def _convblock_args(fn: str, x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, mask: Optional[torch.Tensor],
+                    gamma: torch.Tensor, like: Sequence[Tuple[str, torch.Tensor]] = ()) -> Tuple[int, int, int]:
+    if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise L.VgeError(f"{fn}: x must be a contiguous float32 [B,T,C] tensor, got {x.dtype} {tuple(x.shape)}")
+    B, T, C_ = x.shape
+    for name, t, shape in [("w1", w1, (C_, C_, 5)), ("w2", w2, (C_, C_, 5)), ("gamma", gamma, (C_,))] + \
+            [(n, t, (B, T, C_)) for n, t in (("mask", mask),) + tuple(like) if t is not None]:
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != x.device:
+            raise L.VgeError(f"{fn}: {name} must be a contiguous float32 {list(shape)} tensor on {x.device}, got "
+                             f"{t.dtype} {tuple(t.shape)}")
+    return B, T, C_
+
+
+def _convblock_vector(fn: str, name: str, t: torch.Tensor, n: int, device) -> None:
+    if t.dtype != torch.float32 or tuple(t.shape) != (n,) or not t.is_contiguous() or t.device != device:
+        raise L.VgeError(f"{fn}: {name} must be a contiguous float32 [{n}] tensor on {device}, got {t.dtype} "
+                         f"{tuple(t.shape)} on {t.device}")
+
+
+def _convblock_workspace(lib, B: int, T: int, C_: int, device) -> Tuple[torch.Tensor, int]:
+    wsb = int(lib.vge_convblock_workspace_bytes(B, T, C_))
+    return torch.empty(max(wsb, 16) // 4, dtype=torch.float32, device=device), wsb
+
+
+def convblock_forward(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+                      dilation: int, mask: Optional[torch.Tensor] = None, save: bool = True,
+                      y: Optional[torch.Tensor] = None, saved=None):
+    """One residual conv block (vge_convblock_forward, include/vge.h) on the current stream -> (y, saved), saved =
+    (a, u, mean, rstd) for convblock_backward, or None with save=False (nothing is kept).  x [B,T,C] float32; w1, w2
+    [C,C,5]; mask [B,T,C] the dropout multiplier or None; y / saved: the tensors to write, or None."""
+    lib = L.load()
+    a, u, mean, rstd = saved if saved is not None else (None, None, None, None)
+    B, T, C_ = _convblock_args("convblock_forward", x, w1, w2, mask, gamma, (("y", y), ("a", a), ("u", u)))
+    _convblock_vector("convblock_forward", "beta", beta, C_, x.device)
+    if y is None:
+        y = torch.empty_like(x)
+    if save and saved is None:
+        saved = (torch.empty_like(x), torch.empty_like(x), torch.empty(B, dtype=torch.float32, device=x.device),
+                 torch.empty(B, dtype=torch.float32, device=x.device))
+    a, u, mean, rstd = saved if save else (None, None, None, None)
+    if save:
+        _convblock_vector("convblock_forward", "mean", mean, B, x.device)
+        _convblock_vector("convblock_forward", "rstd", rstd, B, x.device)
+    wsb = int(lib.vge_convblock_forward_workspace_bytes(C_))      # the two weight images
+    ws = torch.empty(max(wsb, 16) // 4, dtype=torch.float32, device=x.device)
+    L.check(lib.vge_convblock_forward(_ptr(x), _ptr(w1), _ptr(w2), _ptr(mask), _ptr(gamma), _ptr(beta), B, T, C_,
+                                      int(dilation), _ptr(a), _ptr(u), _ptr(mean), _ptr(rstd), _ptr(y), _ptr(ws), wsb,
+                                      _stream(x.device)), "vge_convblock_forward")
+    return y, (saved if save else None)
+
+
+def convblock_backward(dy: torch.Tensor, x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, gamma: torch.Tensor,
+                       dilation: int, saved, mask: Optional[torch.Tensor] = None, out=None):
+    """The block's backward (vge_convblock_backward) on the current stream -> (dx, dw1, dw2, dgamma, dbeta).  saved:
+    convblock_forward's (a, u, mean, rstd) of the same x, weights and mask; out: the five result tensors, or None."""
+    lib = L.load()
+    a, u, mean, rstd = saved
+    B, T, C_ = _convblock_args("convblock_backward", x, w1, w2, mask, gamma, (("dy", dy), ("a", a), ("u", u)))
+    _convblock_vector("convblock_backward", "mean", mean, B, x.device)
+    _convblock_vector("convblock_backward", "rstd", rstd, B, x.device)
+    if out is None:
+        out = (torch.empty_like(x), torch.empty_like(w1), torch.empty_like(w2), torch.empty_like(gamma),
+               torch.empty_like(gamma))
+    dx, dw1, dw2, dgamma, dbeta = out
+    _convblock_args("convblock_backward", dx, dw1, dw2, None, dgamma)
+    if dx.shape != x.shape or dx.device != x.device:
+        raise L.VgeError(f"convblock_backward: dx must be a float32 {list(x.shape)} tensor on {x.device}")
+    _convblock_vector("convblock_backward", "dbeta", dbeta, C_, x.device)
+    ws, wsb = _convblock_workspace(lib, B, T, C_, x.device)
+    L.check(lib.vge_convblock_backward(_ptr(dy), _ptr(x), _ptr(w1), _ptr(w2), _ptr(mask), _ptr(gamma), _ptr(a), _ptr(u),
+                                       _ptr(mean), _ptr(rstd), B, T, C_, int(dilation), _ptr(dx), _ptr(dw1), _ptr(dw2),
+                                       _ptr(dgamma), _ptr(dbeta), _ptr(ws), wsb, _stream(x.device)),
+            "vge_convblock_backward")
+    return dx, dw1, dw2, dgamma, dbeta
