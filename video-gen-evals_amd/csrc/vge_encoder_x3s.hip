@@ -130,60 +130,88 @@ constexpr int X3S_LDS_BYTES = X3S_PRE_OFF + 8 * X3S_PRE_WAVE;
 static_assert(X3S_AUX_OFF % 16 == 0, "aux alignment");
 static_assert(X3S_LDS_BYTES <= 160 * 1024, "LDS");
 
+typedef const __attribute__((address_space(3))) char* lchar;  // LDS (not generic) pointers: ds_read, never FLAT
+typedef const __attribute__((address_space(3))) half8* lhalf8;
+
+// chunks in flight per wave in a conv / proj stream: a pair's chunk is only 6 MFMAs (192 cycles) -- 3 chunks ahead would
+// not cover the weight stream's L2 latency while one wave per SIMD streams -- and it has the registers for 7
+template <int W, bool SP>
+constexpr int x3s_pf() {
+  return SP ? (W >= 4 ? X3S_PF_QUAD : X3S_PF_PAIR) : (W >= 4 ? X3S_PF16_QUAD : X3S_PF16_PAIR);
+}
+
+// weights through a buffer resource: the chunk offset in an SGPR, the lane's offset (+ the lo plane) in VGPRs
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t x3s_wrsrc(const char* wb) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(wb), (short)0, 0x7FFFFFF0, 0x00020000);
+}
+template <bool SP>
+__device__ __forceinline__ void x3s_ldb(__amdgpu_buffer_rsrc_t rs, unsigned loff, int chunk, BFrag<1>& b) {
+  const int so = chunk * CHUNK_B;
+  b.h[0] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rs, loff, so, 0));
+  if constexpr (SP) b.l[0] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rs, loff + PLANE_B, so, 0));
+}
+
+// The first PF - 1 chunks of a part (tap 0, in the workgroup's rotated order) into the slots stream_part reads them
+// from.  Weights do not depend on activations, so a half issues this before the barrier that precedes the part --
+// after its epilogue's last store, when the epilogue's temporaries are dead -- and the L2 round trip runs beside the
+// barrier wait instead of in front of the part's first MFMA.
+template <int W, bool SP, int PF>
+__device__ __forceinline__ void prime_part(BFrag<1> (&b)[PF], const char* wb, unsigned loff, int rot) {
+  static_assert(PF == x3s_pf<W, SP>(), "the caller's ring has this unit's depth");
+  const __amdgpu_buffer_rsrc_t rs = x3s_wrsrc(wb);
+#pragma unroll
+  for (int j = 0; j < PF - 1; ++j) x3s_ldb<SP>(rs, loff, (j + rot) & 7, b[j]);
+}
+
 // One part of a conv / proj GEMM without barriers: ntap taps x 8 chunks (input-channel blocks cb0..cb0+7 of each
-// tap).  B fragments 3 chunks ahead in a register ring; A fragments single-buffered per row tile (tile t's fragments
-// of the next chunk are read right after the three MFMAs of this chunk that use them: their latency hides behind the
-// other tiles' MFMAs).  Addresses are formed once per tap -- LDS row bases (the zero row for taps outside the window)
-// plus immediate chunk offsets, uniform weight pointers plus the lane's offset -- so the stream issues almost no VALU
-// work besides its MFMAs (its partner wave's epilogue shares the SIMD's issue slots).
-template <int W, bool SKIP, bool SP>
-__device__ __forceinline__ void stream_part(Acc<W, 1>& acc, const char* wb, int ntap, unsigned loff, const char* xa,
-                                            int i, int dil, int ctr, int rot) {
+// tap).  B fragments PF - 1 chunks ahead in a register ring that the caller owns and has primed (prime_part, or the
+// part before this one: CARRY); A fragments single-buffered per row tile (tile t's fragments of the next chunk are read
+// right after the three MFMAs of this chunk that use them: their latency hides behind the other tiles' MFMAs).
+// Addresses are formed once per tap -- LDS row bases (the zero row for taps outside the window) plus immediate chunk
+// offsets, uniform weight pointers plus the lane's offset -- so the stream issues almost no VALU work besides its
+// MFMAs (its partner wave's epilogue shares the SIMD's issue slots).
+// CARRY: this is part 0 of its GEMM, and part 1 follows it 8 chunks on in the same image.  The ring's last PF - 1
+// refills then load part 1's first chunks, into the slots part 1 reads them from (8 % PF == 0), so part 1 starts with
+// its ring full and needs no prime_part.  Otherwise they re-read the part's own last chunk (data never used).
+template <int W, bool SKIP, bool SP, bool CARRY, int PF>
+__device__ __forceinline__ void stream_part(Acc<W, 1>& acc, BFrag<1> (&b)[PF], const char* wb, int ntap,
+                                            unsigned loff, const char* xa, int i, int dil, int ctr, int rot) {
   constexpr int R = W, G = x3s_g<W>();
-  // chunks in flight: a pair's chunk is only 6 MFMAs (192 cycles) -- 3 chunks ahead would not cover the weight
-  // stream's L2 latency while one wave per SIMD streams -- and it has the registers for 7
-  constexpr int PF = SP ? (R >= 4 ? X3S_PF_QUAD : X3S_PF_PAIR) : (R >= 4 ? X3S_PF16_QUAD : X3S_PF16_PAIR);
+  static_assert(PF == x3s_pf<W, SP>(), "the caller's ring has this unit's depth");
   // the ring's slots restart at every tap (chunk j of a tap sits in slot j % PF, and the last steps of a tap load the
   // next tap's first chunks into the slots they will be read from): a depth that does not divide a tap's 8 chunks
   // reads the wrong chunk (measured: depths 3 / 6 / 12 gave wrong scores)
   static_assert(8 % PF == 0, "ring depth must divide a tap's 8 chunks");
-  const char* xw = xa + (i / G) * x3s_wsb<W>();  // this lane's MFMA row: its window's block ...
+  // the activation rows as LDS pointers by type: a generic row pointer that reaches the reads through a merge the
+  // compiler cannot see through becomes a FLAT access (tests/test_isa_guard.py)
+  const lchar xl = (lchar)xa;
+  const lchar xw = xl + (i / G) * x3s_wsb<W>();  // this lane's MFMA row: its window's block ...
   const int fi = i % G;                          // ... and its frame within the tile's group
-  const char* xz = xa + x3s_zr<W>();
-  auto rowp = [&](int k, int t) -> const char* {
+  const lchar xz = xl + x3s_zr<W>();
+  auto rowp = [&](int k, int t) -> lchar {
     const int tt = G * t + fi + (k - ctr) * dil;
     return (unsigned)tt < 32u ? xw + tt * XRB : xz;
   };
-  // weights through a buffer resource: the chunk offset in an SGPR, the lane's offset (+ the lo plane) in VGPRs
-  const __amdgpu_buffer_rsrc_t rs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(wb), (short)0, 0x7FFFFFF0, 0x00020000);
-  const unsigned loff_l = loff + PLANE_B;
+  const __amdgpu_buffer_rsrc_t rs = x3s_wrsrc(wb);
   // rot: this workgroup's chunk order inside a tap (logical chunk j is input-channel block (j + rot) & 7): the CUs of
   // an XCD stream the same encoder's weights together, and rotated they do not all read one chunk's lines at once
-  auto ldb = [&](int k, int j, BFrag<1>& b) {  // chunk j (0..7) of tap k
-    const int so = (k * 16 + ((j + rot) & 7)) * CHUNK_B;
-    b.h[0] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rs, loff, so, 0));
-    if constexpr (SP) b.l[0] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rs, loff_l, so, 0));
-  };
-  BFrag<1> b[PF];
-#pragma unroll
-  for (int j = 0; j < PF - 1; ++j) ldb(0, j, b[j]);
+  auto ldb = [&](int k, int j, BFrag<1>& f) { x3s_ldb<SP>(rs, loff, k * 16 + ((j + rot) & 7), f); };  // chunk j of tap k
   half8 ah[R], al[R];
-  const char* pt[R];
+  lchar pt[R];
   bool okc[R];  // tile t takes part in the current tap (uniform)
 #pragma unroll
   for (int t = 0; t < R; ++t) {
     pt[t] = rowp(0, t);
     okc[t] = x3s_tap_ok<W, SKIP>(t, -ctr * dil);
     if (okc[t]) {
-      ah[t] = *reinterpret_cast<const half8*>(pt[t] + rot * 32);
-      if constexpr (SP) al[t] = *reinterpret_cast<const half8*>(pt[t] + rot * 32 + XLO);
+      ah[t] = *reinterpret_cast<lhalf8>(pt[t] + rot * 32);
+      if constexpr (SP) al[t] = *reinterpret_cast<lhalf8>(pt[t] + rot * 32 + XLO);
     }
   }
   for (int k = 0; k < ntap; ++k) {
     const bool more = k + 1 < ntap;
     const int kn = more ? k + 1 : k;
-    const char* pn[R];
+    lchar pn[R];
     bool okn[R];
 #pragma unroll
     for (int t = 0; t < R; ++t) {
@@ -194,7 +222,10 @@ __device__ __forceinline__ void stream_part(Acc<W, 1>& acc, const char* wb, int 
     for (int j = 0; j < 8; ++j) {
 #if !(VGE_ABL & 2)
       if (j + PF - 1 < 8) ldb(k, j + PF - 1, b[(j + PF - 1) % PF]);
-      else ldb(kn, more ? j + PF - 1 - 8 : 7, b[(j + PF - 1) % PF]);  // (past the end: reload the last chunk)
+      else {  // the next tap's first chunks; past the end, part 1's (its tap 0) or a reload of the last chunk
+        const int jn = (j + PF - 1 - 8 + rot) & 7;
+        x3s_ldb<SP>(rs, loff, more ? (k + 1) * 16 + jn : CARRY ? 8 + jn : k * 16 + ((7 + rot) & 7), b[(j + PF - 1) % PF]);
+      }
 #endif
 #pragma unroll
       for (int t = 0; t < R; ++t) {
@@ -209,9 +240,9 @@ __device__ __forceinline__ void stream_part(Acc<W, 1>& acc, const char* wb, int 
 #endif
 #if !(VGE_ABL & 4)
         if (j < 7 ? okc[t] : okn[t]) {
-          const char* q = j < 7 ? pt[t] + ((j + 1 + rot) & 7) * 32 : pn[t] + rot * 32;
-          ah[t] = *reinterpret_cast<const half8*>(q);
-          if constexpr (SP) al[t] = *reinterpret_cast<const half8*>(q + XLO);
+          const lchar q = j < 7 ? pt[t] + ((j + 1 + rot) & 7) * 32 : pn[t] + rot * 32;
+          ah[t] = *reinterpret_cast<lhalf8>(q);
+          if constexpr (SP) al[t] = *reinterpret_cast<lhalf8>(q + XLO);
         }
 #endif
         __builtin_amdgcn_sched_barrier(0);  // tile by tile: the next fragments reuse this tile's registers
@@ -462,22 +493,29 @@ __device__ __forceinline__ void conv_x3s_body(const float* __restrict__ feats, i
   char* pre_lds = lds_raw + X3S_PRE_OFF + wave * X3S_PRE_WAVE;  // this wave's fold operands (X3S_PRE_WAVE)
   auto prefetch = [&](auto kind_tag, int gi) {
     constexpr int KIND = decltype(kind_tag)::value;
-    const int blk = gi >> 1;
     pre_wcs = gload(ed.cs + (1 + gi) * 256 + col);
     if constexpr (KIND == 2) {
       pre_sx = gload(ed.fold + 3 * 256 * 16 + col * 2);
       pre_sy = gload(ed.fold + 3 * 256 * 16 + col * 2 + 1);
-    } else if constexpr (KIND == 0) {
-      if (blk > 0) {  // LDS-DMA: the wave's 32 columns x 16 floats (2 KB, contiguous), then gamma | beta
-        const float* fb = ed.fold + ((size_t)(blk - 1) * 256 + wave * 32) * 16;
-        glds16(fb + lane * 4, pre_lds);
-        glds16(fb + 256 + lane * 4, pre_lds + 1024);
-        const float* gsrc = (h ? ed.gn_b : ed.gn_w) + (blk - 1) * 256 + col;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                         (__attribute__((address_space(3))) void*)(pre_lds + 2048), 4, 0, 0);
-        asm volatile("" ::: "memory");
-      }
     }
+  };
+  // The fold operands of block blk's conv1 epilogue (blk >= 1) by LDS-DMA: the wave's 32 columns x 16 floats (2 KB,
+  // contiguous), then gamma | beta.  Issued at the end of the epilogue before that conv (ahead of the ring's priming
+  // loads and of the barrier), not between its two parts: the compiler puts vmcnt(0) in front of the first LDS read
+  // after an LDS-DMA (there part 1's accumulator rescale), which exposed the DMA's round trip in front of part 1 and
+  // would now drain the ring part 0 has filled for it.  pre_lds is this wave's alone, and its last reader (the conv1
+  // epilogue of the block before) is long past.
+  auto prefetch_fold = [&](int blk) {
+    const float* fb = ed.fold + ((size_t)(blk - 1) * 256 + wave * 32) * 16;
+    glds16(fb + lane * 4, pre_lds);
+    glds16(fb + 256 + lane * 4, pre_lds + 1024);
+    const float *gw = ed.gn_w, *gb = ed.gn_b;
+    asm volatile("" : "+s"(gw), "+s"(gb));  // both pointers first: a select of the two loads becomes a load through
+                                            // a selected address, a round trip of its own in front of the DMA
+    const float* gsrc = (h ? gb : gw) + (blk - 1) * 256 + col;
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
+                                     (__attribute__((address_space(3))) void*)(pre_lds + 2048), 4, 0, 0);
+    asm volatile("" ::: "memory");
   };
 
   auto epilogue = [&](auto kind_tag, int gi) {
@@ -604,9 +642,30 @@ __device__ __forceinline__ void conv_x3s_body(const float* __restrict__ feats, i
   // SKIP (compile time): the tap-skipping stream code only where taps can be skipped (blocks 2, 3: dilation 4, 8);
   // the branch-free form for the others (same-box A/B: 1.099-1.108 ms with the skipping code everywhere, 1.084-1.090
   // this way)
-  auto stream = [&](auto skip_tag, int gi, int part) {
+  // The weight ring lives here, across the phase barriers: part 0 of a GEMM is primed by the epilogue before it
+  // (prime, ahead of that epilogue's closing barrier) and leaves the ring primed for part 1 (stream_part's CARRY).
+  BFrag<1> ring[x3s_pf<W, SP>()];
+  const int crot = X3S_ROT ? __builtin_amdgcn_readfirstlane((int)(blockIdx.x >> 3) & 7) : 0;
+  auto wpart = [&](int gi, int part) {  // the weights of GEMM gi's part
+    return reinterpret_cast<const char*>(gi == 8 ? ed.proj : ed.conv + (size_t)gi * 80 * (CHUNK_B / 2)) +
+           (size_t)part * 8 * CHUNK_B;
+  };
+  auto prime = [&](int gi) { prime_part<W, SP>(ring, wpart(gi, 0), loff, crot); };
+  // Where a primed ring reaches its part through a join of paths (the block loops' back edges, the fold operands'
+  // LDS-DMA in flight on one of them) the compiler's wait counting gives up and puts vmcnt(0) in front of EVERY tap's
+  // first MFMA, behind that step's refill: a round trip per tap.  Naming the primed fragments after the barrier makes
+  // it wait for them once, there, and count from a clean slate inside the part.
+  auto ring_landed = [&]() {
+#pragma unroll
+    for (int j = 0; j < x3s_pf<W, SP>() - 1; ++j) {
+      asm volatile("" : "+v"(ring[j].h[0]));
+      if constexpr (SP) asm volatile("" : "+v"(ring[j].l[0]));
+    }
+  };
+  auto stream = [&](auto skip_tag, int gi, auto part_tag) {
     constexpr bool SKIP = decltype(skip_tag)::value;
-    if (part == 0) {
+    constexpr int part = decltype(part_tag)::value;
+    if constexpr (part == 0) {
       acc.zero();
     } else {  // channels of B: the accumulators move from A's exponent to B's (exact), window by window
       float f[R];
@@ -618,11 +677,9 @@ __device__ __forceinline__ void conv_x3s_body(const float* __restrict__ feats, i
         for (int r = 0; r < 16; ++r) acc.c[t][0][r] *= f[x3s_rwin<W>(r)];
     }
     const bool proj = gi == 8;
-    const char* wb = reinterpret_cast<const char*>(proj ? ed.proj : ed.conv + (size_t)gi * 80 * (CHUNK_B / 2)) +
-                     (size_t)part * 8 * CHUNK_B;
     if (X3S_PRIO) __builtin_amdgcn_s_setprio(1);
-    stream_part<W, SKIP, SP>(acc, wb, proj ? 1 : 5, loff, xa + part * 8 * 32, i, proj ? 0 : 1 << (gi >> 1),
-                             proj ? 0 : 2, X3S_ROT ? __builtin_amdgcn_readfirstlane((int)(blockIdx.x >> 3) & 7) : 0);
+    stream_part<W, SKIP, SP, part == 0>(acc, ring, wpart(gi, part), proj ? 1 : 5, loff, xa + part * 8 * 32, i,
+                                        proj ? 0 : 1 << (gi >> 1), proj ? 0 : 2, crot);
     __builtin_amdgcn_s_setprio(0);
   };
 
@@ -643,33 +700,41 @@ __device__ __forceinline__ void conv_x3s_body(const float* __restrict__ feats, i
   if (grp == 1) phase_end();
   else lane_setup();
   stem_epilogue();
+  prime(0);
   phase_end();
   using NoSkip = std::integral_constant<bool, false>;
   using Skip = std::integral_constant<bool, true>;
+  using P0 = std::integral_constant<int, 0>;
+  using P1 = std::integral_constant<int, 1>;
   auto block = [&](auto skip_tag, int blk) {
-    stream(skip_tag, 2 * blk, 0);
+    ring_landed();
+    stream(skip_tag, 2 * blk, P0{});
     phase_end();
     prefetch(K0{}, 2 * blk);
-    stream(skip_tag, 2 * blk, 1);
+    stream(skip_tag, 2 * blk, P1{});
     phase_end();
     epilogue(K0{}, 2 * blk);
+    prime(2 * blk + 1);
     phase_end();
-    stream(skip_tag, 2 * blk + 1, 0);
+    stream(skip_tag, 2 * blk + 1, P0{});
     phase_end();
     prefetch(K1{}, 2 * blk + 1);
-    stream(skip_tag, 2 * blk + 1, 1);
+    stream(skip_tag, 2 * blk + 1, P1{});
     phase_end();
     epilogue(K1{}, 2 * blk + 1);
+    if (blk < 3) prefetch_fold(blk + 1);
+    prime(2 * blk + 2);  // the next block's conv1, or the proj
     phase_end();
   };
 #pragma unroll 1
   for (int blk = 0; blk < 2; ++blk) block(NoSkip{}, blk);
 #pragma unroll 1
   for (int blk = 2; blk < 4; ++blk) block(Skip{}, blk);
-  stream(NoSkip{}, 8, 0);
+  ring_landed();
+  stream(NoSkip{}, 8, P0{});
   phase_end();
   prefetch(K2{}, 8);
-  stream(NoSkip{}, 8, 1);
+  stream(NoSkip{}, 8, P1{});  // (the unit's last part: nothing is carried across units)
   phase_end();
   epilogue(K2{}, 8);
   phase_end();
