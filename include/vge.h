@@ -349,6 +349,69 @@ int vge_convblock_backward(const float* dy, const float* x, const float* w1, con
                            int B, int T, int C, int dilation, float* dx, float* dw1, float* dw2, float* dgamma,
                            float* dbeta, void* workspace, size_t workspace_bytes, vge_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * One layer of the temporal stack for training: nn.TransformerEncoderLayer(d_model = D, nhead = H,
+ * dim_feedforward = F, batch_first = True), post-norm, ReLU, eps 1e-5; a forward that keeps what the backward needs,
+ * and the backward to x and all twelve parameter tensors.  Exact f32; row-major activations [B,S,*].
+ *
+ *   x [B,S,D], S tokens (CLS + frames), d = D / H.  Parameters in torch's layouts: in_proj_weight Win [3D,D] (rows
+ *   q, k, v) and in_proj_bias b_in [3D]; out_proj Wo [D,D], b_o [D]; linear1 W1 [F,D], c1 [F]; linear2 W2 [D,F],
+ *   c2 [D]; norm1 g1, beta1 [D]; norm2 g2, beta2 [D].  Dropout multipliers (entries 0 or 1 / (1 - p)), each NULL for
+ *   all ones: m_attn [B,H,S,S], m1 [B,S,D], m_ff [B,S,F], m2 [B,S,D].
+ *   LN(u; g, beta) = u^ g + beta,  u^ = (u - mean_row) rstd_row,  rstd = 1 / sqrt(biased variance over D + eps).
+ *
+ *   forward    qkv = x Win^T + b_in     (q, k, v: columns 0, D, 2D; head h: columns h d .. h d + d - 1 of each)
+ *              P[b,h,i,:] = softmax_j(<q_i, k_j> / sqrt(d))         o = (P m_attn) v          z = o Wo^T + b_o
+ *              u1 = x + z m1            x1 = LN(u1; g1, beta1)      f = relu(x1 W1^T + c1) m_ff
+ *              g = f W2^T + c2          u2 = x1 + g m2              y = LN(u2; g2, beta2)
+ *   backward   LayerNorm, for (dy, u2, g2) and then (dx1, u1, g1):  dbeta = sum_rows dy,  dgamma = sum_rows dy u^,
+ *                q = dy gamma,  du = rstd (q - mean_D(q) - u^ mean_D(q u^))
+ *              dg = du2 m2              dW2 = dg^T f                dc2 = sum_rows dg
+ *              da = (dg W2) m_ff [f > 0]       dW1 = da^T x1        dc1 = sum_rows da         dx1 = du2 + da W1
+ *              dz = du1 m1              dWo = dz^T o                db_o = sum_rows dz        do = dz Wo
+ *              per (b, h):  dv = (P m_attn)^T do      dP = (do v^T) m_attn     dS = P (dP - sum_j dP P)
+ *                           dq = dS k / sqrt(d)       dk = dS^T q / sqrt(d)
+ *              dWin = dqkv^T x          db_in = sum_rows dqkv       dx = du1 + dqkv Win
+ *
+ * Saved tensors: the forward writes qkv [B,S,3D], u1 [B,S,D], f [B,S,F], u2 [B,S,D] and stats [4][B S] = (mean1,
+ * rstd1, mean2, rstd2); the backward takes them back with x, the masks, the four weights, g1, beta1 and g2.  P, o
+ * and x1 are recomputed in the backward (from qkv and m_attn, and from u1).  Pass all five NULL to a forward whose
+ * backward will not run: nothing but y is written then.
+ * Shapes: D a multiple of 32 in [32, 256]; H divides D and d = D / H is a multiple of 16 and at most 64; F = 4 D;
+ * 1 <= S <= 65; B >= 1 and every tensor below 2^31 elements; anything else returns VGE_ERR_UNSUPPORTED and the
+ * workspace queries return 0.  Every pointer is device memory, 16-byte aligned (VGE_ERR_ARG otherwise, and for a NULL
+ * other than a mask or the saved set); inputs may alias each other, an output or the workspace may overlap nothing
+ * else that is passed (VGE_ERR_ARG).  workspace: >= vge_timelayer_workspace_bytes for the backward, which is enough for
+ * either call; the forward alone needs vge_timelayer_forward_workspace_bytes (VGE_ERR_WORKSPACE otherwise); its
+ * contents do not carry over from one call to the next.  All of these checks run before the first HIP call.  No
+ * allocation, no host synchronisation, everything on `stream`.
+ * Sums: a GEMM output is MFMA chains of 16 exact f32 products added in f64 and rounded to f32 once; the attention's
+ * products are formed and summed in f64; softmax (row maximum subtracted) and LayerNorm row sums are f64 sums of f32
+ * values.  Only the parameter gradients are summed across samples: f64 partials per chunk of rows in the workspace,
+ * added by a second launch in chunk order.  No floating-point atomics; the order of every sum is fixed by
+ * (B, S, D, H), so two calls on the same input give the same bits.  A NaN in one sample's x reaches that sample's y
+ * and dx and the parameter gradients, and no other sample's y or dx.
+ */
+size_t vge_timelayer_workspace_bytes(int B, int S, int D, int H, int F);
+size_t vge_timelayer_forward_workspace_bytes(int B, int S, int D, int H, int F);
+int vge_timelayer_forward(const float* x, const float* in_proj_weight, const float* in_proj_bias,
+                          const float* out_proj_weight, const float* out_proj_bias, const float* linear1_weight,
+                          const float* linear1_bias, const float* linear2_weight, const float* linear2_bias,
+                          const float* norm1_weight, const float* norm1_bias, const float* norm2_weight,
+                          const float* norm2_bias, const float* m_attn, const float* m1, const float* m_ff,
+                          const float* m2, int B, int S, int D, int H, int F, float* qkv, float* u1, float* f, float* u2,
+                          float* stats, float* y, void* workspace, size_t workspace_bytes, vge_stream_t stream);
+int vge_timelayer_backward(const float* dy, const float* x, const float* in_proj_weight, const float* out_proj_weight,
+                           const float* linear1_weight, const float* linear2_weight, const float* norm1_weight,
+                           const float* norm1_bias, const float* norm2_weight, const float* m_attn, const float* m1,
+                           const float* m_ff, const float* m2, const float* qkv, const float* u1, const float* f,
+                           const float* u2, const float* stats, int B, int S, int D, int H, int F, float* dx,
+                           float* d_in_proj_weight, float* d_in_proj_bias, float* d_out_proj_weight,
+                           float* d_out_proj_bias, float* d_linear1_weight, float* d_linear1_bias,
+                           float* d_linear2_weight, float* d_linear2_bias, float* d_norm1_weight, float* d_norm1_bias,
+                           float* d_norm2_weight, float* d_norm2_bias, void* workspace, size_t workspace_bytes,
+                           vge_stream_t stream);
+
 const char* vge_last_error(void);
 const char* vge_version(void);
 

@@ -3,7 +3,7 @@
 config-2 synthetic set (256 synthetic 32-frame clips, one window each), d_model 256, dropout 0.1, after a warm-up.
 Prints one JSON object and nothing else.
 
-    python tools/bench_train.py [--conv-backend hip]
+    python tools/bench_train.py [--conv-backend hip] [--time-backend hip]
 
 ms are medians over the timed repetitions.  Per repetition the pieces of one step are timed in order -- featurise,
 the three time gathers, the four module forwards, the loss forward + backward (to the gradients of the four
@@ -16,7 +16,12 @@ B = 2048 on unit embeddings of ten classes.
 forward / backward kernels of vge_convblock.hip (a second module with the same initial weights and its own optimiser,
 HIP loss), alternated with the two existing columns in the same repetitions; and "convblock_240", one block alone
 (B = 240, T = 32, C = 256; events around 20 calls) with its FLOPs over the time against the 155 TFLOP/s the f32-input
-MFMA was measured at.  Without the flag the output is what it was."""
+MFMA was measured at.  Without the flag the output is what it was.
+
+--time-backend hip adds the column "time_hip" in the same way: the same step with the temporal stack's layers on the
+forward / backward kernels of vge_timelayer.hip (conv blocks on torch, HIP loss), alternated with the other columns in
+the same repetitions; and "timelayer_240", one layer alone (B = 240, S = 33, D = 256, 8 heads, dropout 0.1; events
+around 10 calls) on the kernels and as torch's own layer under autograd, forward and backward."""
 import argparse
 import copy
 import json
@@ -83,11 +88,51 @@ def convblock_alone(dev, B=240, Tn=32, Cn=256, calls=20):
     return out
 
 
+def timelayer_alone(dev, B=240, S=33, D=256, H=8, calls=10):
+    """One temporal layer's forward and backward alone, on the kernels and as torch's layer -> ms per call, and the
+    kernels' TFLOP/s over the 12 D^2 weights' GEMMs (forward 2, backward 4 FLOP per weight and row)."""
+    from torch.nn.attention import SDPBackend, sdpa_kernel
+    from vge import timelayer as TL
+    torch.manual_seed(3)
+    layer = torch.nn.TransformerEncoderLayer(D, H, 4 * D, 0.1, batch_first=True).to(dev).train()
+    params = tuple(p.detach() for p in TL.layer_params(layer))
+    x, dy = torch.randn(B, S, D, device=dev), torch.randn(B, S, D, device=dev)
+    masks = TL.draw_masks(x, H, 4 * D, 0.1)
+    _, saved = ops.timelayer_forward(x, params, H, masks)
+    xr = x.clone().requires_grad_(True)
+    t = {k: [] for k in ("hip_forward", "hip_backward", "torch_forward", "torch_backward")}
+    for rep in range(WARMUP + REPS):
+        ev = {}
+        ev["hip_forward"], _ = timed(lambda: [ops.timelayer_forward(x, params, H, masks) for _ in range(calls)])
+        ev["hip_backward"], _ = timed(lambda: [ops.timelayer_backward(dy, x, params, H, saved, masks)
+                                               for _ in range(calls)])
+        with sdpa_kernel(SDPBackend.MATH):
+            ev["torch_forward"], ys = timed(lambda: [layer(xr) for _ in range(calls)])
+            ev["torch_backward"], _ = timed(lambda: [torch.autograd.grad(y, [xr] + list(layer.parameters()), dy)
+                                                     for y in ys])
+        torch.cuda.synchronize(dev)
+        if rep >= WARMUP:
+            for k, (a, b) in ev.items():
+                t[k].append(a.elapsed_time(b) / calls)
+    out = {k + "_ms": round(statistics.median(v), 4) for k, v in t.items()}
+    gemm_flop = 2.0 * B * S * 12 * D * D
+    for k, flop in (("hip_forward", gemm_flop), ("hip_backward", 2 * gemm_flop)):
+        tf = flop / (out[k + "_ms"] * 1e-3) / 1e12
+        out[k + "_tflops"] = round(tf, 2)
+        out[k + "_share_of_f32_mfma_ceiling"] = round(tf / MFMA_F32_TFLOPS, 4)
+    out["hip_over_torch_forward"] = round(out["hip_forward_ms"] / out["torch_forward_ms"], 4)
+    out["hip_over_torch_backward"] = round(out["hip_backward_ms"] / out["torch_backward_ms"], 4)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--conv-backend", default="torch", choices=["torch", "hip"],
                     help="hip: add the conv_hip column (residual blocks on vge_convblock.hip) and convblock_240")
-    conv_backend = ap.parse_args().conv_backend
+    ap.add_argument("--time-backend", default="torch", choices=["torch", "hip"],
+                    help="hip: add the time_hip column (temporal layers on vge_timelayer.hip) and timelayer_240")
+    args = ap.parse_args()
+    conv_backend, time_backend = args.conv_backend, args.time_backend
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     clips, names = [], []
@@ -114,6 +159,10 @@ def main():
         model_h = HumanActionScorer(dims_raw, dims_diff, dropout=0.1, conv_backend="hip").to(dev).train()
         model_h.load_state_dict(copy.deepcopy(model.state_dict()))
         columns["conv_hip"] = (model_h, *T.make_optimizer(model_h, 3e-4, 100, 30), "hip")
+    if time_backend == "hip":
+        model_t = HumanActionScorer(dims_raw, dims_diff, dropout=0.1, time_backend="hip").to(dev).train()
+        model_t.load_state_dict(copy.deepcopy(model.state_dict()))
+        columns["time_hip"] = (model_t, *T.make_optimizer(model_t, 3e-4, 100, 30), "hip")
     order = tuple(columns)
     gen = torch.Generator().manual_seed(1337)
     tables = [V.partial_shuffle_indices(B, 32, generator=gen).to(dev), V.reverse_indices(B).to(dev),
@@ -154,6 +203,10 @@ def main():
         for k in ("forwards", "module_backward", "step"):
             out[f"conv_hip_over_torch_{k}"] = round(out["conv_hip"][k + "_ms"] / out["hip"][k + "_ms"], 4)
         out["convblock_240"] = convblock_alone(dev)
+    if time_backend == "hip":
+        for k in ("forwards", "module_backward", "step"):
+            out[f"time_hip_over_torch_{k}"] = round(out["time_hip"][k + "_ms"] / out["hip"][k + "_ms"], 4)
+        out["timelayer_240"] = timelayer_alone(dev)
 
     # the loss pair alone at B = 2048
     Bl = 2048

@@ -1,7 +1,7 @@
 // The scoring core's interface between the C ABI (vge_api.cpp) and its kernels: every kernel-argument struct, defined
 // once for host and device, and every launcher of vge_featurize.hip, vge_encoder.hip, vge_encoder_x3.hip,
-// vge_encoder_x3s.hip, vge_encoder_gen.hip, vge_transformer_x3.hip, vge_convblock.hip and vge_score.hip.  Host-safe: no
-// device helpers.
+// vge_encoder_x3s.hip, vge_encoder_gen.hip, vge_transformer_x3.hip, vge_convblock.hip, vge_timelayer.hip and
+// vge_score.hip.  Host-safe: no device helpers.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -216,6 +216,46 @@ hipError_t launch_convblock_forward(const ConvBlockFwdArgs& a, hipStream_t s);
 hipError_t launch_convblock_backward(const ConvBlockBwdArgs& a, hipStream_t s);
 hipError_t launch_convblock_wgrad(const ConvBlockWgradArgs& a, float* dw1, float* dw2, hipStream_t s);
 hipError_t launch_convblock_gbreduce(const double* gb_part, int B, int C, float* dgamma, float* dbeta, hipStream_t s);
+
+// ------------------------------------------------------------------ vge_timelayer.hip (training: one temporal layer)
+// Exact-f32 GEMM C [M][N] (row stride ldc) from A and B in one of three operand forms; epilogue in this order, each
+// step only where its pointer / flag is set: + bias[n], relu, * mask[m][n], gate[m][n] <= 0 ? 0 : v, res[m][n] + v
+// (mask, gate and res have C's layout).  TIME_GEMM_TN writes f64 partials part[chunk][M][N] over chunks of K instead.
+enum { TIME_GEMM_NT = 0,   // C[m][n] = sum_k A[m][k] B[n][k]
+       TIME_GEMM_NN = 1,   // C[m][n] = sum_k A[m][k] B[k][n]
+       TIME_GEMM_TN = 2 }; // part[c][m][n] = sum_{k in chunk c} A[k][m] B[k][n]
+struct TimeGemmArgs {
+  const float* A; int lda; const float* B; int ldb;
+  int M, N, K;
+  const float* bias; const float* mask; const float* gate; const float* res; int relu;
+  float* C; int ldc;
+  double* part; int k_per_chunk;       // TIME_GEMM_TN; k_per_chunk: set by the launcher
+};
+
+// qkv [B S][3 D], m (null: all ones) [B][H][S][S], d_o / o [B S][D], dqkv [B S][3 D]
+struct TimeAttnArgs {
+  const float* qkv; const float* m; const float* d_o;
+  float* o; float* dqkv;
+  int B, S, D, H;
+};
+
+int timelayer_wgrad_chunks(int R, int* k_per_chunk);  // row chunks of a weight gradient over R rows, rows per chunk
+int timelayer_ln_chunks(int R);                       // workgroups (partials) of the LayerNorm backward
+int timelayer_colsum_chunks(int R);                   // row chunks of a bias gradient
+hipError_t launch_timelayer_gemm(const TimeGemmArgs& a, int form, hipStream_t s);
+hipError_t launch_timelayer_attn_forward(const TimeAttnArgs& a, hipStream_t s);
+hipError_t launch_timelayer_attn_backward(const TimeAttnArgs& a, hipStream_t s);
+// u = x (+ z m; z, m nullable), y = LayerNorm(u); u, mean / rstd stored where given
+hipError_t launch_timelayer_ln_forward(const float* x, const float* z, const float* m, const float* gamma,
+                                       const float* beta, int R, int D, float* u, float* mean, float* rstd, float* y,
+                                       hipStream_t s);
+// du, dum = du m (m nullable: dum untouched), dgamma, dbeta; part: 2 timelayer_ln_chunks(R) D doubles
+hipError_t launch_timelayer_ln_backward(const float* dy, const float* u, const float* mean, const float* rstd,
+                                        const float* gamma, const float* m, int R, int D, float* du, float* dum,
+                                        double* part, float* dgamma, float* dbeta, hipStream_t s);
+hipError_t launch_timelayer_reduce(const double* part, int n_chunks, int n, float* out, hipStream_t s);
+// out[n] = sum_r src[r][n]; part: timelayer_colsum_chunks(R) N doubles
+hipError_t launch_timelayer_colsum(const float* src, int R, int N, double* part, float* out, hipStream_t s);
 
 // ------------------------------------------------------------------ vge_score.hip
 // d <= 256

@@ -64,7 +64,9 @@ EXPORTS = ["vge_featurize", "vge_featurize_layout", "vge_layout_feat_dim", "vge_
            "vge_apng_decode_device", "vge_apng_decode_device_workspace_bytes",
            "vge_time_gather", "vge_tcl_workspace_bytes", "vge_tcl_loss", "vge_hardneg_loss", "vge_centroid_distance",
            "vge_tcl_grad_workspace_bytes", "vge_tcl_loss_grad", "vge_hardneg_loss_grad",
-           "vge_convblock_workspace_bytes", "vge_convblock_forward_workspace_bytes", "vge_convblock_forward", "vge_convblock_backward"]
+           "vge_convblock_workspace_bytes", "vge_convblock_forward_workspace_bytes", "vge_convblock_forward", "vge_convblock_backward",
+           "vge_timelayer_workspace_bytes", "vge_timelayer_forward_workspace_bytes", "vge_timelayer_forward",
+           "vge_timelayer_backward"]
 
 
 class VgeError(RuntimeError):
@@ -333,6 +335,10 @@ def load() -> C.CDLL:
         "vge_convblock_forward_workspace_bytes": [i32],
         "vge_convblock_forward": [vp] * 6 + [i32] * 4 + [vp] * 6 + [C.c_size_t, vp],
         "vge_convblock_backward": [vp] * 10 + [i32] * 4 + [vp] * 6 + [C.c_size_t, vp],
+        "vge_timelayer_workspace_bytes": [i32] * 5,
+        "vge_timelayer_forward_workspace_bytes": [i32] * 5,
+        "vge_timelayer_forward": [vp] * 17 + [i32] * 5 + [vp] * 7 + [C.c_size_t, vp],
+        "vge_timelayer_backward": [vp] * 18 + [i32] * 5 + [vp] * 14 + [C.c_size_t, vp],
     }
     for name, args in sig.items():
         f = getattr(lib, name)
@@ -343,6 +349,8 @@ def load() -> C.CDLL:
     lib.vge_tcl_grad_workspace_bytes.restype = C.c_size_t
     lib.vge_convblock_workspace_bytes.restype = C.c_size_t
     lib.vge_convblock_forward_workspace_bytes.restype = C.c_size_t
+    lib.vge_timelayer_workspace_bytes.restype = C.c_size_t
+    lib.vge_timelayer_forward_workspace_bytes.restype = C.c_size_t
     lib.vge_jpeg_entropy_workspace_bytes.restype = C.c_size_t
     lib.vge_jpeg_entropy_decode_workspace_bytes.restype = C.c_size_t
     lib.vge_ingest_decode_device_workspace_bytes.restype = C.c_size_t

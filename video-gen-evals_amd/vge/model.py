@@ -22,8 +22,10 @@ This module's forward and backward run on torch's kernels (rocBLAS / hipBLASLt a
 encoder kernels keep no activations and have no backward.  The HIP of a training step is the loss (vge.losses) and,
 with conv_backend="hip", the residual blocks of the movement encoders: each block is then one autograd node
 (vge.convblock.ConvBlockFunction) on the forward and backward kernels of vge_convblock.hip, with the same parameters
-under the same state-dict keys.  The default conv_backend="torch" is the graph described above, unchanged.  The stem,
-the projection, the fusion and the temporal stack run on torch under either backend.
+under the same state-dict keys.  With time_backend="hip" each layer of the temporal stack is one autograd node as well
+(vge.timelayer.TimeLayerFunction) on the kernels of vge_timelayer.hip, again on the nn.TransformerEncoder's own
+parameters.  The defaults conv_backend="torch" and time_backend="torch" are the graph described above, unchanged.  The
+stem, the projection and the fusion run on torch under every backend.
 """
 from __future__ import annotations
 
@@ -36,16 +38,24 @@ import torch.nn.functional as F
 from torch.nn.attention import SDPBackend, sdpa_kernel
 
 from .convblock import convblock
+from .timelayer import draw_masks, layer_params, timelayer
 
 KERNEL_SIZE = 5
 DILATIONS = (1, 2, 4, 8)
 CONV_BACKENDS = ("torch", "hip")
+TIME_BACKENDS = ("torch", "hip")
 
 
 def _check_conv_backend(conv_backend: str) -> str:
     if conv_backend not in CONV_BACKENDS:
         raise ValueError(f"conv_backend must be one of {CONV_BACKENDS}, got {conv_backend!r}")
     return conv_backend
+
+
+def _check_time_backend(time_backend: str) -> str:
+    if time_backend not in TIME_BACKENDS:
+        raise ValueError(f"time_backend must be one of {TIME_BACKENDS}, got {time_backend!r}")
+    return time_backend
 
 
 def _uniform_fan_in(shape, fan_in: int) -> nn.Parameter:
@@ -168,9 +178,10 @@ class _Positions(nn.Module):
 class HumanActionScorer(nn.Module):
     def __init__(self, dims_map_raw: Dict[str, int], dims_map_diff: Dict[str, int], d_model: int = 256,
                  latent_dim: int = 128, time_layers: int = 4, time_heads: int = 8, dropout: float = 0.1,
-                 conv_backend: str = "torch"):
+                 conv_backend: str = "torch", time_backend: str = "torch"):
         super().__init__()
         self.conv_backend = _check_conv_backend(conv_backend)
+        self.time_backend = _check_time_backend(time_backend)
         if not isinstance(dims_map_raw, dict) or not isinstance(dims_map_diff, dict):
             raise ValueError("dims_map_raw and dims_map_diff must be dicts of {modality: dim}")
         if set(dims_map_raw) != set(dims_map_diff):
@@ -192,6 +203,18 @@ class HumanActionScorer(nn.Module):
         layer = nn.TransformerEncoderLayer(d_model, time_heads, 4 * d_model, dropout, batch_first=True)
         self.temporal = nn.TransformerEncoder(layer, num_layers=time_layers, enable_nested_tensor=False)
 
+    def _temporal_hip(self, tokens: torch.Tensor) -> torch.Tensor:
+        """self.temporal layer by layer through vge.timelayer, on each layer's own parameters.  In training mode the
+        four dropout multipliers are drawn as torch's layer draws its masks (vge.timelayer.draw_masks)."""
+        for layer in self.temporal.layers:
+            H = layer.self_attn.num_heads
+            masks = None
+            if self.training:
+                masks = draw_masks(tokens, H, layer.linear1.out_features, layer.self_attn.dropout, layer.dropout1.p,
+                                   layer.dropout.p, layer.dropout2.p)
+            tokens = timelayer(tokens, layer_params(layer), H, masks)
+        return tokens
+
     def forward(self, x: torch.Tensor):
         """x [B,T,sum(raw) + sum(diff)] -> (seq_embed [B,d], frame_embeds [B,T+1,d], tokens [B,T+1,d])."""
         n_raw = sum(self.dims_raw.values())
@@ -208,6 +231,9 @@ class HumanActionScorer(nn.Module):
             per_mod.append(F.layer_norm(s, s.shape[-1:]))
         frames = self.fusion(torch.stack(per_mod, dim=2))
         tokens = torch.cat([self.cls.expand(x.shape[0], -1, -1), frames], dim=1)
+        if self.time_backend == "hip":
+            tokens = self._temporal_hip(self.pos_enc(tokens))
+            return F.normalize(tokens[:, 0, :]), F.normalize(tokens, dim=-1), tokens
         # attention as matmul + softmax + matmul (the "math" route of scaled_dot_product_attention): torch's fused
         # attention kernels are less exact in float32 -- with them two step-0 gradient norms of the golden checkpoint
         # sit 8.7 r from float64 on an MI355X, with this route the worst is 2.2 r

@@ -498,3 +498,98 @@ def convblock_backward(dy: torch.Tensor, x: torch.Tensor, w1: torch.Tensor, w2: 
                                        _ptr(dgamma), _ptr(dbeta), _ptr(ws), wsb, _stream(x.device)),
             "vge_convblock_backward")
     return dx, dw1, dw2, dgamma, dbeta
+
+
+# the twelve parameter tensors of one temporal layer, in the order of vge_timelayer_forward, with their shapes
+TIMELAYER_PARAMS = ("in_proj_weight", "in_proj_bias", "out_proj_weight", "out_proj_bias", "linear1_weight",
+                    "linear1_bias", "linear2_weight", "linear2_bias", "norm1_weight", "norm1_bias", "norm2_weight",
+                    "norm2_bias")
+
+
+def _timelayer_shapes(B: int, S: int, D: int, H: int, F_: int) -> Dict[str, Tuple[int, ...]]:
+    return {"x": (B, S, D), "y": (B, S, D), "dy": (B, S, D), "dx": (B, S, D),
+            "in_proj_weight": (3 * D, D), "in_proj_bias": (3 * D,), "out_proj_weight": (D, D), "out_proj_bias": (D,),
+            "linear1_weight": (F_, D), "linear1_bias": (F_,), "linear2_weight": (D, F_), "linear2_bias": (D,),
+            "norm1_weight": (D,), "norm1_bias": (D,), "norm2_weight": (D,), "norm2_bias": (D,),
+            "m_attn": (B, H, S, S), "m1": (B, S, D), "m_ff": (B, S, F_), "m2": (B, S, D),
+            "qkv": (B, S, 3 * D), "u1": (B, S, D), "f": (B, S, F_), "u2": (B, S, D), "stats": (4, B * S)}
+
+
+TIMELAYER_SAVED = ("qkv", "u1", "f", "u2", "stats")
+TIMELAYER_MASKS = ("m_attn", "m1", "m_ff", "m2")
+
+
+def _timelayer_check(fn: str, x: torch.Tensor, params: Sequence[torch.Tensor], heads: int,
+                     named: Sequence[Tuple[str, Optional[torch.Tensor]]]) -> Tuple[int, int, int, int, Dict]:
+    if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise L.VgeError(f"{fn}: x must be a contiguous float32 [B,S,D] tensor, got {x.dtype} {tuple(x.shape)}")
+    if len(params) != 12:
+        raise L.VgeError(f"{fn}: params must be the twelve tensors {TIMELAYER_PARAMS}")
+    B, S, D = x.shape
+    F_ = int(params[4].shape[0]) if params[4].dim() == 2 else -1
+    shapes = _timelayer_shapes(B, S, D, int(heads), F_)
+    for name, t in list(zip(TIMELAYER_PARAMS, params)) + [(n, t) for n, t in named if t is not None]:
+        key = name[2:] if name.startswith("d_") else name
+        if t.dtype != torch.float32 or tuple(t.shape) != shapes[key] or not t.is_contiguous() or t.device != x.device:
+            raise L.VgeError(f"{fn}: {name} must be a contiguous float32 {list(shapes[key])} tensor on {x.device}, got "
+                             f"{t.dtype} {tuple(t.shape)} on {t.device}")
+    return B, S, D, F_, shapes
+
+
+def _timelayer_new(shapes, names, device):
+    return tuple(torch.empty(shapes[n], dtype=torch.float32, device=device) for n in names)
+
+
+def timelayer_forward(x: torch.Tensor, params: Sequence[torch.Tensor], heads: int, masks=None, save: bool = True,
+                      y: Optional[torch.Tensor] = None, saved=None, workspace: Optional[torch.Tensor] = None):
+    """One temporal layer (vge_timelayer_forward, include/vge.h) on the current stream -> (y, saved), saved = (qkv, u1,
+    f, u2, stats) for timelayer_backward, or None with save=False (nothing but y is written).  x [B,S,D] float32;
+    params: the twelve tensors of TIMELAYER_PARAMS; masks: (m_attn, m1, m_ff, m2), each a dropout multiplier or None,
+    or None for no dropout; y / saved: the tensors to write, or None; workspace: a float32 tensor to use, or None."""
+    lib = L.load()
+    masks = tuple(masks) if masks is not None else (None,) * 4
+    given = tuple(saved) if (save and saved is not None) else (None,) * 5
+    B, S, D, F_, shapes = _timelayer_check("timelayer_forward", x, params, heads,
+                                           list(zip(TIMELAYER_MASKS, masks)) + [("y", y)] +
+                                           list(zip(TIMELAYER_SAVED, given)))
+    if y is None:
+        y = torch.empty_like(x)
+    if save and saved is None:
+        saved = _timelayer_new(shapes, TIMELAYER_SAVED, x.device)
+    out = tuple(saved) if save else (None,) * 5
+    wsb = int(lib.vge_timelayer_forward_workspace_bytes(B, S, D, int(heads), F_))
+    if workspace is None:
+        workspace = torch.empty(max(wsb, 16) // 4, dtype=torch.float32, device=x.device)
+    else:
+        wsb = workspace.numel() * 4
+    L.check(lib.vge_timelayer_forward(_ptr(x), *[_ptr(p) for p in params], *[_ptr(m) for m in masks], B, S, D,
+                                      int(heads), F_, *[_ptr(t) for t in out], _ptr(y), _ptr(workspace), wsb,
+                                      _stream(x.device)), "vge_timelayer_forward")
+    return y, (tuple(saved) if save else None)
+
+
+def timelayer_backward(dy: torch.Tensor, x: torch.Tensor, params: Sequence[torch.Tensor], heads: int, saved,
+                       masks=None, out=None, workspace: Optional[torch.Tensor] = None):
+    """The layer's backward (vge_timelayer_backward) on the current stream -> (dx, then the twelve parameter gradients
+    in TIMELAYER_PARAMS order).  saved: timelayer_forward's (qkv, u1, f, u2, stats) of the same x, params and masks;
+    out: the thirteen result tensors, or None; workspace: a float32 tensor to use, or None."""
+    lib = L.load()
+    masks = tuple(masks) if masks is not None else (None,) * 4
+    named = [("dy", dy)] + list(zip(TIMELAYER_MASKS, masks)) + list(zip(TIMELAYER_SAVED, saved))
+    if out is not None:
+        named += list(zip(("dx",) + tuple("d_" + n for n in TIMELAYER_PARAMS), out))
+    B, S, D, F_, shapes = _timelayer_check("timelayer_backward", x, params, heads, named)
+    if out is None:
+        out = _timelayer_new(shapes, ("dx",) + TIMELAYER_PARAMS, x.device)
+    wsb = int(lib.vge_timelayer_workspace_bytes(B, S, D, int(heads), F_))
+    if workspace is None:
+        workspace = torch.empty(max(wsb, 16) // 4, dtype=torch.float32, device=x.device)
+    else:
+        wsb = workspace.numel() * 4
+    p = dict(zip(TIMELAYER_PARAMS, params))
+    weights = [p[n] for n in ("in_proj_weight", "out_proj_weight", "linear1_weight", "linear2_weight", "norm1_weight",
+                              "norm1_bias", "norm2_weight")]
+    L.check(lib.vge_timelayer_backward(_ptr(dy), _ptr(x), *[_ptr(t) for t in weights], *[_ptr(m) for m in masks],
+                                       *[_ptr(t) for t in saved], B, S, D, int(heads), F_, *[_ptr(t) for t in out],
+                                       _ptr(workspace), wsb, _stream(x.device)), "vge_timelayer_backward")
+    return tuple(out)
