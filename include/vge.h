@@ -412,6 +412,89 @@ int vge_timelayer_backward(const float* dy, const float* x, const float* in_proj
                            float* d_norm2_weight, float* d_norm2_bias, void* workspace, size_t workspace_bytes,
                            vge_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * A bias-free linear map for training: the movement encoders' stems (1 x 1 convolutions) and projections.
+ *
+ *   x [R,K] with row stride ldx (floats) -- a column slice of a wider tensor is read in place --, W [N,K] as
+ *   _ConvWeight.weight[:, :, 0] and _Linear.weight hold it, y and dy [R,N] dense.
+ *
+ *   forward    y[r,n]  = sum_k x[r,k] W[n,k]
+ *   backward   dx[r,k] = sum_n dy[r,n] W[n,k]        (dx [R,K] dense; skipped when dx is NULL)
+ *              dW[n,k] = sum_r dy[r,n] x[r,k]
+ *
+ * Shapes: R >= 1, 1 <= K <= 4096, N a multiple of 32 in [32, 256], R max(K, N, ldx) < 2^31: anything else returns
+ * VGE_ERR_UNSUPPORTED (and the workspace query 0); ldx < K returns VGE_ERR_ARG.  x needs 4-byte alignment only -- it is
+ * read with 16-byte loads where its address, ldx and K are all multiples of 4 floats, with scalar loads otherwise --;
+ * every other pointer is device memory, 16-byte aligned (VGE_ERR_ARG otherwise, and for a NULL other than dx); inputs
+ * may alias each other, an output or the workspace may overlap nothing else that is passed (VGE_ERR_ARG).  workspace:
+ * >= vge_linear_workspace_bytes(R, K, N) bytes for the backward (VGE_ERR_WORKSPACE otherwise); the forward needs none.
+ * All of these checks run before the first HIP call.  No allocation, no host synchronisation, everything on `stream`.
+ * Sums: the temporal layer's GEMM rule -- MFMA chains of 16 exact f32 products added in f64 and rounded to f32 once; K
+ * past the operand is zero in LDS and is never read from memory nor stored; dW is f64 partials per chunk of rows in the
+ * workspace, added by a second launch in chunk order.  No floating-point atomics: two calls give the same bits.
+ */
+size_t vge_linear_workspace_bytes(int R, int K, int N);
+int vge_linear_forward(const float* x, int ldx, const float* W, float* y, int R, int K, int N, vge_stream_t stream);
+int vge_linear_backward(const float* dy, const float* x, int ldx, const float* W, float* dx, float* dW,
+                        void* workspace, size_t workspace_bytes, int R, int K, int N, vge_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The modality fusion for training: the affine-free LayerNorm over each modality's token and the learned-query
+ * attention over the M tokens of a row (vge/model.py _Fusion), forward and backward, in the folded form.  eps 1e-5.
+ *
+ *   s [R,M,D]: the per-modality sums of R = B T frames.  Parameters: latent [D], q_ln g_q, b_q [D], kv_ln g_kv, b_kv
+ *   [D], Wq, Wk, Wv, Wo [D,D] (out, in), logit_temp, logit_bias [M].  m_attn [R,M]: the dropout multiplier of the
+ *   attention weights (entries 0 or 1 / (1 - p)), NULL for all ones.
+ *   LN^(v) = (v - mean_D(v)) rstd,  rstd = 1 / sqrt(biased variance over D + eps).
+ *
+ *   forward    t_m = LN^(s_m)          h_m = LN^(t_m)             kv_m = h_m g_kv + b_kv
+ *              ql = LN^(latent) g_q + b_q      qv = Wq ql          u = Wk^T qv          (the same for every row)
+ *              c_m = 1 / sqrt(D) / (softplus(logit_temp_m) + 1e-3)
+ *              l_m = <kv_m, u> c_m + logit_bias_m      a = softmax_m(l)        ad_m = a_m m_attn_m
+ *              p = sum_m ad_m kv_m     vp = Wv p        out = Wo vp
+ *   backward   dWo = d_out^T vp        dvp = d_out Wo   dWv = dvp^T p          dp = dvp Wv
+ *              da_m = <dp, kv_m> m_attn_m              dl_m = a_m (da_m - sum_j a_j da_j)
+ *              dlogit_bias_m = sum_rows dl_m           dc_m = sum_rows dl_m <kv_m, u>
+ *              dlogit_temp_m = -dc_m c_m sigmoid(logit_temp_m) / (softplus(logit_temp_m) + 1e-3)
+ *              dkv_m = ad_m dp + dl_m c_m u            du = sum_rows sum_m dl_m c_m kv_m
+ *              dg_kv = sum_rows sum_m dkv_m h_m        db_kv = sum_rows sum_m dkv_m
+ *              LN^ backward, for (dkv_m g_kv, h_m, rstd1) and then (dt_m, t_m, rstd0):
+ *                dv = rstd (q - mean_D(q) - v^ mean_D(q v^));   ds_m is the second one's result
+ *              dWk = qv (x) du          dqv = Wk du     dWq = dqv (x) ql       dql = Wq^T dqv
+ *              dg_q = dql LN^(latent)   db_q = dql      dlatent = LN^ backward of (dql g_q)
+ *
+ * Saved tensors: the forward writes stats [4][R M] = (mean0, rstd0 of s_m; mean1, rstd1 of t_m), a [R,M], p [R,D] and
+ * vp [R,D]; the backward takes them back with s, m_attn and the parameters.  t, h and kv are recomputed from s.  Pass
+ * all four NULL to a forward whose backward will not run: nothing but out is written then.
+ * Shapes: R >= 1, 1 <= M <= 8, D a multiple of 32 in [32, 256], R M D < 2^31; anything else returns
+ * VGE_ERR_UNSUPPORTED and the workspace queries return 0.  Every pointer is device memory, 16-byte aligned
+ * (VGE_ERR_ARG otherwise, and for a NULL other than m_attn or the saved set); inputs may alias each other, an output
+ * or the workspace may overlap nothing else that is passed (VGE_ERR_ARG).  workspace: >= vge_fusion_workspace_bytes for
+ * the backward, which is enough for either call; the forward alone needs vge_fusion_forward_workspace_bytes
+ * (VGE_ERR_WORKSPACE otherwise).  All of these checks run before the first HIP call.  No allocation, no host
+ * synchronisation, everything on `stream`.
+ * Sums: the four GEMMs over R rows and their gradients follow the linear node's rule.  Row sums (LayerNorm means and
+ * variances, the dot products, the softmax sum, the pooling) are f64 sums rounded once; the softmax subtracts the row
+ * maximum.  Only parameter gradients are summed across rows: f64 partials per 16 rows in the workspace, added by a
+ * second launch in chunk order.  No floating-point atomics: two calls give the same bits.  A row's out and ds depend
+ * on that row of s, d_out and m_attn alone.
+ */
+size_t vge_fusion_workspace_bytes(int R, int M, int D);
+size_t vge_fusion_forward_workspace_bytes(int R, int M, int D);
+int vge_fusion_forward(const float* s, const float* latent, const float* q_ln_weight, const float* q_ln_bias,
+                       const float* kv_ln_weight, const float* kv_ln_bias, const float* Wq, const float* Wk,
+                       const float* Wv, const float* Wo, const float* logit_temp, const float* logit_bias,
+                       const float* m_attn, int R, int M, int D, float* stats, float* a, float* p, float* vp, float* out,
+                       void* workspace, size_t workspace_bytes, vge_stream_t stream);
+int vge_fusion_backward(const float* d_out, const float* s, const float* latent, const float* q_ln_weight,
+                        const float* q_ln_bias, const float* kv_ln_weight, const float* kv_ln_bias, const float* Wq,
+                        const float* Wk, const float* Wv, const float* Wo, const float* logit_temp,
+                        const float* logit_bias, const float* m_attn, const float* stats, const float* a, const float* p,
+                        const float* vp, int R, int M, int D, float* ds, float* d_latent, float* d_q_ln_weight,
+                        float* d_q_ln_bias, float* d_kv_ln_weight, float* d_kv_ln_bias, float* d_Wq, float* d_Wk,
+                        float* d_Wv, float* d_Wo, float* d_logit_temp, float* d_logit_bias, void* workspace,
+                        size_t workspace_bytes, vge_stream_t stream);
+
 const char* vge_last_error(void);
 const char* vge_version(void);
 

@@ -3,7 +3,7 @@
 config-2 synthetic set (256 synthetic 32-frame clips, one window each), d_model 256, dropout 0.1, after a warm-up.
 Prints one JSON object and nothing else.
 
-    python tools/bench_train.py [--conv-backend hip] [--time-backend hip]
+    python tools/bench_train.py [--conv-backend hip] [--time-backend hip] [--linear-backend hip] [--fusion-backend hip]
 
 ms are medians over the timed repetitions.  Per repetition the pieces of one step are timed in order -- featurise,
 the three time gathers, the four module forwards, the loss forward + backward (to the gradients of the four
@@ -21,7 +21,13 @@ MFMA was measured at.  Without the flag the output is what it was.
 --time-backend hip adds the column "time_hip" in the same way: the same step with the temporal stack's layers on the
 forward / backward kernels of vge_timelayer.hip (conv blocks on torch, HIP loss), alternated with the other columns in
 the same repetitions; and "timelayer_240", one layer alone (B = 240, S = 33, D = 256, 8 heads, dropout 0.1; events
-around 10 calls) on the kernels and as torch's own layer under autograd, forward and backward."""
+around 10 calls) on the kernels and as torch's own layer under autograd, forward and backward.
+
+--linear-backend hip and --fusion-backend hip add the columns "linear_hip" (stems and projections on vge_linear.hip)
+and "fusion_hip" (the per-modality LayerNorm and the fusion on vge_fusion.hip); given together they add
+"linear_fusion_hip" with both, and with all four backend flags on hip the column "all_hip".  --fusion-backend hip also
+adds "fusion_240", the fusion node alone (R = 240 x 32, M = 5, D = 256, dropout 0.1; events around 10 calls) on the
+kernels and as the module's _Fusion behind F.layer_norm under autograd, forward and backward."""
 import argparse
 import copy
 import json
@@ -125,14 +131,49 @@ def timelayer_alone(dev, B=240, S=33, D=256, H=8, calls=10):
     return out
 
 
+def fusion_alone(dev, R=240 * 32, M=5, D=256, calls=10):
+    """The fusion node's forward and backward alone, on the kernels and as torch's graph -> ms per call."""
+    import torch.nn.functional as F
+    from vge import fusion as FU
+    from vge.model import _Fusion
+    torch.manual_seed(4)
+    mod = _Fusion(D, M, 0.1).to(dev).train()
+    params = tuple(p.detach().reshape(D) if i == 0 else p.detach() for i, p in enumerate(FU.fusion_params(mod)))
+    s, dy = torch.randn(R, M, D, device=dev), torch.randn(R, D, device=dev)
+    m_attn = F.dropout(torch.ones(R, M, device=dev), 0.1, True)
+    _, saved = ops.fusion_forward(s, params, m_attn)
+    sr = s.view(240, R // 240, M, D).clone().requires_grad_(True)          # _Fusion takes [B,T,M,D]
+    dyr = dy.view(240, R // 240, D)
+    t = {k: [] for k in ("hip_forward", "hip_backward", "torch_forward", "torch_backward")}
+    for rep in range(WARMUP + REPS):
+        ev = {}
+        ev["hip_forward"], _ = timed(lambda: [ops.fusion_forward(s, params, m_attn) for _ in range(calls)])
+        ev["hip_backward"], _ = timed(lambda: [ops.fusion_backward(dy, s, params, saved, m_attn) for _ in range(calls)])
+        ev["torch_forward"], ys = timed(lambda: [mod(F.layer_norm(sr, (D,))) for _ in range(calls)])
+        ev["torch_backward"], _ = timed(lambda: [torch.autograd.grad(y, [sr] + list(mod.parameters()), dyr) for y in ys])
+        torch.cuda.synchronize(dev)
+        if rep >= WARMUP:
+            for k, (a, b) in ev.items():
+                t[k].append(a.elapsed_time(b) / calls)
+    out = {k + "_ms": round(statistics.median(v), 4) for k, v in t.items()}
+    out["hip_over_torch_forward"] = round(out["hip_forward_ms"] / out["torch_forward_ms"], 4)
+    out["hip_over_torch_backward"] = round(out["hip_backward_ms"] / out["torch_backward_ms"], 4)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--conv-backend", default="torch", choices=["torch", "hip"],
                     help="hip: add the conv_hip column (residual blocks on vge_convblock.hip) and convblock_240")
     ap.add_argument("--time-backend", default="torch", choices=["torch", "hip"],
                     help="hip: add the time_hip column (temporal layers on vge_timelayer.hip) and timelayer_240")
+    ap.add_argument("--linear-backend", default="torch", choices=["torch", "hip"],
+                    help="hip: add the linear_hip column (stems and projections on vge_linear.hip)")
+    ap.add_argument("--fusion-backend", default="torch", choices=["torch", "hip"],
+                    help="hip: add the fusion_hip column (LayerNorm + fusion on vge_fusion.hip) and fusion_240")
     args = ap.parse_args()
     conv_backend, time_backend = args.conv_backend, args.time_backend
+    linear_backend, fusion_backend = args.linear_backend, args.fusion_backend
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     clips, names = [], []
@@ -163,6 +204,20 @@ def main():
         model_t = HumanActionScorer(dims_raw, dims_diff, dropout=0.1, time_backend="hip").to(dev).train()
         model_t.load_state_dict(copy.deepcopy(model.state_dict()))
         columns["time_hip"] = (model_t, *T.make_optimizer(model_t, 3e-4, 100, 30), "hip")
+    extra = {}
+    if fusion_backend == "hip":
+        extra["fusion_hip"] = {"fusion_backend": "hip"}
+    if linear_backend == "hip":
+        extra["linear_hip"] = {"linear_backend": "hip"}
+    if linear_backend == fusion_backend == "hip":
+        extra["linear_fusion_hip"] = {"linear_backend": "hip", "fusion_backend": "hip"}
+        if conv_backend == time_backend == "hip":
+            extra["all_hip"] = {"conv_backend": "hip", "time_backend": "hip", "linear_backend": "hip",
+                                "fusion_backend": "hip"}
+    for name, kw in extra.items():
+        m = HumanActionScorer(dims_raw, dims_diff, dropout=0.1, **kw).to(dev).train()
+        m.load_state_dict(copy.deepcopy(model.state_dict()))
+        columns[name] = (m, *T.make_optimizer(m, 3e-4, 100, 30), "hip")
     order = tuple(columns)
     gen = torch.Generator().manual_seed(1337)
     tables = [V.partial_shuffle_indices(B, 32, generator=gen).to(dev), V.reverse_indices(B).to(dev),
@@ -207,6 +262,11 @@ def main():
         for k in ("forwards", "module_backward", "step"):
             out[f"time_hip_over_torch_{k}"] = round(out["time_hip"][k + "_ms"] / out["hip"][k + "_ms"], 4)
         out["timelayer_240"] = timelayer_alone(dev)
+    for name in extra:
+        for k in ("forwards", "module_backward", "step"):
+            out[f"{name}_over_torch_{k}"] = round(out[name][k + "_ms"] / out["hip"][k + "_ms"], 4)
+    if fusion_backend == "hip":
+        out["fusion_240"] = fusion_alone(dev)
 
     # the loss pair alone at B = 2048
     Bl = 2048

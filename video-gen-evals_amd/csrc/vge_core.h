@@ -1,7 +1,7 @@
 // The scoring core's interface between the C ABI (vge_api.cpp) and its kernels: every kernel-argument struct, defined
 // once for host and device, and every launcher of vge_featurize.hip, vge_encoder.hip, vge_encoder_x3.hip,
-// vge_encoder_x3s.hip, vge_encoder_gen.hip, vge_transformer_x3.hip, vge_convblock.hip, vge_timelayer.hip and
-// vge_score.hip.  Host-safe: no device helpers.
+// vge_encoder_x3s.hip, vge_encoder_gen.hip, vge_transformer_x3.hip, vge_convblock.hip, vge_timelayer.hip,
+// vge_linear.hip, vge_fusion.hip and vge_score.hip.  Host-safe: no device helpers.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -256,6 +256,43 @@ hipError_t launch_timelayer_ln_backward(const float* dy, const float* u, const f
 hipError_t launch_timelayer_reduce(const double* part, int n_chunks, int n, float* out, hipStream_t s);
 // out[n] = sum_r src[r][n]; part: timelayer_colsum_chunks(R) N doubles
 hipError_t launch_timelayer_colsum(const float* src, int R, int N, double* part, float* out, hipStream_t s);
+
+// ------------------------------------------------------------------ vge_linear.hip (training: a bias-free linear map)
+// y [R][N] = x W^T, dx [R][K] = dy W, dW [N][K] = dy^T x on the GEMM of vge_f32gemm.h; x [R][K] with row stride ldx,
+// W [N][K].  x needs 4-byte alignment only: an operand that is not 16-byte aligned row by row, or a K that is no
+// multiple of 4, takes the scalar-load instantiations.  part: linear_wgrad_chunks(R) N K doubles.
+int linear_wgrad_chunks(int R);
+hipError_t launch_linear_forward(const float* x, int ldx, const float* W, float* y, int R, int K, int N, hipStream_t s);
+hipError_t launch_linear_dgrad(const float* dy, const float* W, float* dx, int R, int K, int N, hipStream_t s);
+hipError_t launch_linear_wgrad(const float* dy, const float* x, int ldx, double* part, float* dW, int R, int K, int N,
+                               hipStream_t s);
+
+// ------------------------------------------------------------------ vge_fusion.hip (training: the modality fusion)
+// s, ds [R][M][D]; stats [4][R M] = mean0, rstd0 (the affine-free LayerNorm), mean1, rstd1 (kv_ln); a, m (null: all
+// ones) [R][M]; p, dp [R][D]; qvec [3][D] = LN(latent) g_q + b_q, qv = Wq of it, u = Wk^T qv
+struct FusionRowArgs {
+  const float* s; const float* g_kv; const float* b_kv; const float* temp; const float* bias; const float* m;
+  const float* qvec;
+  float* stats; float* a;              // forward: written where given (both or neither); backward: read
+  float* p;                            // forward: written
+  const float* dp; float* ds;          // backward
+  double* part;                        // backward: [chunks][3 D + 16] sums of du, dg_kv, db_kv, dbias[8], dscale[8]
+  int R, M, D;
+};
+struct FusionQueryArgs {
+  const float* latent; const float* g_q; const float* b_q; const float* Wq; const float* Wk;
+  float* qvec;                         // forward: written; backward: read
+  const float* sums;                   // backward: [3 D + 16] the reduced row sums
+  const float* temp;
+  float* d_latent; float* d_g_q; float* d_b_q; float* d_g_kv; float* d_b_kv; float* d_Wq; float* d_Wk;
+  float* d_temp; float* d_bias;
+  int M, D;
+};
+int fusion_row_chunks(int R);          // workgroups (partials) of the row backward
+hipError_t launch_fusion_query_forward(const FusionQueryArgs& a, hipStream_t s);
+hipError_t launch_fusion_query_backward(const FusionQueryArgs& a, hipStream_t s);
+hipError_t launch_fusion_rows_forward(const FusionRowArgs& a, hipStream_t s);
+hipError_t launch_fusion_rows_backward(const FusionRowArgs& a, hipStream_t s);
 
 // ------------------------------------------------------------------ vge_score.hip
 // d <= 256

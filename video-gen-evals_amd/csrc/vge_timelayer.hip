@@ -2,14 +2,8 @@
 // training on gfx950: a forward that keeps what the backward needs, and the backward to the input and all twelve
 // parameter tensors (vge_timelayer_forward / vge_timelayer_backward, formulas in include/vge.h).
 //
-//   tl_gemm_kernel     exact-f32 GEMM on v_mfma_f32_16x16x4_f32, one 64 x 64 output tile per workgroup, in the three
-//                      operand forms a layer needs:
-//                        <0,0,0>  C[m,n] = sum_k A[m,k] W[n,k]      the four forward GEMMs (x W^T)
-//                        <0,1,0>  C[m,n] = sum_k A[m,k] W[k,n]      the data gradients (dY W)
-//                        <1,1,1>  P[c][m,n] = sum_{r in chunk c} A[r,m] B[r,n]   the weight gradients (dY^T X), one f64
-//                                 partial per chunk of rows
-//                      with the epilogue  v = f32(sum) (+ bias[n]) (relu) (* mask[m,n]) (gate[m,n] <= 0 ? 0 : v)
-//                      (res[m,n] + v).
+//   tl_gemm_kernel     the exact-f32 GEMM of vge_f32gemm.h (shared with the linear and fusion nodes), in its three
+//                      operand forms, with vector loads: every extent of a layer is a multiple of 4.
 //   tl_attn_fwd_kernel one workgroup = one (sample, head): q, k, v [S <= 65][d <= 64] in LDS, the logits, the softmax,
 //                      P m_attn, o = (P m_attn) v.
 //   tl_attn_bwd_kernel one workgroup = one (sample, head): P again from q and k, then dv, dP, dS, dq, dk.
@@ -17,7 +11,7 @@
 //   tl_ln_bwd_kernel   one workgroup = 16 rows, one wave per row at a time: du (and du m), and the workgroup's f64
 //                      partials of dgamma / dbeta.
 //   tl_colsum_kernel   bias gradients: f64 column sums of one 64-row chunk.
-//   tl_reduce_kernel   adds f64 chunk partials in chunk order and rounds to f32 once.
+//   tl_reduce_kernel   (vge_f32gemm.h) adds f64 chunk partials in chunk order and rounds to f32 once.
 //
 // Summation.  A GEMM output's K products are summed in two levels: one MFMA chain per 16 products (exact f32
 // products, f32 adds), the chains added in f64, the sum rounded to f32 once.  The weight gradients do the same over
@@ -38,6 +32,8 @@
 #include "../../include/vge.h"
 #include "vge_core.h"
 #include "vge_error.h"
+#include "vge_f32gemm.h"
+#include "vge_node_args.h"
 #include "vge_lds_attr.h"
 
 namespace {
@@ -45,104 +41,10 @@ namespace {
 using vge::TimeAttnArgs;
 using vge::TimeGemmArgs;
 
-typedef double doublex4 __attribute__((ext_vector_type(4)));
-
-constexpr int TL_TILE = 64;        // output tile of the GEMM, both ways
-constexpr int TL_KSTEP = 32;       // K per LDS fill: two chains of 16
-constexpr int TL_LDT = 80;         // LDS row stride of a [k][64] operand tile: the 4 lane groups hit 4 x 16 banks
-constexpr int TL_WG_CHUNKS = 8;    // row chunks of a weight gradient
 constexpr int TL_LN_ROWS = 16;     // rows per workgroup of the LayerNorm backward
 constexpr int TL_CS_ROWS = 64;     // rows per workgroup of the column sums
 constexpr int TL_MAX_S = 65;
 constexpr float TL_EPS = 1e-5f;
-
-// ------------------------------------------------------------------------------------------------ GEMM
-// MC (A_MC / B_MC): the operand's M (N) index is the contiguous one (row = k); otherwise k is contiguous (row = m or n).
-// grid (ceil(M / 64), ceil(N / 64), chunks); chunks > 1 only with PARTIAL.  M is arbitrary; N and the contiguous
-// extents are multiples of 4, K (without PARTIAL) a multiple of 32.
-template <bool MC>
-__device__ __forceinline__ void tl_fill(float* T, const float* __restrict__ G, int ld, int mn0, int MN, int k0, int kend,
-                                        int tid) {
-  if (MC) {  // row k: 16 float4 along mn
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int k = (tid >> 4) + 16 * p, mn = (tid & 15) * 4;
-      floatx4 v = floatx4{0.f, 0.f, 0.f, 0.f};
-      if (k0 + k < kend && mn0 + mn < MN) v = *reinterpret_cast<const floatx4*>(G + (size_t)(k0 + k) * ld + mn0 + mn);
-      *reinterpret_cast<floatx4*>(T + k * TL_LDT + mn) = v;
-    }
-  } else {  // row mn: 8 float4 along k
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int mn = (tid >> 3) + 32 * p, k = (tid & 7) * 4;
-      floatx4 v = floatx4{0.f, 0.f, 0.f, 0.f};
-      if (mn0 + mn < MN && k0 + k < kend) v = *reinterpret_cast<const floatx4*>(G + (size_t)(mn0 + mn) * ld + k0 + k);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) T[(k + q) * TL_LDT + mn] = v[q];
-    }
-  }
-}
-
-template <bool A_MC, bool B_MC, bool PARTIAL>
-__global__ void __launch_bounds__(256) tl_gemm_kernel(TimeGemmArgs G) {
-  __shared__ __attribute__((aligned(16))) float As[TL_KSTEP * TL_LDT];
-  __shared__ __attribute__((aligned(16))) float Bs[TL_KSTEP * TL_LDT];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, il = lane & 15, g = lane >> 4;
-  const int m0 = blockIdx.x * TL_TILE, n0 = blockIdx.y * TL_TILE;
-  int k0 = 0, kend = G.K;
-  if (PARTIAL) {
-    k0 = blockIdx.z * G.k_per_chunk;
-    kend = min(G.K, k0 + G.k_per_chunk);
-  }
-  doublex4 acc[4];
-#pragma unroll
-  for (int rt = 0; rt < 4; ++rt) acc[rt] = doublex4{0.0, 0.0, 0.0, 0.0};
-  const floatx4 zero = floatx4{0.f, 0.f, 0.f, 0.f};
-  const bool col_live = n0 + wave * 16 < G.N;  // this wave's 16 columns exist (N is a multiple of 16)
-
-  for (int kb = k0; kb < kend; kb += TL_KSTEP) {
-    __syncthreads();  // the previous step's reads
-    tl_fill<A_MC>(As, G.A, G.lda, m0, G.M, kb, kend, tid);
-    tl_fill<B_MC>(Bs, G.B, G.ldb, n0, G.N, kb, kend, tid);
-    __syncthreads();
-    if (col_live) {
-#pragma unroll
-      for (int ch = 0; ch < TL_KSTEP / 16; ++ch) {
-        floatx4 part[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int k = ch * 16 + q * 4 + g;
-          const float b = Bs[k * TL_LDT + wave * 16 + il];
-#pragma unroll
-          for (int rt = 0; rt < 4; ++rt) part[rt] = mfma16x16x4(As[k * TL_LDT + rt * 16 + il], b, q == 0 ? zero : part[rt]);
-        }
-#pragma unroll
-        for (int rt = 0; rt < 4; ++rt) acc[rt] += __builtin_convertvector(part[rt], doublex4);
-      }
-    }
-  }
-  if (!col_live) return;
-  const int n = n0 + wave * 16 + il;
-#pragma unroll
-  for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int m = m0 + rt * 16 + 4 * g + r;
-      if (m >= G.M) continue;
-      if (PARTIAL) {
-        G.part[((size_t)blockIdx.z * G.M + m) * G.N + n] = acc[rt][r];
-        continue;
-      }
-      const size_t o = (size_t)m * G.ldc + n;
-      float v = (float)acc[rt][r];
-      if (G.bias) v += G.bias[n];
-      if (G.relu) v = v < 0.f ? 0.f : v;  // a NaN stays a NaN
-      if (G.mask) v *= G.mask[o];
-      if (G.gate) v = G.gate[o] <= 0.f ? 0.f : v;  // a NaN gate lets v through, as torch's relu backward does
-      if (G.res) v = G.res[o] + v;
-      G.C[o] = v;
-    }
-}
 
 // ------------------------------------------------------------------------------------------------ attention
 __device__ __forceinline__ int tl_ldq(int d) { return d + 1; }  // odd row stride: a column of rows is conflict-free
@@ -389,26 +291,11 @@ __global__ void __launch_bounds__(256) tl_colsum_kernel(const float* __restrict_
   part[(size_t)blockIdx.x * N + n] = s;
 }
 
-// out[e] = f32(sum over chunks, in chunk order, of part[chunk][e])
-__global__ void __launch_bounds__(256) tl_reduce_kernel(const double* __restrict__ part, int n_chunks, int n,
-                                                        float* __restrict__ out) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= n) return;
-  double s = 0.0;
-  for (int ch = 0; ch < n_chunks; ++ch) s += part[(size_t)ch * n + e];
-  out[e] = (float)s;
-}
-
 }  // namespace
 
 namespace vge {
 
-int timelayer_wgrad_chunks(int R, int* k_per_chunk) {
-  int per = (R + TL_WG_CHUNKS - 1) / TL_WG_CHUNKS;
-  per = (per + 15) & ~15;  // whole chains of 16 rows
-  if (k_per_chunk) *k_per_chunk = per;
-  return (R + per - 1) / per;
-}
+int timelayer_wgrad_chunks(int R, int* k_per_chunk) { return tl_wgrad_chunks(R, k_per_chunk); }
 int timelayer_ln_chunks(int R) { return (R + TL_LN_ROWS - 1) / TL_LN_ROWS; }
 int timelayer_colsum_chunks(int R) { return (R + TL_CS_ROWS - 1) / TL_CS_ROWS; }
 
@@ -418,17 +305,7 @@ hipError_t launch_timelayer_reduce(const double* part, int n_chunks, int n, floa
 }
 
 hipError_t launch_timelayer_gemm(const TimeGemmArgs& a, int form, hipStream_t s) {
-  TimeGemmArgs g = a;
-  const dim3 grid((a.M + TL_TILE - 1) / TL_TILE, (a.N + TL_TILE - 1) / TL_TILE, 1);
-  if (form == TIME_GEMM_NT) {
-    hipLaunchKernelGGL((tl_gemm_kernel<false, false, false>), grid, dim3(256), 0, s, g);
-  } else if (form == TIME_GEMM_NN) {
-    hipLaunchKernelGGL((tl_gemm_kernel<false, true, false>), grid, dim3(256), 0, s, g);
-  } else {
-    const int nch = timelayer_wgrad_chunks(a.K, &g.k_per_chunk);
-    hipLaunchKernelGGL((tl_gemm_kernel<true, true, true>), dim3(grid.x, grid.y, nch), dim3(256), 0, s, g);
-  }
-  return hipGetLastError();
+  return tl_launch_gemm(a, form, false, false, s);
 }
 
 hipError_t launch_timelayer_attn_forward(const TimeAttnArgs& a, hipStream_t s) {
@@ -479,25 +356,6 @@ hipError_t launch_timelayer_colsum(const float* src, int R, int N, double* part,
 // ------------------------------------------------------------------------------------------------ C ABI
 namespace {
 
-int fail(int code, const std::string& msg) {
-  vge::set_last_error(msg);
-  return code;
-}
-
-hipStream_t tl_stream(vge_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-
-struct Span {
-  const void* p;
-  size_t bytes;
-  const char* name;
-  bool optional;
-};
-
-bool overlap(const Span& a, const Span& b) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a.p), b0 = reinterpret_cast<uintptr_t>(b.p);
-  return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
-}
-
 bool tl_shape_ok(int B, int S, int D, int H, int F) {
   if (D < 32 || D > 256 || D % 32 != 0 || H < 1 || D % H != 0) return false;
   const int d = D / H;
@@ -511,24 +369,6 @@ int tl_shape(const char* fn, int B, int S, int D, int H, int F) {
               "dimension D / H that is a multiple of 16 and at most 64, F = 4 D, 1 <= S <= 65, B >= 1 and every tensor "
               "below 2^31 elements; got B " + std::to_string(B) + ", S " + std::to_string(S) + ", D " +
               std::to_string(D) + ", H " + std::to_string(H) + ", F " + std::to_string(F));
-}
-
-// null, alignment and aliasing of the listed buffers: the first n_in are inputs (they may alias each other), the
-// rest outputs (they may alias nothing); optional entries may be null
-int tl_buffers(const char* fn, const Span* sp, int n_in, int n) {
-  for (int i = 0; i < n; ++i) {
-    if (!sp[i].p) {
-      if (sp[i].optional) continue;
-      return fail(VGE_ERR_ARG, std::string(fn) + ": null " + sp[i].name);
-    }
-    if (reinterpret_cast<uintptr_t>(sp[i].p) & 15)
-      return fail(VGE_ERR_ARG, std::string(fn) + ": " + sp[i].name + " must be 16-byte aligned");
-  }
-  for (int i = n_in; i < n; ++i)
-    for (int k = 0; k < i; ++k)
-      if (sp[i].p && sp[k].p && overlap(sp[i], sp[k]))
-        return fail(VGE_ERR_ARG, std::string(fn) + ": " + sp[i].name + " must not alias " + sp[k].name);
-  return VGE_OK;
 }
 
 // workspace layouts, in floats (every offset a multiple of 4: R D is a multiple of 32)
@@ -566,12 +406,6 @@ TlBwdWs tl_bwd_ws(int B, int S, int D, int F) {
   w.total = w.cspart + 2 * (size_t)vge::timelayer_colsum_chunks(R) * F;
   return w;
 }
-
-#define HIPCHK(expr)                                                                                    \
-  do {                                                                                                  \
-    hipError_t _e = (expr);                                                                             \
-    if (_e != hipSuccess) return fail(VGE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
 
 TimeGemmArgs tl_gemm(const float* A, int lda, const float* Bm, int ldb, int M, int N, int K, float* C) {
   TimeGemmArgs g{};

@@ -66,7 +66,10 @@ EXPORTS = ["vge_featurize", "vge_featurize_layout", "vge_layout_feat_dim", "vge_
            "vge_tcl_grad_workspace_bytes", "vge_tcl_loss_grad", "vge_hardneg_loss_grad",
            "vge_convblock_workspace_bytes", "vge_convblock_forward_workspace_bytes", "vge_convblock_forward", "vge_convblock_backward",
            "vge_timelayer_workspace_bytes", "vge_timelayer_forward_workspace_bytes", "vge_timelayer_forward",
-           "vge_timelayer_backward"]
+           "vge_timelayer_backward",
+           "vge_linear_workspace_bytes", "vge_linear_forward", "vge_linear_backward",
+           "vge_fusion_workspace_bytes", "vge_fusion_forward_workspace_bytes", "vge_fusion_forward",
+           "vge_fusion_backward"]
 
 
 class VgeError(RuntimeError):
@@ -339,6 +342,13 @@ def load() -> C.CDLL:
         "vge_timelayer_forward_workspace_bytes": [i32] * 5,
         "vge_timelayer_forward": [vp] * 17 + [i32] * 5 + [vp] * 7 + [C.c_size_t, vp],
         "vge_timelayer_backward": [vp] * 18 + [i32] * 5 + [vp] * 14 + [C.c_size_t, vp],
+        "vge_linear_workspace_bytes": [i32] * 3,
+        "vge_linear_forward": [vp, i32, vp, vp, i32, i32, i32, vp],
+        "vge_linear_backward": [vp, vp, i32, vp, vp, vp, vp, C.c_size_t, i32, i32, i32, vp],
+        "vge_fusion_workspace_bytes": [i32] * 3,
+        "vge_fusion_forward_workspace_bytes": [i32] * 3,
+        "vge_fusion_forward": [vp] * 13 + [i32] * 3 + [vp] * 6 + [C.c_size_t, vp],
+        "vge_fusion_backward": [vp] * 18 + [i32] * 3 + [vp] * 13 + [C.c_size_t, vp],
     }
     for name, args in sig.items():
         f = getattr(lib, name)
@@ -351,6 +361,9 @@ def load() -> C.CDLL:
     lib.vge_convblock_forward_workspace_bytes.restype = C.c_size_t
     lib.vge_timelayer_workspace_bytes.restype = C.c_size_t
     lib.vge_timelayer_forward_workspace_bytes.restype = C.c_size_t
+    lib.vge_linear_workspace_bytes.restype = C.c_size_t
+    lib.vge_fusion_workspace_bytes.restype = C.c_size_t
+    lib.vge_fusion_forward_workspace_bytes.restype = C.c_size_t
     lib.vge_jpeg_entropy_workspace_bytes.restype = C.c_size_t
     lib.vge_jpeg_entropy_decode_workspace_bytes.restype = C.c_size_t
     lib.vge_ingest_decode_device_workspace_bytes.restype = C.c_size_t

@@ -24,8 +24,14 @@ with conv_backend="hip", the residual blocks of the movement encoders: each bloc
 (vge.convblock.ConvBlockFunction) on the forward and backward kernels of vge_convblock.hip, with the same parameters
 under the same state-dict keys.  With time_backend="hip" each layer of the temporal stack is one autograd node as well
 (vge.timelayer.TimeLayerFunction) on the kernels of vge_timelayer.hip, again on the nn.TransformerEncoder's own
-parameters.  The defaults conv_backend="torch" and time_backend="torch" are the graph described above, unchanged.  The
-stem, the projection and the fusion run on torch under every backend.
+parameters.  With linear_backend="hip" the stem and the projection of every movement encoder go through
+vge.linear.LinearFunction on the kernels of vge_linear.hip -- the stem reads its columns of x in place, as a view with
+a row stride --, and with fusion_backend="hip" the per-modality LayerNorm and the fusion are one node
+(vge.fusion.FusionFunction, vge_fusion.hip) in the folded form: Wk meets the query, not the tokens, and Wv and Wo run
+over the pooled rows.  The four switches are independent; their defaults, "torch", are the graph described above,
+unchanged.  With all four on "hip" every GEMM and every sum across samples of a step's forward and backward runs in
+the project's kernels; what stays on torch is elementwise or per row (the additions, positions, dropout masks,
+F.normalize) and the concatenation of CLS.
 """
 from __future__ import annotations
 
@@ -38,12 +44,16 @@ import torch.nn.functional as F
 from torch.nn.attention import SDPBackend, sdpa_kernel
 
 from .convblock import convblock
+from .fusion import fusion, fusion_params
+from .linear import linear
 from .timelayer import draw_masks, layer_params, timelayer
 
 KERNEL_SIZE = 5
 DILATIONS = (1, 2, 4, 8)
 CONV_BACKENDS = ("torch", "hip")
 TIME_BACKENDS = ("torch", "hip")
+LINEAR_BACKENDS = ("torch", "hip")
+FUSION_BACKENDS = ("torch", "hip")
 
 
 def _check_conv_backend(conv_backend: str) -> str:
@@ -56,6 +66,18 @@ def _check_time_backend(time_backend: str) -> str:
     if time_backend not in TIME_BACKENDS:
         raise ValueError(f"time_backend must be one of {TIME_BACKENDS}, got {time_backend!r}")
     return time_backend
+
+
+def _check_linear_backend(linear_backend: str) -> str:
+    if linear_backend not in LINEAR_BACKENDS:
+        raise ValueError(f"linear_backend must be one of {LINEAR_BACKENDS}, got {linear_backend!r}")
+    return linear_backend
+
+
+def _check_fusion_backend(fusion_backend: str) -> str:
+    if fusion_backend not in FUSION_BACKENDS:
+        raise ValueError(f"fusion_backend must be one of {FUSION_BACKENDS}, got {fusion_backend!r}")
+    return fusion_backend
 
 
 def _uniform_fan_in(shape, fan_in: int) -> nn.Parameter:
@@ -127,17 +149,20 @@ class _Linear(nn.Module):
 
 
 class _MovementEncoder(nn.Module):
-    def __init__(self, d_in: int, d_out: int, p: float, conv_backend: str = "torch"):
+    def __init__(self, d_in: int, d_out: int, p: float, conv_backend: str = "torch", linear_backend: str = "torch"):
         super().__init__()
+        self.linear_backend = _check_linear_backend(linear_backend)
         self.stem = _ConvWeight(d_in, d_out, 1)
         self.blocks = nn.ModuleList([_Block(d_out, dil, p, conv_backend) for dil in DILATIONS])
         self.proj = _Linear(d_out, d_out)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        y = self.stem(x)
+        hip = self.linear_backend == "hip"
+        # x is a column slice of the feature tensor: linear() reads it in place
+        y = linear(x, self.stem.weight.view(self.stem.weight.shape[:2])) if hip else self.stem(x)
         for blk in self.blocks:
             y = blk(y)
-        return self.proj(y)
+        return linear(y, self.proj.weight) if hip else self.proj(y)
 
 
 class _Fusion(nn.Module):
@@ -178,10 +203,13 @@ class _Positions(nn.Module):
 class HumanActionScorer(nn.Module):
     def __init__(self, dims_map_raw: Dict[str, int], dims_map_diff: Dict[str, int], d_model: int = 256,
                  latent_dim: int = 128, time_layers: int = 4, time_heads: int = 8, dropout: float = 0.1,
-                 conv_backend: str = "torch", time_backend: str = "torch"):
+                 conv_backend: str = "torch", time_backend: str = "torch", linear_backend: str = "torch",
+                 fusion_backend: str = "torch"):
         super().__init__()
         self.conv_backend = _check_conv_backend(conv_backend)
         self.time_backend = _check_time_backend(time_backend)
+        self.linear_backend = _check_linear_backend(linear_backend)
+        self.fusion_backend = _check_fusion_backend(fusion_backend)
         if not isinstance(dims_map_raw, dict) or not isinstance(dims_map_diff, dict):
             raise ValueError("dims_map_raw and dims_map_diff must be dicts of {modality: dim}")
         if set(dims_map_raw) != set(dims_map_diff):
@@ -192,10 +220,12 @@ class HumanActionScorer(nn.Module):
         self.hyper_parameters = {"d_model": int(d_model), "latent_dim": int(latent_dim),
                                  "time_layers": int(time_layers), "time_heads": int(time_heads),
                                  "dropout": float(dropout)}
-        self.state_enc = nn.ModuleDict({m: _MovementEncoder(self.dims_raw[m], d_model, dropout, conv_backend)
+        self.state_enc = nn.ModuleDict({m: _MovementEncoder(self.dims_raw[m], d_model, dropout, conv_backend,
+                                                            linear_backend)
                                         for m in self.modalities})
         with_diff = [m for m in self.modalities if self.dims_diff[m] > 0]
-        self.motion_enc = nn.ModuleDict({m: _MovementEncoder(self.dims_diff[m], d_model, dropout, conv_backend)
+        self.motion_enc = nn.ModuleDict({m: _MovementEncoder(self.dims_diff[m], d_model, dropout, conv_backend,
+                                                             linear_backend)
                                          for m in with_diff}) if with_diff else None
         self.fusion = _Fusion(d_model, len(self.modalities), dropout)
         self.cls = nn.Parameter(torch.randn(1, 1, d_model))
@@ -228,8 +258,16 @@ class HumanActionScorer(nn.Module):
             s = self.state_enc[m](raw[m])
             if self.dims_diff[m] > 0:
                 s = s + self.motion_enc[m](diff[m])
-            per_mod.append(F.layer_norm(s, s.shape[-1:]))
-        frames = self.fusion(torch.stack(per_mod, dim=2))
+            per_mod.append(s if self.fusion_backend == "hip" else F.layer_norm(s, s.shape[-1:]))
+        if self.fusion_backend == "hip":
+            # the node owns the affine-free LayerNorm; the multiplier self.fusion.dropout would apply to the attention
+            # weights is drawn where the torch backend draws it
+            p = self.fusion.dropout.p
+            m_attn = F.dropout(torch.ones(x.shape[0], x.shape[1], len(per_mod), dtype=x.dtype, device=x.device), p,
+                               True) if self.training and p > 0 else None
+            frames = fusion(torch.stack(per_mod, dim=2), fusion_params(self.fusion), m_attn)
+        else:
+            frames = self.fusion(torch.stack(per_mod, dim=2))
         tokens = torch.cat([self.cls.expand(x.shape[0], -1, -1), frames], dim=1)
         if self.time_backend == "hip":
             tokens = self._temporal_hip(self.pos_enc(tokens))

@@ -593,3 +593,131 @@ def timelayer_backward(dy: torch.Tensor, x: torch.Tensor, params: Sequence[torch
                                        *[_ptr(t) for t in saved], B, S, D, int(heads), F_, *[_ptr(t) for t in out],
                                        _ptr(workspace), wsb, _stream(x.device)), "vge_timelayer_backward")
     return tuple(out)
+
+
+def _linear_check(fn: str, x: torch.Tensor, W: torch.Tensor,
+                  named: Sequence[Tuple[str, Optional[torch.Tensor], Tuple[int, ...]]]) -> Tuple[int, int, int, int]:
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_cuda or (x.shape[1] > 1 and x.stride(1) != 1) or \
+            (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        raise L.VgeError(f"{fn}: x must be a float32 [R,K] device tensor with unit column stride and a row stride >= K, "
+                         f"got {x.dtype} {tuple(x.shape)} strides {tuple(x.stride())}")
+    R, K = x.shape
+    if W.dim() != 2 or int(W.shape[1]) != K:
+        raise L.VgeError(f"{fn}: W must be [N,{K}], got {tuple(W.shape)}")
+    N = int(W.shape[0])
+    for name, t, shape in [("W", W, (N, K))] + [e for e in named if e[1] is not None]:
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != x.device:
+            raise L.VgeError(f"{fn}: {name} must be a contiguous float32 {list(shape)} tensor on {x.device}, got "
+                             f"{t.dtype} {tuple(t.shape)} on {t.device}")
+    return R, K, N, (int(x.stride(0)) if R > 1 else max(K, int(x.stride(0))))
+
+
+def linear_forward(x: torch.Tensor, W: torch.Tensor, y: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = x W^T (vge_linear_forward, include/vge.h) on the current stream.  x float32 [R,K], read in place: a column
+    slice of a wider tensor keeps its row stride; W [N,K]; y: the [R,N] tensor to write, or None."""
+    lib = L.load()
+    R, K, N, ldx = _linear_check("linear_forward", x, W, [("y", y, (x.shape[0], int(W.shape[0])))])
+    if y is None:
+        y = torch.empty((R, N), dtype=torch.float32, device=x.device)
+    L.check(lib.vge_linear_forward(x.data_ptr(), ldx, _ptr(W), _ptr(y), R, K, N, _stream(x.device)), "vge_linear_forward")
+    return y
+
+
+def linear_backward(dy: torch.Tensor, x: torch.Tensor, W: torch.Tensor, need_dx: bool = True, out=None,
+                    workspace: Optional[torch.Tensor] = None):
+    """The linear map's backward (vge_linear_backward) on the current stream -> (dx [R,K] or None, dW [N,K]).  out:
+    the two result tensors (dx None to skip it), or None; workspace: a float32 tensor to use, or None."""
+    lib = L.load()
+    N_ = int(W.shape[0]) if W.dim() == 2 else -1
+    dx, dW = out if out is not None else (None, None)
+    R, K, N, ldx = _linear_check("linear_backward", x, W, [("dy", dy, (x.shape[0], N_)), ("dx", dx, tuple(x.shape)),
+                                                           ("dW", dW, tuple(W.shape))])
+    if out is None:
+        dx = torch.empty((R, K), dtype=torch.float32, device=x.device) if need_dx else None
+        dW = torch.empty_like(W)
+    wsb = int(lib.vge_linear_workspace_bytes(R, K, N))
+    if workspace is None:
+        workspace = torch.empty(max(wsb, 16) // 4, dtype=torch.float32, device=x.device)
+    else:
+        wsb = workspace.numel() * 4
+    L.check(lib.vge_linear_backward(_ptr(dy), x.data_ptr(), ldx, _ptr(W), _ptr(dx), _ptr(dW), _ptr(workspace), wsb, R,
+                                    K, N, _stream(x.device)), "vge_linear_backward")
+    return dx, dW
+
+
+# the eleven parameter tensors of the fusion, in the order of vge_fusion_forward
+FUSION_PARAMS = ("latent", "q_ln_weight", "q_ln_bias", "kv_ln_weight", "kv_ln_bias", "Wq", "Wk", "Wv", "Wo",
+                 "logit_temp", "logit_bias")
+FUSION_SAVED = ("stats", "a", "p", "vp")
+
+
+def _fusion_shapes(R: int, M: int, D: int) -> Dict[str, Tuple[int, ...]]:
+    return {"s": (R, M, D), "ds": (R, M, D), "out": (R, D), "d_out": (R, D), "latent": (D,), "q_ln_weight": (D,),
+            "q_ln_bias": (D,), "kv_ln_weight": (D,), "kv_ln_bias": (D,), "Wq": (D, D), "Wk": (D, D), "Wv": (D, D),
+            "Wo": (D, D), "logit_temp": (M,), "logit_bias": (M,), "m_attn": (R, M), "stats": (4, R * M), "a": (R, M),
+            "p": (R, D), "vp": (R, D)}
+
+
+def _fusion_check(fn: str, s: torch.Tensor, params: Sequence[torch.Tensor],
+                  named: Sequence[Tuple[str, Optional[torch.Tensor]]]) -> Tuple[int, int, int, Dict]:
+    if s.dim() != 3 or s.dtype != torch.float32 or not s.is_contiguous():
+        raise L.VgeError(f"{fn}: s must be a contiguous float32 [R,M,D] tensor, got {s.dtype} {tuple(s.shape)}")
+    if len(params) != 11:
+        raise L.VgeError(f"{fn}: params must be the eleven tensors {FUSION_PARAMS}")
+    R, M, D = s.shape
+    shapes = _fusion_shapes(R, M, D)
+    for name, t in list(zip(FUSION_PARAMS, params)) + [(n, t) for n, t in named if t is not None]:
+        key = name[2:] if name.startswith("d_") and name != "d_out" else name
+        if t.dtype != torch.float32 or tuple(t.shape) != shapes[key] or not t.is_contiguous() or t.device != s.device:
+            raise L.VgeError(f"{fn}: {name} must be a contiguous float32 {list(shapes[key])} tensor on {s.device}, got "
+                             f"{t.dtype} {tuple(t.shape)} on {t.device}")
+    return R, M, D, shapes
+
+
+def fusion_forward(s: torch.Tensor, params: Sequence[torch.Tensor], m_attn: Optional[torch.Tensor] = None,
+                   save: bool = True, out: Optional[torch.Tensor] = None, saved=None,
+                   workspace: Optional[torch.Tensor] = None):
+    """The modality fusion (vge_fusion_forward, include/vge.h) on the current stream -> (out [R,D], saved), saved =
+    (stats, a, p, vp) for fusion_backward, or None with save=False (nothing but out is written).  s [R,M,D] float32: the
+    per-modality sums before the affine-free LayerNorm; params: the eleven tensors of FUSION_PARAMS (latent as [D]);
+    m_attn [R,M]: the dropout multiplier or None; out / saved: the tensors to write, or None."""
+    lib = L.load()
+    given = tuple(saved) if (save and saved is not None) else (None,) * 4
+    R, M, D, shapes = _fusion_check("fusion_forward", s, params,
+                                    [("m_attn", m_attn), ("out", out)] + list(zip(FUSION_SAVED, given)))
+    if out is None:
+        out = torch.empty(shapes["out"], dtype=torch.float32, device=s.device)
+    if save and saved is None:
+        saved = tuple(torch.empty(shapes[n], dtype=torch.float32, device=s.device) for n in FUSION_SAVED)
+    keep = tuple(saved) if save else (None,) * 4
+    wsb = int(lib.vge_fusion_forward_workspace_bytes(R, M, D))
+    if workspace is None:
+        workspace = torch.empty(max(wsb, 16) // 4, dtype=torch.float32, device=s.device)
+    else:
+        wsb = workspace.numel() * 4
+    L.check(lib.vge_fusion_forward(_ptr(s), *[_ptr(p) for p in params], _ptr(m_attn), R, M, D, *[_ptr(t) for t in keep],
+                                   _ptr(out), _ptr(workspace), wsb, _stream(s.device)), "vge_fusion_forward")
+    return out, (tuple(saved) if save else None)
+
+
+def fusion_backward(d_out: torch.Tensor, s: torch.Tensor, params: Sequence[torch.Tensor], saved,
+                    m_attn: Optional[torch.Tensor] = None, out=None, workspace: Optional[torch.Tensor] = None):
+    """The fusion's backward (vge_fusion_backward) on the current stream -> (ds, then the eleven parameter gradients in
+    FUSION_PARAMS order).  saved: fusion_forward's (stats, a, p, vp) of the same s, params and m_attn; out: the twelve
+    result tensors, or None; workspace: a float32 tensor to use, or None."""
+    lib = L.load()
+    named = [("d_out", d_out), ("m_attn", m_attn)] + list(zip(FUSION_SAVED, saved))
+    if out is not None:
+        named += list(zip(("ds",) + tuple("d_" + n for n in FUSION_PARAMS), out))
+    R, M, D, shapes = _fusion_check("fusion_backward", s, params, named)
+    if out is None:
+        out = tuple(torch.empty(shapes[n], dtype=torch.float32, device=s.device) for n in ("ds",) + FUSION_PARAMS)
+    wsb = int(lib.vge_fusion_workspace_bytes(R, M, D))
+    if workspace is None:
+        workspace = torch.empty(max(wsb, 16) // 4, dtype=torch.float32, device=s.device)
+    else:
+        wsb = workspace.numel() * 4
+    L.check(lib.vge_fusion_backward(_ptr(d_out), _ptr(s), *[_ptr(p) for p in params], _ptr(m_attn),
+                                    *[_ptr(t) for t in saved], R, M, D, *[_ptr(t) for t in out], _ptr(workspace), wsb,
+                                    _stream(s.device)), "vge_fusion_backward")
+    return tuple(out)

@@ -16,7 +16,9 @@ this library's HIP kernels.  The module's forward and backward (vge.model.HumanA
 torch's kernels: the hand-written encoder keeps no activations and has no backward.  With conv_backend="hip" the
 residual blocks of the movement encoders run on vge_convblock.hip's forward and backward kernels instead
 (vge.convblock), and with time_backend="hip" the layers of the temporal stack run on vge_timelayer.hip's
-(vge.timelayer); both default to "torch" and are independent of each other.
+(vge.timelayer); with linear_backend="hip" the stems and projections run on vge_linear.hip's (vge.linear) and with
+fusion_backend="hip" the per-modality LayerNorm and the fusion on vge_fusion.hip's (vge.fusion).  All four default to
+"torch" and are independent of each other.
 
 Differences from the reference, all deliberate: the sampler is seeded (default_rng(seed); the reference's is not), the
 shuffle tables come from a CPU generator seeded with `seed` rather than torch's global one, dropout masks come from
@@ -153,10 +155,10 @@ def train(real_meshes_dir: str, real_kp_dir: Optional[str], save_dir: str, epoch
           hard_weight: float = 10.0, eval_batch: int = 2048, ingest: str = "host", device="cuda",
           loss_backend: str = "hip", model_kwargs: Optional[dict] = None, compute: str = "f32x3",
           init_state_dict: Optional[dict] = None, log=None, conv_backend: str = "torch",
-          time_backend: str = "torch") -> List[dict]:
+          time_backend: str = "torch", linear_backend: str = "torch", fusion_backend: str = "torch") -> List[dict]:
     """Exp_TCL_Hard_V2Plus.run (train.py:433-467) -> one record per epoch: {"epoch", "train_loss", "steps",
     "skipped_steps", "lr", "eval_loss", "components", "n_batches", "skipped_batches", "centroid_distance",
-    "class_distances", "validated_by", "conv_backend", "time_backend", "checkpoint" (the file written this epoch, or None)}.  save_dir receives
+    "class_distances", "validated_by", "conv_backend", "time_backend", "linear_backend", "fusion_backend", "checkpoint" (the file written this epoch, or None)}.  save_dir receives
     label_mapping.json once and best_eval_epoch{e:03d}_loss{loss:.4f}.pt whenever the held-out loss improves.
     model_kwargs: d_model / time_layers / time_heads of another shape; init_state_dict: initial weights."""
     from . import eval as E
@@ -175,7 +177,8 @@ def train(real_meshes_dir: str, real_kp_dir: Optional[str], save_dir: str, epoch
     sampler = PKBatchSampler(label_list, P=P, K=K, drop_last=True, generator=np.random.default_rng(seed))
 
     model = HumanActionScorer(dp.dims_raw, dp.dims_diff, dropout=dropout, conv_backend=conv_backend,
-                              time_backend=time_backend, **(model_kwargs or {}))
+                              time_backend=time_backend, linear_backend=linear_backend,
+                              fusion_backend=fusion_backend, **(model_kwargs or {}))
     if init_state_dict is not None:
         model.load_state_dict({k: torch.as_tensor(np.asarray(v)) for k, v in init_state_dict.items()})
     model.to(dev).train()
@@ -199,7 +202,7 @@ def train(real_meshes_dir: str, real_kp_dir: Optional[str], save_dir: str, epoch
                 skipped += 1
         rec = {"epoch": epoch + 1, "train_loss": total / max(1, len(sampler)), "steps": steps,
                "skipped_steps": skipped, "lr": float(scheduler.get_last_lr()[0]), "conv_backend": conv_backend,
-               "time_backend": time_backend}
+               "time_backend": time_backend, "linear_backend": linear_backend, "fusion_backend": fusion_backend}
         val = validate_module(model, dp, real_meshes_dir, real_kp_dir, clip_len, stride, eval_batch, seed, compute,
                               hard_weight)
         rec["eval_loss"] = val.pop("loss")
@@ -242,6 +245,10 @@ def main(argv=None):
                     help="the movement encoders' residual blocks: torch ops, or the forward / backward HIP kernels")
     ap.add_argument("--time-backend", default="torch", choices=["torch", "hip"],
                     help="the temporal stack's layers: torch's nn.TransformerEncoder, or the forward / backward HIP kernels")
+    ap.add_argument("--linear-backend", default="torch", choices=["torch", "hip"],
+                    help="the movement encoders' stems and projections: torch matmuls, or the forward / backward HIP kernels")
+    ap.add_argument("--fusion-backend", default="torch", choices=["torch", "hip"],
+                    help="the per-modality LayerNorm and the fusion: torch ops, or the forward / backward HIP kernels")
     ap.add_argument("--d-model", type=int, default=256)
     ap.add_argument("--time-layers", type=int, default=4)
     ap.add_argument("--time-heads", type=int, default=8)
@@ -254,6 +261,7 @@ def main(argv=None):
     train(a.real_meshes, a.real_kp, a.save_dir, epochs=a.epochs, lr=a.lr, P=a.P, K=a.K, clip_len=a.clip_len,
           stride=a.stride, seed=a.seed, dropout=a.dropout, hard_weight=a.hard_weight, eval_batch=a.eval_batch,
           ingest=a.ingest, device=a.device, loss_backend=a.loss_backend, conv_backend=a.conv_backend, time_backend=a.time_backend,
+          linear_backend=a.linear_backend, fusion_backend=a.fusion_backend,
           model_kwargs={"d_model": a.d_model, "time_layers": a.time_layers, "time_heads": a.time_heads},
           log=lambda rec: print(json.dumps(rec), flush=True))
     return 0
